@@ -15,6 +15,7 @@ processes its own 32-image shard (configs[3] = 8 x 32).
 Prints ONE JSON line (rank 0) with the driver's keys plus `roofline` (dominant kernel, timed live
 with hipEvents on the launch stream) and `cpu_baseline` (the CPU oracle = PyTorch-CPU fp32
 restatement of the reference + SciPy L-BFGS-B, timed on this host on a bounded sample).
+`--dump-outputs DIR` also writes the last timed step's detection records to DIR/records.npy, to compare two builds.
 """
 import argparse
 import json
@@ -76,7 +77,35 @@ def parse_args():
     ap.add_argument('--force-launch', action='store_true', help='go through the rank launcher even for --gpus 1 (rehearses the N > 1 path: process group, RCCL all-gather)')
     ap.add_argument('--rehearse-one-gpu', action='store_true', help='DIAGNOSTIC: the N ranks of --gpus N all run on GPU 0 and exchange their records over gloo through host memory (RCCL refuses duplicate devices): the whole N > 1 code path - shards, pipelined gather, ordering, diagnostics - on a one-GPU box; the line is marked INVALID')
     ap.add_argument('--dry-launch', action='store_true', help='launcher rehearsal over gloo on CPU tensors, no GPU and no hot path (line marked INVALID)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step handed its caller (the (world*B, topk, 32) detection '
+                         'records) as DIR/records.npy (float32, at most 64 MB: a fixed seeded sample of images beyond that); '
+                         'inputs are seeded, so two builds run with the same arguments can be compared output for output')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """Writes each tensor of `arrays` (name -> tensor) as d/<name>.npy in float32 (float64 stays float64).  If they exceed
+    DUMP_BUDGET_BYTES together, each keeps a fixed seeded sample of its rows (first axis), and d/<name>_rows.npy says which."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    for name, a in arrs.items():
+        if total > DUMP_BUDGET_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * (DUMP_BUDGET_BYTES - 2 ** 20) // total))
+            rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(d, name + '_rows.npy'), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(a))
 
 
 def _best_median(ts):
@@ -577,6 +606,8 @@ def dry_launch(args, world, rank):
     dt, multi = multi_diagnostics(world, B, args.steps, dt, rec, local, dev, None, _startup_s(t0))
     multi['block_ranks'] = [int(v) for v in rec.reshape(world, B, topk, rdist.RECORD)[:, 0, 0, 0].tolist()]
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {'records': rec})
         print(json.dumps({'metric': 'images_per_sec', 'value': None, 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
                           'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
                           'vs_baseline': None, 'dtype': 'fp16', 'data': 'synthetic',
@@ -766,6 +797,8 @@ def main():
             dist.all_gather_object(notes, wcache_note)
             multi['shared_weight_cache'] = {'dir': wcache_note['dir'], 'per_rank': [{k: n[k] for k in ('rank', 'hits', 'misses', 'plan_build_s')} for n in notes],
                                             'note': 'rank 0 folds + packs (misses) and writes the file, ranks >= 1 build their plan from it (hits) behind a barrier'}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'records': rec})          # the last timed step's records, before anything else runs
 
     if rank == 0:
         ms_step = dt / args.steps * 1e3

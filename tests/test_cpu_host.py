@@ -503,6 +503,37 @@ def test_bench_launcher_dry_launch(n):
     assert 'INVALID' in out and out['value'] is None
 
 
+def test_bench_dump_outputs_dry_launch(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's gathered records as DIR/records.npy (float32), identical from run to
+    run with the same arguments; `--steps` is echoed and ms_per_step reported."""
+    import json
+    outs = []
+    for k in range(2):
+        d = str(tmp_path / ('run%d' % k))
+        r = _run_bench(['--gpus', '2', '--dry-launch', '--steps', '3', '--warmup', '1', '--batch', '4', '--dump-outputs', d])
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
+        assert line['steps'] == 3 and line['ms_per_step'] > 0
+        assert sorted(os.listdir(d)) == ['records.npy']
+        outs.append(np.load(os.path.join(d, 'records.npy')))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (8, 100, rdist.RECORD)
+    np.testing.assert_array_equal(outs[0], outs[1])
+    assert outs[0][:, 0, 0].tolist() == [0.0] * 4 + [1.0] * 4          # both ranks' blocks, in rank order
+
+
+def test_bench_dump_outputs_budget(tmp_path):
+    """Outputs over the 64 MB budget keep a fixed seeded sample of rows, and say which rows."""
+    import bench
+    big = torch.arange(96 * 2 ** 18, dtype=torch.float32).reshape(96, 2 ** 18)          # 96 MB
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), {'records': big, 'n': torch.arange(96, dtype=torch.int32)})
+    a, rows = np.load(str(tmp_path / '0' / 'records.npy')), np.load(str(tmp_path / '0' / 'records_rows.npy'))
+    assert a.dtype == np.float32 and rows.dtype == np.float64 and np.load(str(tmp_path / '0' / 'n.npy')).dtype == np.float32
+    assert sum(os.path.getsize(str(tmp_path / '0' / f)) for f in os.listdir(str(tmp_path / '0'))) <= bench.DUMP_BUDGET_BYTES
+    np.testing.assert_array_equal(a, big.numpy()[rows.astype(np.int64)])
+    np.testing.assert_array_equal(a, np.load(str(tmp_path / '1' / 'records.npy')))
+
+
 def test_bench_refuses_world_size_mismatch():
     """Under a launcher that started a different number of ranks than --gpus claims, bench.py exits non-zero (it used to
     print a note and measure WORLD_SIZE ranks silently)."""

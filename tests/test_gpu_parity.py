@@ -1081,6 +1081,27 @@ def test_bench_spawn_path_nccl_world1(dev):
     assert out['multi_gpu']['allgather_us_last_step'] > 0 and out['value'] > 0
 
 
+def test_bench_dump_outputs(dev, tmp_path):
+    """`bench.py --dump-outputs DIR`: the records the last timed step handed its caller, as DIR/records.npy (float32, (B, topk, 32)),
+    with a detection in every image of the seeded workload; `--steps` sets the timed steps and ms_per_step is reported."""
+    import subprocess, sys, os, json
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = str(tmp_path / 'out')
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--batch', '4', '--height', '128',
+                        '--width', '256', '--backbone', 'RESNET-18', '--no-cpu-baseline', '--no-parity', '--no-sparse-probe', '--dump-outputs', d],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
+    assert out['steps'] == 3 and out['ms_per_step'] > 0
+    rec = np.load(os.path.join(d, 'records.npy'))
+    assert rec.dtype == np.float32 and rec.shape == (4, 100, 32) and np.isfinite(rec).all()
+    n = (rec[..., 31] > 0).sum(1)                          # flag column: valid records per image
+    assert n.sum() == out['config']['detections_per_batch_rank0']
+
+
 def test_bench_line_parity_of_the_default_solver(dev):
     """The default `python bench.py` line (DLA-34 bs=32 384x1280; few steps, no CPU baseline here) runs the PUBLISHED solver form in
     its timed step and its stage parity - the device decode kernels on the oracle's logits with 16 cuboids planted per image -
