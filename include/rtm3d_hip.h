@@ -404,6 +404,47 @@ size_t rtm3d_verify_softmax_workspace_bytes(int B, int C, int n_u);
 int rtm3d_verify_softmax_fuse_f32(void* stream, const rtm3d_vtensor* z_in, const rtm3d_vtensor* z_out, int n_u,
                                   const rtm3d_vtensor* u, int B, int H, int W, int C, void* d_workspace);
 
+/* ------------------------------------------------------------------ MXFP8 head convolutions (opt-in; csrc/conv_mx8.hip)
+ * The Python layer's head_precision='mxfp8' (rtm3d_amd/plan.py): the fused map z is quantised once, the dilation-6 and
+ * dilation-1 head convs run on block-scaled e4m3 operands (v_mfma_scale_f32_32x32x64_f8f6f4), the last one writes the fp16
+ * tensor rtm3d_op_headout reads.  Added in ABI 9 without changing any existing declaration.
+ *
+ * MX8 tensor: [B][H+2*pad][W+2*pad][C] OCP e4m3fn bytes and a scale plane [B][H+2*pad][W+2*pad][C/32] of E8M0 bytes
+ * (value = e4m3 * 2^(scale - 127)); C % 32 == 0.  The zero border (scale 127) is written once at creation.  MX8 tensor ids
+ * are their own namespace: they are accepted only by the functions below.
+ * Quantisation (OCP MX v1.0, host restatement: rtm3d_amd/mx8.py): per 32 channels of a pixel shared_exp =
+ * floor(log2(amax)) - 8 clamped to [-127, 127] (all-zero block: 127 - i.e. exponent 0), each element round-to-nearest-even
+ * e4m3(x / 2^shared_exp) saturated to +-448.                                                                          */
+int rtm3d_tensor_create_mx8(rtm3d_ctx* ctx, int B, int H, int W, int C, int pad, int* id);
+/* Dequantised fp32 NCHW copy of channels [c0, c0+C) of the interior (synchronous; tests).                              */
+int rtm3d_tensor_download_mx8(rtm3d_ctx* ctx, int id, int c0, int C, float* h_nchw);
+/* The whole padded arrays, borders included: h_data B*Hp*Wp*C bytes, h_scale B*Hp*Wp*C/32 bytes (synchronous; tests).   */
+int rtm3d_tensor_download_mx8_raw(rtm3d_ctx* ctx, int id, void* h_data, void* h_scale);
+int rtm3d_tensor_upload_mx8_raw(rtm3d_ctx* ctx, int id, const void* h_data, const void* h_scale);
+/* Quantise `channels` (multiple of 32) channels from in_coff (multiple of 8) of an fp16 tensor into out_coff (multiple of
+ * 32) of an MX8 tensor of the same B, H, W.  Interior pixels only.                                                      */
+int rtm3d_op_quant_mx8(rtm3d_ctx* ctx, int in_tensor, int in_coff, int out_tensor, int out_coff, int channels);
+/* Stride-1 convolution over an MX8 input onto a map of the same size: output pixel (n, y, x), channels
+ * out_coff[g] + [0, cout) = bias + sum over taps t and channels c of  w[g][co][t][c] * in(n, y + tap_dy[t], x + tap_dx[t],
+ * in_coff[g] + c), then ReLU (relu != 0), stored as MX8 (one scale per 32 output channels of a pixel, the rule above) or as
+ * fp16 NHWC (out_fp16 = 1, out_tensor is then an ordinary tensor id).  cin % 64 == 0, cout % 256 == 0, in_coff[g] % 64 ==
+ * 0, the input tensor's C % 64 == 0; every tap must stay inside the padded input.
+ * Blobs, kt = (cin / 64) * ntaps k-steps in the order k = tap * (cin / 64) + chunk:
+ *   w_blob      e4m3  [groups][cout / 256][kt][256 rows = output channel % 256][64 = channel chunk * 64 + j]
+ *   wscale_blob E8M0  [groups][cout / 256][kt][256 rows][2]   (the scales of channels [0, 32) and [32, 64) of the chunk)
+ *   bias_blob   fp32  [groups][cout]  (BN folded)                                                                   */
+typedef struct rtm3d_conv_mx8_desc {
+    int in_tensor;                     /* MX8 tensor id */
+    int out_tensor;                    /* MX8 tensor id, or (out_fp16 = 1) fp16 tensor id */
+    int out_fp16;
+    int cin, cout, groups, ntaps;      /* per group; groups <= RTM3D_MAX_GROUPS, ntaps <= RTM3D_MAX_TAPS */
+    int in_coff[RTM3D_MAX_GROUPS], out_coff[RTM3D_MAX_GROUPS];
+    int tap_dy[RTM3D_MAX_TAPS], tap_dx[RTM3D_MAX_TAPS];   /* shared by all groups */
+    int relu;
+    int w_blob, wscale_blob, bias_blob;
+} rtm3d_conv_mx8_desc;
+int rtm3d_op_conv_mx8(rtm3d_ctx* ctx, const rtm3d_conv_mx8_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,18 @@ class VConvDesc(ctypes.Structure):
     ]
 
 
+class ConvMx8Desc(ctypes.Structure):
+    """Mirror of struct rtm3d_conv_mx8_desc."""
+    _fields_ = [
+        ('in_tensor', c_int), ('out_tensor', c_int), ('out_fp16', c_int),
+        ('cin', c_int), ('cout', c_int), ('groups', c_int), ('ntaps', c_int),
+        ('in_coff', c_int * MAX_GROUPS), ('out_coff', c_int * MAX_GROUPS),
+        ('tap_dy', c_int * MAX_TAPS), ('tap_dx', c_int * MAX_TAPS),
+        ('relu', c_int),
+        ('w_blob', c_int), ('wscale_blob', c_int), ('bias_blob', c_int),
+    ]
+
+
 # name -> (restype, argtypes); also the list of symbols include/rtm3d_hip.h declares
 SIGNATURES = {
     'rtm3d_last_error': (ctypes.c_char_p, []),
@@ -116,6 +128,12 @@ SIGNATURES = {
                                               c_int, c_int, c_int, c_int, c_void_p]),
     'rtm3d_decode3d_slots': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    'rtm3d_tensor_create_mx8': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    'rtm3d_tensor_download_mx8': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    'rtm3d_tensor_download_mx8_raw': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    'rtm3d_tensor_upload_mx8_raw': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    'rtm3d_op_quant_mx8': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    'rtm3d_op_conv_mx8': (c_int, [c_void_p, ctypes.POINTER(ConvMx8Desc)]),
 }
 
 _lib = None

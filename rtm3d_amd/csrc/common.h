@@ -200,6 +200,31 @@ struct PatchMaskArgs {
     int n_slots, S, C, img_H, img_W, origin;
 };
 
+// MXFP8 head convolution (conv_mx8.hip): operands are MX8 tensors (padded NHWC e4m3 bytes + one E8M0 scale per 32 channels)
+struct ConvMx8Args {
+    const uint8_t* in; const uint8_t* in_s;     // input data / scale plane, padded element [0][0][0][0]
+    const uint8_t* wgt;                         // e4m3 [group][cout tile][k-step][256 rows][64]
+    const uint8_t* wsc;                         // E8M0 [group][cout tile][k-step][256 rows][2]
+    const float* bias;                          // [group][cout]
+    void* out; uint8_t* out_s;                  // MX8 output (data, scales) or fp16 NHWC (out_s unused)
+    int M, HmWm, Wm;
+    int in_Hp, in_Wp, in_C, in_P;
+    int out_Hp, out_Wp, out_C, out_P;
+    int cin, cout, ntaps, cpt, ksteps;          // cpt = 64-channel chunks per tap
+    int relu, out_fp16, MT, NT;
+    int in_coff[RT_MAX_GROUPS], out_coff[RT_MAX_GROUPS];
+    int tap_pix[RT_MAX_TAPS];                   // dy * in_Wp + dx
+};
+struct QuantMx8Args {
+    const f16* in;          // padded NHWC fp16, element [0][0][0][0]
+    uint8_t* out;           // padded NHWC e4m3
+    uint8_t* out_s;         // scale plane
+    int B, H, W;
+    int in_Hp, in_Wp, in_C, in_P, in_coff;
+    int out_Hp, out_Wp, out_C, out_P, out_coff;
+    int nblk;               // channels / 32
+};
+
 // kernel launchers (each returns hipGetLastError())
 hipError_t launch_patch_mask(const PatchMaskArgs& a, hipStream_t s);
 hipError_t launch_conv32s2_fused(const Conv32S2Args& a, int cu_count, unsigned int* ticket_ctr, hipStream_t s);
@@ -222,3 +247,5 @@ bool conv_smallc_supported(int cin, int cout, int ntaps);
 hipError_t launch_nchw_to_nhwc4(const float* in, f16* out, int B, int H, int W, int Hp, int Wp, int P, hipStream_t s);
 hipError_t launch_maxpool(const PoolKArgs& a, hipStream_t s);
 hipError_t launch_softmax_fuse(const SoftmaxKArgs& a, hipStream_t s);
+hipError_t launch_quant_mx8(const QuantMx8Args& a, hipStream_t s);
+hipError_t launch_conv_mx8(const ConvMx8Args& a, int groups, hipStream_t s);

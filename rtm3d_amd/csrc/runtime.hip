@@ -1,6 +1,7 @@
 // Runtime of librtm3d_hip.so: context (activation workspace + packed weights + launch plan) and
 // the C ABI declared in include/rtm3d_hip.h.  The plan is recorded once by the host
 // (rtm3d_amd/plan.py) and replayed by rtm3d_forward on the caller's HIP stream.
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -27,7 +28,17 @@ struct Tensor {
     size_t elems;   // padded elements (without guards)
 };
 
-enum OpKind { OP_CONV_MFMA, OP_CONV_MFMA256, OP_CONV64_HALO, OP_CONV64_ROOT, OP_CONV64S2_HALO, OP_CONV128_HALO, OP_STEM_FUSED, OP_CONV32S2_FUSED, OP_CONV_SMALLC, OP_INPUT4, OP_HEADOUT, OP_MAXPOOL, OP_SOFTMAX, OP_PATCH_MASK };
+// MX8 tensor (conv_mx8.hip): padded NHWC e4m3 bytes + E8M0 scale plane [B][Hp][Wp][C/32]
+struct MxTensor {
+    int B, H, W, C, P, Hp, Wp;
+    uint8_t* alloc;     // data allocation (guard band in front)
+    uint8_t* base;      // padded byte [0][0][0][0]
+    uint8_t* s_alloc;
+    uint8_t* s_base;    // padded scale [0][0][0][0]
+    size_t elems;       // padded data bytes (without guards)
+};
+
+enum OpKind { OP_CONV_MFMA, OP_CONV_MFMA256, OP_CONV64_HALO, OP_CONV64_ROOT, OP_CONV64S2_HALO, OP_CONV128_HALO, OP_STEM_FUSED, OP_CONV32S2_FUSED, OP_CONV_SMALLC, OP_INPUT4, OP_HEADOUT, OP_MAXPOOL, OP_SOFTMAX, OP_PATCH_MASK, OP_QUANT_MX8, OP_CONV_MX8 };
 
 struct Op {
     OpKind kind;
@@ -44,12 +55,15 @@ struct Op {
     Conv32S2Args c32;
     PatchMaskArgs pm;
     RootKArgs root;
+    QuantMx8Args qm;
+    ConvMx8Args cm;
 };
 
 struct rtm3d_ctx {
     int device;
     int n_cus = 256;
     std::vector<Tensor> tensors;
+    std::vector<struct MxTensor> mx8;   // MX8 tensors (rtm3d_tensor_create_mx8): ids of their own
     std::vector<void*> blobs;
     std::vector<size_t> blob_bytes;
     std::vector<Op> ops;
@@ -125,6 +139,7 @@ extern "C" int rtm3d_ctx_create(int device, rtm3d_ctx** out) {
 extern "C" void rtm3d_ctx_destroy(rtm3d_ctx* ctx) {
     if (!ctx) return;
     for (auto& t : ctx->tensors) (void)hipFree(t.alloc);
+    for (auto& t : ctx->mx8) { (void)hipFree(t.alloc); (void)hipFree(t.s_alloc); }
     for (auto p : ctx->blobs) (void)hipFree(p);
     for (auto p : ctx->extra) (void)hipFree(p);
     for (auto e : ctx->probe_ev) (void)hipEventDestroy(e);
@@ -441,6 +456,159 @@ extern "C" int rtm3d_op_conv(rtm3d_ctx* ctx, const rtm3d_conv_desc* d) {
         ctx->stat_tensor[stat_slot] = d->out_tensor;
         op.stat_out = ctx->stat_buf + (size_t)stat_slot * in->B * chunks * 256 * 2;
     }
+    ctx->ops.push_back(op);
+    return 0;
+}
+
+// ------------------------------------------------------------------ MX8 tensors and the MXFP8 head ops (conv_mx8.hip)
+static MxTensor* get_mx8(rtm3d_ctx* ctx, int id) {
+    if (id < 0 || id >= (int)ctx->mx8.size()) return nullptr;
+    return &ctx->mx8[id];
+}
+
+extern "C" int rtm3d_tensor_create_mx8(rtm3d_ctx* ctx, int B, int H, int W, int C, int pad, int* id) {
+    if (!ctx || !id) RT_FAIL("tensor_create_mx8: null argument");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || pad < 0 || (C % 32) != 0)
+        RT_FAIL("tensor_create_mx8: bad shape B=%d H=%d W=%d C=%d pad=%d (C must be a multiple of 32)", B, H, W, C, pad);
+    MxTensor t;
+    t.B = B; t.H = H; t.W = W; t.C = C; t.P = pad; t.Hp = H + 2 * pad; t.Wp = W + 2 * pad;
+    t.elems = (size_t)B * t.Hp * t.Wp * C;
+    if (t.elems >= ((size_t)1 << 32) - 2 * GUARD) RT_FAIL("tensor_create_mx8: %zu bytes exceed the 32-bit offset range of the kernels", t.elems);
+    const size_t sbytes = t.elems / 32;
+    RT_HIP(hipMalloc((void**)&t.alloc, t.elems + 2 * GUARD));
+    RT_HIP(hipMemset(t.alloc, 0, t.elems + 2 * GUARD));
+    if (hipMalloc((void**)&t.s_alloc, sbytes + 2 * GUARD) != hipSuccess) { (void)hipFree(t.alloc); RT_FAIL("tensor_create_mx8: out of device memory"); }
+    RT_HIP(hipMemset(t.s_alloc, 127, sbytes + 2 * GUARD));      // E8M0 127 = 2^0: the border's zeros dequantise to zero at any scale
+    t.base = t.alloc + GUARD; t.s_base = t.s_alloc + GUARD;
+    ctx->mx8.push_back(t);
+    *id = (int)ctx->mx8.size() - 1;
+    return 0;
+}
+
+// OCP e4m3fn -> float (0x7f / 0xff are NaN; the kernels never write them)
+static float e4m3_to_float(uint8_t b) {
+    const int s = b >> 7, e = (b >> 3) & 15, m = b & 7;
+    if (e == 15 && m == 7) return NAN;
+    const float v = e == 0 ? ldexpf((float)m, -9) : ldexpf((float)(8 + m), e - 10);
+    return s ? -v : v;
+}
+
+extern "C" int rtm3d_tensor_download_mx8(rtm3d_ctx* ctx, int id, int c0, int C, float* h_nchw) {
+    MxTensor* t = ctx ? get_mx8(ctx, id) : nullptr;
+    if (!t || !h_nchw || c0 < 0 || C <= 0 || c0 + C > t->C) RT_FAIL("tensor_download_mx8: bad arguments");
+    std::vector<uint8_t> d(t->elems), sc(t->elems / 32);
+    RT_HIP(hipDeviceSynchronize());
+    RT_HIP(hipMemcpy(d.data(), t->base, d.size(), hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(sc.data(), t->s_base, sc.size(), hipMemcpyDeviceToHost));
+    for (int n = 0; n < t->B; ++n)
+        for (int c = 0; c < C; ++c)
+            for (int y = 0; y < t->H; ++y)
+                for (int x = 0; x < t->W; ++x) {
+                    const size_t px = ((size_t)n * t->Hp + y + t->P) * t->Wp + x + t->P;
+                    const int cc = c0 + c;
+                    h_nchw[(((size_t)n * C + c) * t->H + y) * t->W + x] = ldexpf(e4m3_to_float(d[px * t->C + cc]), (int)sc[px * (t->C / 32) + cc / 32] - 127);
+                }
+    return 0;
+}
+
+static int mx8_raw_copy(rtm3d_ctx* ctx, int id, void* h_data, void* h_scale, bool up) {
+    MxTensor* t = ctx ? get_mx8(ctx, id) : nullptr;
+    if (!t || !h_data || !h_scale) RT_FAIL("tensor_%sload_mx8_raw: bad arguments", up ? "up" : "down");
+    RT_HIP(hipDeviceSynchronize());
+    if (up) {
+        RT_HIP(hipMemcpy(t->base, h_data, t->elems, hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpy(t->s_base, h_scale, t->elems / 32, hipMemcpyHostToDevice));
+    } else {
+        RT_HIP(hipMemcpy(h_data, t->base, t->elems, hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(h_scale, t->s_base, t->elems / 32, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+extern "C" int rtm3d_tensor_download_mx8_raw(rtm3d_ctx* ctx, int id, void* h_data, void* h_scale) { return mx8_raw_copy(ctx, id, h_data, h_scale, false); }
+extern "C" int rtm3d_tensor_upload_mx8_raw(rtm3d_ctx* ctx, int id, const void* h_data, const void* h_scale) {
+    return mx8_raw_copy(ctx, id, const_cast<void*>(h_data), const_cast<void*>(h_scale), true);
+}
+
+extern "C" int rtm3d_op_quant_mx8(rtm3d_ctx* ctx, int in_tensor, int in_coff, int out_tensor, int out_coff, int channels) {
+    Tensor* in = ctx ? get_tensor(ctx, in_tensor) : nullptr;
+    MxTensor* o = ctx ? get_mx8(ctx, out_tensor) : nullptr;
+    if (!in || !o) RT_FAIL("op_quant_mx8: bad tensors (fp16 input %d, MX8 output %d)", in_tensor, out_tensor);
+    if (in->B != o->B || in->H != o->H || in->W != o->W) RT_FAIL("op_quant_mx8: input and output maps differ in shape");
+    if (channels <= 0 || channels % 32 || in_coff < 0 || in_coff % 8 || in->C % 8 || in_coff + channels > in->C)
+        RT_FAIL("op_quant_mx8: input slice [%d, %d) of a %d-channel tensor (multiples of 32 channels from a multiple of 8)", in_coff, in_coff + channels, in->C);
+    if (out_coff < 0 || out_coff % 32 || out_coff + channels > o->C) RT_FAIL("op_quant_mx8: output slice [%d, %d) (32-channel blocks)", out_coff, out_coff + channels);
+    Op op;
+    op.kind = OP_QUANT_MX8; op.name = "quant_mx8";
+    QuantMx8Args& a = op.qm;
+    memset(&a, 0, sizeof(a));
+    a.in = in->base; a.out = o->base; a.out_s = o->s_base;
+    a.B = in->B; a.H = in->H; a.W = in->W;
+    a.in_Hp = in->Hp; a.in_Wp = in->Wp; a.in_C = in->C; a.in_P = in->P; a.in_coff = in_coff;
+    a.out_Hp = o->Hp; a.out_Wp = o->Wp; a.out_C = o->C; a.out_P = o->P; a.out_coff = out_coff;
+    a.nblk = channels / 32;
+    op.flops = 0;
+    op.bytes = (double)in->B * in->H * in->W * channels * (2.0 + 1.0 + 1.0 / 32);
+    ctx->ops.push_back(op);
+    return 0;
+}
+
+extern "C" int rtm3d_op_conv_mx8(rtm3d_ctx* ctx, const rtm3d_conv_mx8_desc* d) {
+    if (!ctx || !d) RT_FAIL("op_conv_mx8: null argument");
+    MxTensor* in = get_mx8(ctx, d->in_tensor);
+    if (!in) RT_FAIL("op_conv_mx8: bad MX8 input tensor %d", d->in_tensor);
+    if (d->out_fp16 != 0 && d->out_fp16 != 1) RT_FAIL("op_conv_mx8: out_fp16 must be 0 or 1");
+    Tensor* of = d->out_fp16 ? get_tensor(ctx, d->out_tensor) : nullptr;
+    MxTensor* om = d->out_fp16 ? nullptr : get_mx8(ctx, d->out_tensor);
+    if (!of && !om) RT_FAIL("op_conv_mx8: bad %s output tensor %d", d->out_fp16 ? "fp16" : "MX8", d->out_tensor);
+    if (om == in) RT_FAIL("op_conv_mx8: the output tensor is the input tensor");
+    const int oB = of ? of->B : om->B, oH = of ? of->H : om->H, oW = of ? of->W : om->W, oC = of ? of->C : om->C;
+    if (oB != in->B || oH != in->H || oW != in->W) RT_FAIL("op_conv_mx8: input and output maps differ in shape (stride 1, same size)");
+    if (d->groups < 1 || d->groups > RT_MAX_GROUPS || d->ntaps < 1 || d->ntaps > RT_MAX_TAPS) RT_FAIL("op_conv_mx8: groups/ntaps out of range");
+    if (d->cin <= 0 || d->cin % 64 || d->cout <= 0 || d->cout % 256) RT_FAIL("op_conv_mx8: needs cin %% 64 == 0 and cout %% 256 == 0 (cin=%d cout=%d)", d->cin, d->cout);
+    if (in->C % 64) RT_FAIL("op_conv_mx8: the input tensor's channel count %d is not a multiple of 64", in->C);
+    for (int t = 0; t < d->ntaps; ++t) {
+        const int dy = d->tap_dy[t], dx = d->tap_dx[t];
+        if (dy < -in->P || dx < -in->P || in->H - 1 + dy >= in->H + in->P || in->W - 1 + dx >= in->W + in->P)
+            RT_FAIL("op_conv_mx8: tap (%d,%d) leaves the padded input (H=%d W=%d pad=%d)", dy, dx, in->H, in->W, in->P);
+    }
+    for (int g = 0; g < d->groups; ++g) {
+        if (d->in_coff[g] < 0 || d->in_coff[g] % 64 || d->in_coff[g] + d->cin > in->C)
+            RT_FAIL("op_conv_mx8: input slice [%d, %d) of a %d-channel tensor (offsets multiples of 64)", d->in_coff[g], d->in_coff[g] + d->cin, in->C);
+        const int align = of ? 8 : 32;
+        if (d->out_coff[g] < 0 || d->out_coff[g] % align || d->out_coff[g] + d->cout > oC)
+            RT_FAIL("op_conv_mx8: output slice [%d, %d) of a %d-channel tensor (offsets multiples of %d)", d->out_coff[g], d->out_coff[g] + d->cout, oC, align);
+        for (int h = 0; h < g; ++h)
+            if (d->out_coff[h] < d->out_coff[g] + d->cout && d->out_coff[g] < d->out_coff[h] + d->cout) RT_FAIL("op_conv_mx8: the output slices of groups %d and %d overlap", h, g);
+    }
+    const int cpt = d->cin / 64, ksteps = d->ntaps * cpt, NT = d->cout / 256;
+    const size_t tiles = (size_t)d->groups * NT * ksteps;
+    size_t wb = 0, sb = 0, bb = 0;
+    const uint8_t* w = (const uint8_t*)get_blob(ctx, d->w_blob, &wb);
+    const uint8_t* ws = (const uint8_t*)get_blob(ctx, d->wscale_blob, &sb);
+    const float* bias = (const float*)get_blob(ctx, d->bias_blob, &bb);
+    if (!w || !ws || !bias) RT_FAIL("op_conv_mx8: bad weight / scale / bias blob");
+    if (wb != tiles * 256 * 64 || sb != tiles * 256 * 2 || bb != (size_t)d->groups * d->cout * sizeof(float))
+        RT_FAIL("op_conv_mx8: blob sizes %zu / %zu / %zu, expected %zu / %zu / %zu", wb, sb, bb, tiles * 256 * 64, tiles * 256 * 2, (size_t)d->groups * d->cout * sizeof(float));
+    const long long M = (long long)in->B * in->H * in->W;
+    if (M >= (1LL << 31)) RT_FAIL("op_conv_mx8: %lld pixels exceed the kernel's 32-bit index", M);
+    Op op;
+    op.kind = OP_CONV_MX8;
+    op.name = d->out_fp16 ? "conv_mx8_to_f16" : "conv_mx8";
+    op.groups = d->groups;
+    ConvMx8Args& a = op.cm;
+    memset(&a, 0, sizeof(a));
+    a.in = in->base; a.in_s = in->s_base; a.wgt = w; a.wsc = ws; a.bias = bias;
+    a.out = of ? (void*)of->base : (void*)om->base; a.out_s = om ? om->s_base : nullptr;
+    a.M = (int)M; a.HmWm = in->H * in->W; a.Wm = in->W;
+    a.in_Hp = in->Hp; a.in_Wp = in->Wp; a.in_C = in->C; a.in_P = in->P;
+    a.out_Hp = of ? of->Hp : om->Hp; a.out_Wp = of ? of->Wp : om->Wp; a.out_C = oC; a.out_P = of ? of->P : om->P;
+    a.cin = d->cin; a.cout = d->cout; a.ntaps = d->ntaps; a.cpt = cpt; a.ksteps = ksteps;
+    a.relu = d->relu ? 1 : 0; a.out_fp16 = d->out_fp16;
+    a.MT = (int)((M + 255) / 256); a.NT = NT;
+    for (int g = 0; g < d->groups; ++g) { a.in_coff[g] = d->in_coff[g]; a.out_coff[g] = d->out_coff[g]; }
+    for (int t = 0; t < d->ntaps; ++t) a.tap_pix[t] = d->tap_dy[t] * in->Wp + d->tap_dx[t];
+    op.flops = 2.0 * (double)M * d->groups * d->cin * d->ntaps * d->cout;
+    op.bytes = (double)M * d->groups * (d->cin * (1.0 + 1.0 / 32) + d->cout * (of ? 2.0 : 1.0 + 1.0 / 32)) + (double)(wb + sb);
     ctx->ops.push_back(op);
     return 0;
 }
@@ -784,6 +952,8 @@ static int launch_op(rtm3d_ctx* ctx, Op& op, hipStream_t s, const float* d_in, f
         case OP_MAXPOOL: e = launch_maxpool(op.pool, s); break;
         case OP_SOFTMAX: e = launch_softmax_fuse(op.sm, s); break;
         case OP_PATCH_MASK: e = launch_patch_mask(op.pm, s); break;
+        case OP_QUANT_MX8: e = launch_quant_mx8(op.qm, s); break;
+        case OP_CONV_MX8: e = launch_conv_mx8(op.cm, op.groups, s); break;
     }
     if (e != hipSuccess) { rt_set_error("launch of op '%s' failed: %s", op.name.c_str(), hipGetErrorString(e)); return 1; }
     return 0;

@@ -50,8 +50,21 @@ class Detections(object):
         self.bbox = torch.zeros(B * topk, 4, dtype=torch.float32, device=device)
 
 
+HEAD_PRECISIONS = plan_mod.HEAD_PRECISIONS
+
+
+def _check_precision(p):
+    if p not in HEAD_PRECISIONS:
+        raise ValueError('head_precision must be one of %s, got %r' % (HEAD_PRECISIONS, p))
+    return p
+
+
 class Model(object):
-    def __init__(self, config, backbone=None):
+    def __init__(self, config, backbone=None, head_precision='fp16'):
+        """head_precision: 'fp16' (default) | 'mxfp8' - the opt-in approximate mode in which the dilation-6 / dilation-1 head convs
+        run on MXFP8 operands (plan.build_plan).  Calls that take a head_precision argument override it per call; a model holds
+        the plans of both precisions side by side."""
+        self.head_precision = _check_precision(head_precision)
         self.config = config
         self._backbone_name = backbone if isinstance(backbone, str) else config.MODEL.BACKBONE
         parse_backbone(self._backbone_name)
@@ -151,14 +164,23 @@ class Model(object):
         return self.forward(x)
 
     # ------------------------------------------------------------------ hot path
-    def _plan_for(self, B, H, W, device, heads='dense'):
+    def _precision(self, head_precision):
+        return self.head_precision if head_precision is None else _check_precision(head_precision)
+
+    def _plan_for(self, B, H, W, device, heads='dense', head_precision=None):
         """heads = 'dense': all branches on the whole map (Model.forward); 'peaks': the heat map alone plus the patch plan that
-        evaluates the regression branches at the detected peaks (detect3d(sparse_heads=True), csrc/sparse_heads.hip)."""
+        evaluates the regression branches at the detected peaks (detect3d(sparse_heads=True), csrc/sparse_heads.hip).
+        head_precision: None = the model's; 'mxfp8' plans are kept under keys of their own."""
         if heads not in ('dense', 'peaks'):
             raise ValueError("heads must be 'dense' or 'peaks'")
+        prec = self._precision(head_precision)
+        if heads == 'peaks' and prec != 'fp16':
+            raise NotImplementedError("peaks-only regression heads (sparse_heads) exist in fp16 only, not with head_precision=%r" % prec)
         if heads == 'peaks' and self._head_variant not in (None, 'rtm3d'):
             raise NotImplementedError('peaks-only regression heads exist for the rtm3d head table')
         key = (B, H, W, device.index) if heads == 'dense' else (B, H, W, device.index, heads)
+        if prec != 'fp16':
+            key = key + (prec,)
         p = self._plans.get(key)
         if p is not None:
             self._plans[key] = self._plans.pop(key)          # most recently used last
@@ -173,7 +195,7 @@ class Model(object):
                 self._wcache = WeightCache(self._sd)
             ir = plan_mod.build_plan(self._sd, self._backbone_name, B, H, W, self._head_variant, cache=self._wcache,
                                      num_classes=self._num_classes, dense_heads=1 if heads == 'peaks' else None,
-                                     header_num_conv=self._num_conv)
+                                     header_num_conv=self._num_conv, head_precision=prec)
             with torch.cuda.device(device):
                 p = plan_mod.RealizedPlan(ir, device.index)
                 # small batches are bound by launch gaps, not by the kernels: replay those plans as one hipGraph
@@ -200,7 +222,7 @@ class Model(object):
             x = x.float()
         return x.contiguous()
 
-    def input_tensor(self, B, H, W, device=None, heads='dense'):
+    def input_tensor(self, B, H, W, device=None, heads='dense', head_precision=None):
         """(device address, border) of the fp16 NHWC4 input tensor of the plan for (B, H, W): the target of
         ``rtm3d_amd.preprocess.preprocess_batch(..., model=self)``.  heads: which plan ('dense' / 'peaks': they own separate
         workspaces) the following ``forward_logits(None, preloaded=..., heads=...)`` will replay."""
@@ -208,9 +230,9 @@ class Model(object):
         if dev is None or dev.type != 'cuda':
             raise RuntimeError('rtm3d_amd.Model.input_tensor needs a CUDA (ROCm) device; call model.to("cuda") first')
         dev = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
-        return self._plan_for(B, H, W, dev, heads).input_tensor()
+        return self._plan_for(B, H, W, dev, heads, head_precision).input_tensor()
 
-    def forward_logits(self, x, preloaded=None, out=None, heads='dense'):
+    def forward_logits(self, x, preloaded=None, out=None, heads='dense', head_precision=None):
         """backbone -> neck -> heads: the four fp32 NCHW logit maps (models/model.py:21-23).
         preloaded=(B, H, W): ``x`` is None and the plan's input tensor was filled by preprocess_batch(model=self).
         out: where the logits go instead of four fresh tensors - a tuple of contiguous fp32 CUDA tensors of the logit
@@ -218,7 +240,8 @@ class Model(object):
         tensors: consume them, in stream order, before the next call).  A hipGraph replay is keyed by these addresses
         (rtm3d_forward), so a loop that holds on to its fresh outputs would pay a capture per call; with out= it replays one
         graph (the bs=1 detect.py loop).
-        heads='peaks': only the heat-map branch is evaluated (a 1-tuple comes back); feed it to ``decode2d_sparse``."""
+        heads='peaks': only the heat-map branch is evaluated (a 1-tuple comes back); feed it to ``decode2d_sparse``.
+        head_precision: 'fp16' | 'mxfp8' for this call (None: the model's, Model(head_precision=...))."""
         if preloaded is not None:
             if x is not None:
                 raise ValueError('forward_logits: pass x=None with preloaded=(B, H, W)')
@@ -232,7 +255,7 @@ class Model(object):
             B, _, H, W = x.shape
             dev = x.device
             xptr = x.data_ptr()
-        plan = self._plan_for(B, H, W, dev, heads)
+        plan = self._plan_for(B, H, W, dev, heads, head_precision)
         with torch.cuda.device(dev):
             shapes = [(B, c, H // 4, W // 4) for c in (self._head_channels if heads == 'dense' else self._head_channels[:1])]
             if out is None:
@@ -297,8 +320,8 @@ class Model(object):
         """Free the fp32 verification executor's device buffers."""
         self._verify = None
 
-    def forward(self, x):
-        pred_logits = self.forward_logits(x)
+    def forward(self, x, head_precision=None):
+        pred_logits = self.forward_logits(x, head_precision=head_precision)
         if self.training:
             # the reference returns the raw logits for its loss (models/model.py:24-25)
             return pred_logits
@@ -387,7 +410,7 @@ class Model(object):
         main key points, 8 vertices, 2D boxes; ``None`` where nothing was kept) - without the dense regression maps that call
         never looks at: the heat map is computed on the whole image, the regression branches at the detected peaks
         (decode2d_sparse).  Same lists as ``model(x)[0]`` up to fp16 round-off of the vertices (<= 1.4e-3 px measured)."""
-        if self._head_variant not in (None, 'rtm3d'):
+        if self._head_variant not in (None, 'rtm3d') or self.head_precision != 'fp16':
             return self.forward(x)[0]
         return self._lists(self.decode2d_sparse(self.forward_logits(x, heads='peaks')))
 
@@ -438,21 +461,28 @@ class Model(object):
                 'vertex_offset_logits': logits[3]}
 
     # ------------------------------------------------------------------ fused device pipeline
-    def detect3d(self, x, K_per_image, dim_ref=None, ref_loc=(0.0, -0.5, 20.0), fp32_verify=False, sparse_heads=False, solver_form=None):
+    def detect3d(self, x, K_per_image, dim_ref=None, ref_loc=(0.0, -0.5, 20.0), fp32_verify=False, sparse_heads=False, solver_form=None,
+                 head_precision=None):
         """forward + 2D decode + 3D decode, all stream-ordered on the device (no host sync).
         K_per_image: (B, 9) float64 CUDA tensor.  Returns (Detections, Boxes3D, logits).
         fp32_verify=True: the network runs in the fp32 verification mode (forward_logits_fp32), the decode kernels are the
         product's own.  sparse_heads=True: the detect.py call surface never reads the dense regression maps, so only the heat
         map is computed densely and the regression branches at the detected peaks (decode2d_sparse); `logits` is then the
-        heat map alone.  solver_form: 'direct' | 'published' (model_utils.solver_form_id), None = the default."""
+        heat map alone.  solver_form: 'direct' | 'published' (model_utils.solver_form_id), None = the default.
+        head_precision: 'fp16' | 'mxfp8' (None: the model's); 'mxfp8' runs neither with sparse_heads nor with fp32_verify."""
         from .model_utils import decode3d_slots, decode_smoke_slots
+        prec = self._precision(head_precision)
+        if prec != 'fp16' and sparse_heads:
+            raise NotImplementedError("detect3d: head_precision=%r has no peaks-only (sparse_heads) form" % prec)
+        if prec != 'fp16' and fp32_verify:
+            raise ValueError("detect3d: fp32_verify runs the fp32 network; it does not combine with head_precision=%r" % prec)
         if sparse_heads:
             if fp32_verify:
                 raise ValueError('detect3d: sparse_heads and fp32_verify are separate modes')
             logits = self.forward_logits(x, heads='peaks')
             det = self.decode2d_sparse(logits)
         else:
-            logits = self.forward_logits_fp32(x) if fp32_verify else self.forward_logits(x)
+            logits = self.forward_logits_fp32(x) if fp32_verify else self.forward_logits(x, head_precision=prec)
             det = self.decode2d(logits)
         dim_ref = dim_ref if dim_ref is not None else self.config.DETECTOR.dim_ref
         if len(dim_ref) < self._num_classes:

@@ -32,7 +32,7 @@ SMALL_BATCH = 2      # batches whose 3D decode (a serial fp64 iteration per obje
 
 class Detect3DPipeline(object):
     def __init__(self, model, batch, device, dim_ref=None, ref_loc=(0.0, -0.5, 20.0), gather=True, depth=None, decode3d=True,
-                 side_cus=0, side_streams=None, sparse_heads=False, solver_form=None):
+                 side_cus=0, side_streams=None, sparse_heads=False, solver_form=None, head_precision=None):
         self.model, self.B, self.dev = model, batch, torch.device(device)
         # sparse_heads: this call surface hands out detection records, never the dense logits, so the regression branches are
         # evaluated at the detected peaks only (Model.decode2d_sparse); the records agree with the dense path's to fp16 round-off
@@ -41,7 +41,11 @@ class Detect3DPipeline(object):
         from .model_utils import solver_form_id, DEFAULT_SOLVER_FORM
         solver_form_id(solver_form)
         self.solver_form = DEFAULT_SOLVER_FORM if solver_form is None else solver_form
-        self.heads = 'peaks' if self.sparse_heads else 'dense' 
+        self.heads = 'peaks' if self.sparse_heads else 'dense'
+        # head_precision: 'fp16' | 'mxfp8' (None: the model's, Model(head_precision=...)); mxfp8 has no peaks-only form
+        self.head_precision = model._precision(head_precision)
+        if self.sparse_heads and self.head_precision != 'fp16':
+            raise NotImplementedError("Detect3DPipeline: sparse_heads has no head_precision=%r form" % self.head_precision)
         self.topk = int(model.config.DETECTOR.TOPK_CANDIDATES)
         dim_ref = dim_ref if dim_ref is not None else model.config.DETECTOR.dim_ref
         if len(dim_ref) < getattr(model, '_num_classes', 0):
@@ -108,8 +112,10 @@ class Detect3DPipeline(object):
         H, W = int(size[0]), int(size[1])
 
         def feed():
-            preprocess.preprocess_batch(images, (H, W), cfg.DATASET.MEAN, cfg.DATASET.STD, resize_to=resize_to, model=self.model, heads=self.heads)
-            return self.model.forward_logits(None, preloaded=(self.B, H, W), out='reuse', heads=self.heads)
+            preprocess.preprocess_batch(images, (H, W), cfg.DATASET.MEAN, cfg.DATASET.STD, resize_to=resize_to, model=self.model, heads=self.heads,
+                                        head_precision=self.head_precision)
+            return self.model.forward_logits(None, preloaded=(self.B, H, W), out='reuse', heads=self.heads,
+                                            head_precision=self.head_precision)
         return self._submit(feed, K_per_image)
 
     def submit(self, x, K_per_image):
@@ -120,7 +126,7 @@ class Detect3DPipeline(object):
             # rtm3d_amd.distributed.padded_shard)
             raise ValueError('Detect3DPipeline was built for batches of %d images, got input of shape %s'
                              % (self.B, tuple(x.shape)))
-        return self._submit(lambda: self.model.forward_logits(x, out='reuse', heads=self.heads), K_per_image)
+        return self._submit(lambda: self.model.forward_logits(x, out='reuse', heads=self.heads, head_precision=self.head_precision), K_per_image)
 
     def _submit(self, run_network, K_per_image):
         if not isinstance(K_per_image, torch.Tensor) or K_per_image.numel() != self.B * 9 or not K_per_image.is_cuda:

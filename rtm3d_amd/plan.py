@@ -21,6 +21,7 @@ import os
 import numpy as np
 
 from . import _lib
+from . import mx8
 from .weights import parse_backbone, DLA34_CHANNELS, DLA34_LEVELS, RESNET_BLOCKS, head_table
 
 V2_MIN_TILES = 200
@@ -47,8 +48,13 @@ class Plan(object):
         self.named = {}      # debug names -> Slice (stage outputs, for parity tests)
 
     # ---- IR construction
-    def tensor(self, H, W, C, pad, name=None):
-        self.tensors.append({'H': H, 'W': W, 'C': C, 'pad': pad})
+    def tensor(self, H, W, C, pad, name=None, fmt=None):
+        """fmt=None: padded NHWC fp16; fmt='mx8': padded NHWC e4m3 + an E8M0 scale per 32 channels (rtm3d_tensor_create_mx8)."""
+        t = {'H': H, 'W': W, 'C': C, 'pad': pad}
+        if fmt is not None:
+            assert fmt == 'mx8' and C % 32 == 0, (fmt, C)
+            t['fmt'] = fmt
+        self.tensors.append(t)
         s = Slice(len(self.tensors) - 1, 0, C)
         if name:
             self.named[name] = s
@@ -165,6 +171,28 @@ class Plan(object):
         zero padding); position (i, j) of slot s is map pixel (y_s + i - origin, x_s + j - origin)."""
         self.ops.append({'op': 'patch_mask', 'name': name, 't': t, 'origin': origin})
 
+    def quant_mx8(self, inp, out, name=''):
+        """fp16 slice -> MX8 slice of the same map (rtm3d_op_quant_mx8)."""
+        assert inp.C == out.C and inp.C % 32 == 0 and out.coff % 32 == 0 and self.tensors[out.tid].get('fmt') == 'mx8'
+        assert self.dims(inp) == self.dims(out)
+        self.ops.append({'op': 'quant_mx8', 'name': name, 'inp': inp, 'out': out})
+
+    def conv_mx8(self, inps, outs, ws, biases, dil=1, relu=False, name=''):
+        """3x3 convs (one per group, same shape) on MX8 operands (rtm3d_op_conv_mx8): inputs are MX8 slices, outputs MX8
+        slices or - when the output tensor is an fp16 one - fp16.  ws[g]: (cout, cin, 3, 3) fp32 with BN folded."""
+        G = len(inps)
+        cout, cin, k, _ = ws[0].shape
+        pad = dil * (k - 1) // 2
+        taps = [(ky * dil - pad, kx * dil - pad) for ky in range(k) for kx in range(k)]
+        assert all(self.tensors[i.tid].get('fmt') == 'mx8' and i.C == cin for i in inps)
+        assert len({self.tensors[o.tid].get('fmt') for o in outs}) == 1 and all(o.C == cout for o in outs)
+        wt = np.stack([np.stack([w[:, :, ky, kx] for ky in range(k) for kx in range(k)], 0) for w in ws], 0)
+        Hm, Wm = self.dims(inps[0])
+        self.ops.append({'op': 'conv_mx8', 'name': name, 'inp': list(inps), 'out': list(outs), 'Hm': Hm, 'Wm': Wm,
+                         'cin': cin, 'cout': cout, 'groups': G, 'taps': taps, 'relu': relu, 'w': wt.astype(np.float32),
+                         'bias': np.stack([np.asarray(b, np.float32) for b in biases], 0),
+                         'out_fp16': self.tensors[outs[0].tid].get('fmt') != 'mx8'})
+
     def softmax_fuse(self, z_in, z_out, us, name=''):
         self.ops.append({'op': 'softmax', 'name': name, 'z_in': z_in, 'z_out': z_out, 'us': list(us)})
 
@@ -178,6 +206,8 @@ class Plan(object):
             elif op['op'] == 'conv':
                 cin = 3 if op['cin'] == 4 else op['cin']          # NHWC4 stem: the 4th channel is zero padding
                 f += 2.0 * self.B * op['Hm'] * op['Wm'] * op['groups'] * cin * len(op['taps'][0]) * op['cout']
+            elif op['op'] == 'conv_mx8':
+                f += 2.0 * self.B * op['Hm'] * op['Wm'] * op['groups'] * op['cin'] * len(op['taps']) * op['cout']
             elif op['op'] == 'headout':
                 H, W = self.dims(op['inp'])
                 f += 2.0 * self.B * H * W * 9 * 256 * sum(w.shape[0] for w in op['w'])
@@ -314,14 +344,25 @@ def _build_resnet(P, sd, H, W, depth, feat_out):
             inpl = pl
 
 
-def build_plan(state_dict, backbone, B, H, W, head_variant='rtm3d', cache=None, num_classes=3, dense_heads=None, header_num_conv=2):
+HEAD_PRECISIONS = ('fp16', 'mxfp8')
+
+
+def build_plan(state_dict, backbone, B, H, W, head_variant='rtm3d', cache=None, num_classes=3, dense_heads=None, header_num_conv=2,
+               head_precision='fp16'):
     """state_dict: reference key names -> torch tensors.  H, W multiples of 32.  cache: a WeightCache of this state dict.
     dense_heads = k: only the first k head branches are evaluated on the whole map (1 = the heat map alone: the other
-    branches then come from build_peak_plan at the detected peaks)."""
+    branches then come from build_peak_plan at the detected peaks).
+    head_precision = 'mxfp8' (opt-in, approximate): the dilation-6 and dilation-1 head convs run on MXFP8 operands
+    (csrc/conv_mx8.hip; z quantised once, the intermediate head maps stored as MX8, the last head conv writes fp16 for the
+    unchanged logit convs).  'fp16' (default) builds exactly the plan it always did."""
+    if head_precision not in HEAD_PRECISIONS:
+        raise ValueError('head_precision must be one of %s, got %r' % (HEAD_PRECISIONS, head_precision))
+    if head_precision == 'mxfp8' and dense_heads is not None:
+        raise NotImplementedError("head_precision='mxfp8' exists for the dense heads only (not for the peaks-only plan)")
     global _CACHE
     _CACHE = cache
     try:
-        P = _build_plan(state_dict, backbone, B, H, W, head_variant, num_classes, dense_heads, header_num_conv)
+        P = _build_plan(state_dict, backbone, B, H, W, head_variant, num_classes, dense_heads, header_num_conv, head_precision)
     finally:
         _CACHE = None
     P.cache = cache
@@ -373,7 +414,7 @@ def build_peak_plan(state_dict, slots, map_hw, head_variant='rtm3d', cache=None,
     return P
 
 
-def _build_plan(state_dict, backbone, B, H, W, head_variant, num_classes=3, dense_heads=None, header_num_conv=2):
+def _build_plan(state_dict, backbone, B, H, W, head_variant, num_classes=3, dense_heads=None, header_num_conv=2, head_precision='fp16'):
     kind, depth = parse_backbone(backbone)
     if H % 32 or W % 32:
         raise ValueError('input height/width must be multiples of 32, got %dx%d' % (H, W))
@@ -452,6 +493,9 @@ def _build_plan(state_dict, backbone, B, H, W, head_variant, num_classes=3, dens
     nconv = int(header_num_conv)
     if nconv < 1:
         raise ValueError('MODEL.HEADER_NUM_CONV must be >= 1, got %r' % (header_num_conv,))
+    if head_precision == 'mxfp8':
+        _build_heads_mx8(P, sd, z, heads, hn, nconv, fh[0])
+        return P
     h1 = P.tensor(fh[0][0], fh[0][1], G * oc, 1, name='h1')
     h2 = P.tensor(fh[0][0], fh[0][1], G * oc, 1, name='h2') if nconv > 1 else None
     ws, bs = zip(*[fold_bn(sd, 'detect_header.%s.0' % seq, 'detect_header.%s.1' % seq) for seq, _, _ in heads])
@@ -469,6 +513,29 @@ def _build_plan(state_dict, backbone, B, H, W, head_variant, num_classes=3, dens
 
 
 # ------------------------------------------------------------------------------------------ realize
+def _build_heads_mx8(P, sd, z, heads, hn, nconv, hw):
+    """The dense heads with head_precision='mxfp8': z -> MX8 (border 6), the d6 conv of all branches and the d1 convs on MX8
+    operands; every head conv but the last writes MX8 (border 1), the last one fp16 for the logit convs (P.headout)."""
+    G, oc = len(heads), 256
+    zq = P.tensor(hw[0], hw[1], oc, 6, name='zq', fmt='mx8')
+    P.quant_mx8(z, zq, name=hn + '.quant_z')
+    last = P.tensor(hw[0], hw[1], G * oc, 1, name='h_last')        # fp16 input of the logit convs
+    mx = [P.tensor(hw[0], hw[1], G * oc, 1, name='h%dq' % (i + 1), fmt='mx8') for i in range(min(nconv - 1, 2))]
+    ws, bs = zip(*[fold_bn(sd, 'detect_header.%s.0' % seq, 'detect_header.%s.1' % seq) for seq, _, _ in heads])
+    dst = last if nconv == 1 else mx[0]
+    P.conv_mx8([zq], [dst], [np.concatenate(ws, 0)], [np.concatenate(bs, 0)], dil=6, relu=True, name=hn + '.conv_d6')
+    src = dst
+    for k in range(1, nconv):
+        ws, bs = zip(*[fold_bn(sd, 'detect_header.%s.%d' % (seq, 3 * k), 'detect_header.%s.%d' % (seq, 3 * k + 1)) for seq, _, _ in heads])
+        dst = last if k == nconv - 1 else mx[k % 2] if len(mx) > 1 else None
+        P.conv_mx8([P.sub(src, g * oc, oc) for g in range(G)], [P.sub(dst, g * oc, oc) for g in range(G)], ws, bs,
+                   relu=True, name=hn + ('.conv_d1' if k == 1 else '.conv_d1_%d' % k))
+        src = dst
+    ws, bs = zip(*[fold_bn(sd, 'detect_header.%s.%s' % (seq, last_)) for seq, last_, _ in heads])
+    P.headout(last, ws, bs, name=hn + '.out_convs')
+    P.head_channels = [c for _, _, c in heads]
+
+
 def choose_bn_tile(cout, M):
     """Output-channel tile of the MFMA kernel (conv_mfma.hip).  128 channels go with the 256-pixel ring kernel (one
     8-wave workgroup per CU): taken when the layer still gives about a full round of 256 CUs; otherwise 64-channel tiles
@@ -663,7 +730,10 @@ class RealizedPlan(object):
         self._plan_s2d_only(nfold, tail)
         for i, t in enumerate(plan.tensors):
             tid = ctypes.c_int()
-            _lib.check(lib.rtm3d_tensor_create(ctx, plan.B, t['H'], t['W'], t['C'] + widen.get(i, 0), t['pad'], ctypes.byref(tid)), 'tensor_create')
+            if t.get('fmt') == 'mx8':             # (MX8 tensor ids are a namespace of their own)
+                _lib.check(lib.rtm3d_tensor_create_mx8(ctx, plan.B, t['H'], t['W'], t['C'], t['pad'], ctypes.byref(tid)), 'tensor_create_mx8')
+            else:
+                _lib.check(lib.rtm3d_tensor_create(ctx, plan.B, t['H'], t['W'], t['C'] + widen.get(i, 0), t['pad'], ctypes.byref(tid)), 'tensor_create')
             self.tids.append(tid.value)
         self.op_names = []                      # one entry per RECORDED runtime op (a fused pair records one)
         self.weight_ranges = []                 # per recorded conv: largest |weight| / |bias| as realized (after the level rewrites)
@@ -997,6 +1067,10 @@ class RealizedPlan(object):
             return hit(op['t'], op['t'].C)
         if op['op'] == 'softmax':
             return hit(op['z_in'], op['z_in'].C) or any(hit(u, u.C) for u in op['us'])
+        if op['op'] == 'quant_mx8':
+            return hit(op['inp'], op['inp'].C)
+        if op['op'] == 'conv_mx8':
+            return any(hit(i, op['cin']) for i in op['inp'])
         return False
 
     def _op_conv64_root(self, cv, rt, pool, s2d=None, skip_out=False):
@@ -1096,6 +1170,10 @@ class RealizedPlan(object):
             return op['t'].tid == tid
         if op['op'] == 'softmax':
             return op['z_in'].tid == tid or any(u.tid == tid for u in op['us'])
+        if op['op'] == 'quant_mx8':
+            return op['inp'].tid == tid
+        if op['op'] == 'conv_mx8':
+            return any(s.tid == tid for s in op['inp'])
         return False
 
     def _op_stem_fused(self, a, b, c=None):
@@ -1259,6 +1337,30 @@ class RealizedPlan(object):
         co = (ctypes.c_int * 4)(*([x.shape[0] for x in op['w']] + [0] * (4 - len(op['w']))))
         _lib.check(self.lib.rtm3d_op_headout(self.ctx, self.tids[op['inp'].tid], self._blob(w), self._blob(b), len(op['w']), co), 'op_headout')
 
+    def _op_quant_mx8(self, op):
+        _lib.check(self.lib.rtm3d_op_quant_mx8(self.ctx, self.tids[op['inp'].tid], op['inp'].coff, self.tids[op['out'].tid], op['out'].coff,
+                                               op['inp'].C), 'op_quant_mx8 ' + op['name'])
+
+    def _op_conv_mx8(self, op):
+        self.weight_ranges.append({'op': op['name'], 'max_abs_w': float(np.abs(op['w']).max()), 'max_abs_bias': float(np.abs(op['bias']).max())})
+        d = _lib.ConvMx8Desc()
+        G = op['groups']
+        d.in_tensor = self.tids[op['inp'][0].tid]
+        d.out_tensor = self.tids[op['out'][0].tid]
+        d.out_fp16 = 1 if op['out_fp16'] else 0
+        d.cin, d.cout, d.groups, d.ntaps = op['cin'], op['cout'], G, len(op['taps'])
+        for g in range(G):
+            assert op['inp'][g].tid == op['inp'][0].tid and op['out'][g].tid == op['out'][0].tid
+            d.in_coff[g], d.out_coff[g] = op['inp'][g].coff, op['out'][g].coff
+        for t, (dy, dx) in enumerate(op['taps']):
+            d.tap_dy[t], d.tap_dx[t] = dy, dx
+        d.relu = 1 if op['relu'] else 0
+        packed = [self._packed(op, g, 'mx8', 256, lambda g=g: mx8.pack_conv_weights(op['w'][g])) for g in range(G)]
+        d.w_blob = self._blob(np.concatenate([p[0] for p in packed]))
+        d.wscale_blob = self._blob(np.concatenate([p[1] for p in packed]))
+        d.bias_blob = self._blob(np.ascontiguousarray(op['bias'], np.float32).reshape(-1))
+        _lib.check(self.lib.rtm3d_op_conv_mx8(self.ctx, ctypes.byref(d)), 'op_conv_mx8 ' + op['name'])
+
     def _op_input4(self, op):
         _lib.check(self.lib.rtm3d_op_input_nhwc4(self.ctx, self.tids[op['out'].tid]), 'op_input_nhwc4')
 
@@ -1371,6 +1473,9 @@ class RealizedPlan(object):
                     out[:, :, py::2, px::2] = ph
             return out
         out = np.empty((self.plan.B, s.C, t['H'], t['W']), np.float32)
+        if t.get('fmt') == 'mx8':                 # dequantised
+            _lib.check(self.lib.rtm3d_tensor_download_mx8(self.ctx, self.tids[s.tid], s.coff, s.C, out.ctypes.data_as(ctypes.c_void_p)), 'tensor_download_mx8')
+            return out
         _lib.check(self.lib.rtm3d_tensor_download(self.ctx, self.tids[s.tid], s.coff, s.C, out.ctypes.data_as(ctypes.c_void_p)), 'tensor_download')
         return out
 

@@ -102,7 +102,7 @@ def resize_K(K, hw, new_hw):
     return K
 
 
-def preprocess_batch(images, size, mean, std, resize_to=None, out=None, model=None, heads='dense'):
+def preprocess_batch(images, size, mean, std, resize_to=None, out=None, model=None, heads='dense', head_precision=None):
     """images: list of uint8 CUDA tensors (h, w, 3), any sizes.  size = (H, W) network canvas.
     resize_to: None (images are already resized) or the reference's INPUT_SIZE (longest side after Resize).
     model given: write straight into that model's fp16 NHWC4 input tensor for batch (B, H, W) - call
@@ -132,7 +132,7 @@ def preprocess_batch(images, size, mean, std, resize_to=None, out=None, model=No
         sums = torch.zeros(B, 3, dtype=torch.int64, device=dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         if model is not None:
-            base, border = model.input_tensor(B, H, W, dev, heads)
+            base, border = model.input_tensor(B, H, W, dev, heads, head_precision)
             mode, dst, ret = 1, base, None
         else:
             if out is None:
