@@ -146,7 +146,7 @@ int rtm3d_op_conv32s2_fused(rtm3d_ctx* ctx, int in_tensor, int in_coff, int conv
  * fp32 biases [64] with BN folded.  Same result as the rtm3d_op_conv / rtm3d_op_maxpool launches it replaces up to fp32
  * summation order.  out_tensor < 0: the ordinary copy of `out` is not written (needs s2d_tensor).  s2d_tensor >= 0 (a plain tensor id here, -1 = none): `out` is written a second time in space-to-depth layout - pixel (y, x) to half-resolution
  * pixel (y >> 1, x >> 1), channels s2d_coff + ((y & 1) * 2 + (x & 1)) * 64 + c of s2d_tensor - which lets the neck read the
- * feature map at the resolution of the transposed conv's INPUT grid (rtm3d_amd/plan.py: RealizedPlan._neck_up_folds).        */
+ * feature map at the resolution of the transposed conv's INPUT grid (rtm3d_amd/plan.py: _neck_up_folds).        */
 int rtm3d_op_conv64_root(rtm3d_ctx* ctx, int in_tensor, int in_coff, int res_tensor, int res_coff, int conv_relu,
                          int w_conv_blob, int b_conv_blob, int w_root_blob, int b_root_blob,
                          int out_tensor, int out_coff, int root_relu, int pool_tensor, int pool_coff,

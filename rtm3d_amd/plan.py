@@ -6,9 +6,10 @@ orchestration").  ``build_plan`` walks the architecture once and emits a small I
   tensors : padded NHWC fp16 activations  {H, W, C, pad}
   ops     : input4 | conv | headout | maxpool | softmax   with BatchNorm already folded into weights/bias
 
-``realize`` packs the weights for the chosen kernel and records the plan into a runtime context
-through the C ABI.  The IR is plain numpy so the wiring (channel slices instead of torch.cat,
-sub-pixel phases of the transposed convolutions, BN folding) can be checked on a CPU-only
+``lower`` turns the IR into launches - fusions, level rewrites and the kernel of every conv decided, no
+device needed - and ``RealizedPlan`` packs their weights and records them into a runtime context through
+the C ABI.  The IR is plain numpy so the wiring (channel slices instead of torch.cat, sub-pixel phases
+of the transposed convolutions, BN folding) and the lowering's rewrites can be checked on a CPU-only
 machine by tests/plan_interp.py.
 
 Graph sources: models/nets/dla.py:186-210,322-332 (DLA-34 trees), models/nets/resnet.py:143-158,
@@ -29,7 +30,7 @@ FUSE_LEVEL_ENTRY = True   # DLA level2 entry: 2x2 max-pool + 1x1 project + 3x3 s
 FUSE_LEVEL_TAIL = True    # DLA level2 tail: tree2.conv2 + residual, the root 1x1 and the next level's 2x2 max-pool in one launch (conv64_root.hip)
 FOLD_PROJECT = True       # DLA levels 3-5: a block's `project` 1x1 (on the pooled input) as extra K-steps of the block's second conv
 FOLD_PROJECT_C128 = os.environ.get('RTM3D_FOLD_C128', '1') != '0'  # ... also where that conv would otherwise take conv128_halo (level3), which has no one-tap chunk: generic kernel
-FOLD_NECK_UP = os.environ.get('RTM3D_FOLD_NECK_UP', '1') != '0'   # neck: proj+head 1x1 composed INTO the transposed conv in front of it (RealizedPlan._neck_up_folds)
+FOLD_NECK_UP = os.environ.get('RTM3D_FOLD_NECK_UP', '1') != '0'   # neck: proj+head 1x1 composed INTO the transposed conv in front of it (_neck_up_folds)
 FUSE_STEM = True        # DLA stem: base_layer + level0 in one launch (conv_stem_fused.hip); False = two launches (A/B, tests)
 BN_EPS = 1e-4   # utils/torch_utils.py:79-81: initialize_weights sets eps=1e-4 on every BatchNorm2d
 
@@ -46,6 +47,7 @@ class Plan(object):
         self.tensors = []
         self.ops = []
         self.named = {}      # debug names -> Slice (stage outputs, for parity tests)
+        self.cache = None    # the WeightCache of the state dict (build_plan / build_peak_plan)
 
     # ---- IR construction
     def tensor(self, H, W, C, pad, name=None, fmt=None):
@@ -289,7 +291,7 @@ def _build_dla(P, sd, H, W, feat_out):
         if DLA34_LEVELS[i] == 1:
             level_root = i > 2
             # (level_root: the first block's intermediate map lives in the tensor that holds the pooled input, so that the block's
-            # `project` 1x1 can run as extra K-steps of its second conv: RealizedPlan._project_folds)
+            # `project` 1x1 can run as extra K-steps of its second conv: _project_folds)
             cat = P.tensor(Ho, Wo, 2 * cout + ((cin + cout) if level_root else 0), 1)
             mid = None
             if level_root:
@@ -512,7 +514,6 @@ def _build_plan(state_dict, backbone, B, H, W, head_variant, num_classes=3, dens
     return P
 
 
-# ------------------------------------------------------------------------------------------ realize
 def _build_heads_mx8(P, sd, z, heads, hn, nconv, hw):
     """The dense heads with head_precision='mxfp8': z -> MX8 (border 6), the d6 conv of all branches and the d1 convs on MX8
     operands; every head conv but the last writes MX8 (border 1), the last one fp16 for the logit convs (P.headout)."""
@@ -575,6 +576,7 @@ def choose_variant(cin, cout, M, groups, out_nchw, ntaps=9, stride=1):
     return 0
 
 
+# ------------------------------------------------------------------------------------------ kernels and weight packing
 def pack_mfma_weights(wt, bn):
     """wt: (taps, cout, cin) fp32 -> fp16 [ntile][kstep=(tap, cin/64)][bn rows][8 chunks][8] with the
     LDS bank swizzle (chunk ^= row & 7) baked in (see conv_mfma.hip)."""
@@ -626,11 +628,24 @@ def pack_smallc_weights(wt, rows=False):
     return np.ascontiguousarray(out).astype(np.float16).reshape(-1)
 
 
+_TAPS3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
+
+
+def _conv3x3(op, cin, cout, stride=1):
+    """A plain 3x3 / dilation 1 conv, one group, NHWC output."""
+    return (op['op'] == 'conv' and op['cin'] == cin and op['cout'] == cout and op['groups'] == 1 and op['in_stride'] == stride
+            and op['out_scale'] == 1 and not op['out_nchw'] and list(op['taps'][0]) == _TAPS3)
+
+
+def _conv1x1(op):
+    """A plain 1x1 conv, stride 1, one group, no residual, NHWC output."""
+    return (op['op'] == 'conv' and op['groups'] == 1 and list(op['taps'][0]) == [(0, 0)] and op['in_stride'] == 1 and op['out_scale'] == 1
+            and op['res'][0] is None and not op['out_nchw'])
+
+
 def conv64_eligible(op):
     """3x3 / stride 1 / dilation 1 / 64 -> 64 channels on a map that 8 x 32 pixel tiles cover: conv64_halo.hip."""
-    taps3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
-    return (op['cin'] == 64 and op['cout'] == 64 and op['groups'] == 1 and op['in_stride'] == 1 and op['out_scale'] == 1
-            and not op['out_nchw'] and list(op['taps'][0]) == taps3 and op['Hm'] % 8 == 0 and op['Wm'] % 32 == 0)
+    return _conv3x3(op, 64, 64) and op['Hm'] % 8 == 0 and op['Wm'] % 32 == 0
 
 
 BN_TILE_OVERRIDE = {}     # DIAGNOSTIC (bench.py --bn-tile): op name -> output-channel tile of the 128-pixel kernel, for A/B runs
@@ -643,18 +658,28 @@ def conv128_eligible(op, B):
     """3x3 / stride 1 / dilation 1 / 128 -> 128 channels on a map that 8 x 32 pixel tiles cover, with at least one tile per
     CU: conv128_halo.hip (DLA-34 level3, ResNet layer2).  (The kernel takes any multiples of 128 channels; the plan only
     sends it the layers it was measured to win on.)"""
-    taps3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
-    return (op['cin'] == 128 and op['cout'] == 128 and op['groups'] == 1 and op['in_stride'] == 1 and op['out_scale'] == 1
-            and not op['out_nchw'] and list(op['taps'][0]) == taps3 and op['Hm'] % 8 == 0 and op['Wm'] % 32 == 0
-            and B * (op['Hm'] // 8) * (op['Wm'] // 32) >= C128_MIN_TILES)
+    return (_conv3x3(op, 128, 128) and op['Hm'] % 8 == 0 and op['Wm'] % 32 == 0 and B * (op['Hm'] // 8) * (op['Wm'] // 32) >= C128_MIN_TILES)
 
 
 def conv64s2_eligible(op):
     """3x3 / STRIDE 2 / dilation 1 / 64 -> 128 channels onto a map that 4 x 32 pixel tiles cover: conv64s2_halo.hip."""
-    taps3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
-    return (USE_CONV64S2 and op['cin'] == 64 and op['cout'] == 128 and op['groups'] == 1 and op['in_stride'] == 2 and op['out_scale'] == 1
-            and not op['out_nchw'] and op['res'][0] is None and list(op['taps'][0]) == taps3 and op['Hm'] % 4 == 0 and op['Wm'] % 32 == 0
+    return (USE_CONV64S2 and _conv3x3(op, 64, 128, 2) and op['res'][0] is None and op['Hm'] % 4 == 0 and op['Wm'] % 32 == 0
             and 'tap_dc' not in op)
+
+
+def conv_kernel(op, B):
+    """Kernel variant (rtm3d_conv_desc.kernel) of a conv at batch B: the op's own 'variant' when it names one (tests), else
+    5 = conv64_halo.hip, 7 = conv64s2_halo.hip (with at least 64 of its 4 x 32-pixel tiles), 6 = conv128_halo.hip, else
+    choose_variant's 2 / 0 / 3."""
+    if op.get('variant') is not None:
+        return op['variant']
+    if conv64_eligible(op):
+        return 5
+    if conv64s2_eligible(op) and B * (op['Hm'] // 4) * (op['Wm'] // 32) >= 64:
+        return 7
+    if USE_CONV128 and conv128_eligible(op, B):
+        return 6
+    return choose_variant(op['cin'], op['cout'], B * op['Hm'] * op['Wm'], op['groups'], op['out_nchw'], len(op['taps'][0]), op['in_stride'])
 
 
 def pack_conv64s2_weights(wt):
@@ -673,11 +698,6 @@ def pack_conv64_weights(wt):
 
 
 S2D_ONLY = os.environ.get('RTM3D_S2D_ONLY', '1') != '0'   # a fused level tail skips the ordinary copy of its output when every reader can take the space-to-depth one
-
-
-def folds_pre(rp):
-    """(indices of convs that the project fold rewrites: they keep their ordinary input)"""
-    return set(rp._project_folds().keys()) if FOLD_PROJECT else set()
 
 
 def A_bias(J, D):
@@ -711,522 +731,483 @@ def pack_headout_weights(ws, biases):
     return np.ascontiguousarray(out).astype(np.float16).reshape(-1), bias.reshape(-1)
 
 
+# ------------------------------------------------------------------------------------------ lowering
+def op_reads(op):
+    """The Slices an IR op reads."""
+    if op['op'] in ('conv', 'conv_mx8'):
+        return list(op['inp']) + [r for r in op.get('res', ()) if r is not None]
+    if op['op'] == 'softmax':
+        return [op['z_in']] + list(op['us'])
+    return [op[k] for k in ('inp', 't') if k in op]          # maxpool, headout, quant_mx8; patch_mask (in place)
+
+
+def op_writes(op):
+    """The Slices an IR op writes (a conv's fp32 NCHW logits are not Slices)."""
+    if op['op'] in ('conv', 'conv_mx8'):
+        return [o for o in op['out'] if o is not None]
+    if op['op'] == 'softmax':
+        return [op['z_out']]
+    return [op[k] for k in ('out', 't') if k in op]          # input4, maxpool, quant_mx8; patch_mask (in place)
+
+
+def _overlap(a, b):
+    return a.tid == b.tid and a.coff < b.coff + b.C and b.coff < a.coff + a.C
+
+
+def _same(a, b):
+    return a.tid == b.tid and a.coff == b.coff and a.C == b.C
+
+
+def _readers(P, s, exclude=()):
+    """Indices of the ops, other than `exclude`, that read a channel of Slice s (a whole tensor: s = its tensor id)."""
+    if isinstance(s, int):
+        s = Slice(s, 0, P.tensors[s]['C'])
+    return [j for j, o in enumerate(P.ops) if j not in exclude and any(_overlap(r, s) for r in op_reads(o))]
+
+
+def _softmax_stat_producers(P):
+    """{conv op index: slot} for the convolutions whose epilogue can emit the spatial-softmax partials of a
+    fusion operand (rtm3d_conv_desc.softmax_stat_slot): every operand of a fusion must be the whole 256-channel
+    output of a conv that takes the halo-tile kernel (stride 1, taps within +-1 pixel, 8x32 tiles cover the
+    iteration domain, kernel variant 2), otherwise the fusion keeps its own reduction pass."""
+    slots = {}
+    for si, sop in enumerate(P.ops):
+        if sop['op'] != 'softmax':
+            continue
+        prods = []
+        for u in sop['us']:
+            cand = [k for k in range(si) if P.ops[k]['op'] == 'conv' and any(o.tid == u.tid for o in op_writes(P.ops[k]))]
+            if not cand or u.coff != 0 or u.C != 256 or P.tensors[u.tid]['C'] != 256:
+                prods = None
+                break
+            prods.append(cand[-1])
+        if prods is None or len(set(prods)) != len(prods) or len(prods) > 3:
+            continue
+        if all(conv_kernel(op, P.B) == 2 and op['cout'] == 256 and op['groups'] <= 4 and op['in_stride'] == 1 and not op['out_nchw']
+               and op['Hm'] % 8 == 0 and op['Wm'] % 32 == 0 and len(op['taps'][0]) in (4, 9)
+               and all(r is None for r in op['res']) and all(o.coff == 0 and o.C == 256 for o in op['out'])
+               and all(abs(dy) <= 1 and abs(dx) <= 1 for tp in op['taps'] for dy, dx in tp)
+               and P.tensors[op['inp'][0].tid]['pad'] >= 1 and op['cin'] % 64 == 0 and op['cin'] * len(op['taps'][0]) // 64 >= 4
+               for op in (P.ops[k] for k in prods)):
+            for i, k in enumerate(prods):
+                slots[k] = i
+    return slots
+
+
+def _stem_fusion_pairs(P):
+    """{index of the 7x7 NHWC4 stem conv: [index of the 3x3 16->16 conv that is its only consumer (, index of the 3x3
+    stride-2 16->32 conv that is THAT one's only consumer)]}: the chain becomes one launch (conv_stem_fused.hip) and
+    the 16-channel full-resolution maps between the layers never touch HBM.  FUSE_STEM: True = as deep as possible,
+    2 = the first two layers only (A/B, tests), False = off."""
+    def only_user(k, out):
+        users = _readers(P, out.tid, (k,))
+        return users[0] if len(users) == 1 and users[0] == k + 1 else None
+
+    def plain3x3(b, src, cin, cout, stride):
+        return (_conv3x3(b, cin, cout, stride) and b['relu'] and b['res'][0] is None and b['inp'][0].tid == src.tid
+                and b['inp'][0].coff == src.coff)
+
+    pairs = {}
+    for k, a in enumerate(P.ops):
+        if a['op'] != 'conv' or a['cin'] != 4 or a['cout'] != 16 or a['in_stride'] != 1 or len(a['taps'][0]) != 49 or not a['relu']:
+            continue
+        if a['Hm'] % 16 or a['Wm'] % 32 or P.tensors[a['inp'][0].tid]['pad'] < 4:
+            continue
+        j = only_user(k, a['out'][0])
+        if j is None or not plain3x3(P.ops[j], a['out'][0], 16, 16, 1):
+            continue
+        chain = [j]
+        j2 = only_user(j, P.ops[j]['out'][0])
+        if FUSE_STEM is True and j2 is not None and plain3x3(P.ops[j2], P.ops[j]['out'][0], 16, 32, 2) and P.ops[j2]['out'][0].coff % 8 == 0:
+            chain.append(j2)
+        pairs[k] = chain
+    return pairs
+
+
+def _level_entry_triples(P):
+    """{index of a 2x2/2 max-pool of a 32-channel map: [index of the 1x1 32->64 conv on the pooled map (no ReLU),
+    index of the 3x3 stride-2 32->64 conv (ReLU) on the SAME input]} when the pooled map has no other reader:
+    one launch (conv32s2_fused.hip)."""
+    out = {}
+    for k, m in enumerate(P.ops[:-2]):
+        if m['op'] != 'maxpool' or m['k'] != 2 or m['stride'] != 2 or m['pad'] != 0 or m['inp'].C != 32:
+            continue
+        pj, cv = P.ops[k + 1], P.ops[k + 2]
+        Hi, Wi = P.dims(m['inp'])
+        ok = (_readers(P, m['out'].tid, (k,)) == [k + 1]
+              and _conv1x1(pj) and pj['cin'] == 32 and pj['cout'] == 64 and not pj['relu']
+              and pj['inp'][0].tid == m['out'].tid and pj['inp'][0].coff == m['out'].coff
+              and _conv3x3(cv, 32, 64, 2) and cv['relu'] and cv['res'][0] is None
+              and cv['inp'][0].tid == m['inp'].tid and cv['inp'][0].coff == m['inp'].coff
+              and Hi % 16 == 0 and Wi % 64 == 0 and P.tensors[m['inp'].tid]['pad'] >= 1
+              and pj['out'][0].coff % 8 == 0 and cv['out'][0].coff % 8 == 0)
+        if ok:
+            out[k] = [k + 1, k + 2]
+    return out
+
+
+def _level_tail_chains(P):
+    """{index of a 64 -> 64 3x3 conv with a residual (conv64_halo-eligible): [index of the 1x1 128 -> 64 conv over
+    cat[that conv's output | its residual] (the tree's root; the conv's output has no other reader) (, index of a 2x2/2
+    max-pool of the root's output, when it directly follows)]}: one launch (conv64_root.hip); x2 is never written."""
+    out = {}
+    for k, cv in enumerate(P.ops[:-1]):
+        rt = P.ops[k + 1]
+        if cv['op'] != 'conv' or not conv64_eligible(cv) or cv['res'][0] is None or cv.get('variant') is not None:
+            continue
+        x2, x1 = cv['out'][0], cv['res'][0]
+        ok = (_conv1x1(rt) and rt['cin'] == 128 and rt['cout'] == 64 and rt.get('variant') is None
+              and x2.tid == x1.tid and x1.coff == x2.coff + 64 and rt['inp'][0].tid == x2.tid and rt['inp'][0].coff == x2.coff
+              and _readers(P, x2, (k,)) == [k + 1] and rt['out'][0].coff % 8 == 0
+              and not (rt['out'][0].tid == x2.tid and rt['out'][0].coff < x2.coff + 128 and x2.coff < rt['out'][0].coff + 64)
+              and rt['out'][0].tid != cv['inp'][0].tid
+              and not any(n.tid == x2.tid and n.coff < x2.coff + 64 and x2.coff < n.coff + n.C for n in P.named.values()))
+        if not ok:
+            continue
+        chain = [k + 1]
+        if k + 2 < len(P.ops):
+            m = P.ops[k + 2]
+            ro = rt['out'][0]
+            if (m['op'] == 'maxpool' and m['k'] == 2 and m['stride'] == 2 and m['pad'] == 0 and m['inp'].tid == ro.tid
+                    and m['inp'].coff == ro.coff and m['inp'].C == 64 and m['out'].coff % 8 == 0 and m['out'].tid != ro.tid):
+                chain.append(k + 2)
+        out[k] = chain
+    return out
+
+
+def _project_folds(P):
+    """{index of a block's second conv: index of the `project` 1x1 that produces its residual} where the 1x1 (no ReLU, stride
+    1, a multiple of 64 input channels) reads another channel slice of the tensor the conv reads, and nothing else reads its
+    output: conv(t) + bias + project(b) is ONE convolution over [t | b] whose extra taps are the centre pixel of b
+    (models/nets/dla.py:92-99,190-198: out = bn2(conv2(.)) + project(bottom), then ReLU).  Exact in real arithmetic; in fp16
+    storage it saves the rounding of the projected map.  The 1x1 launch, its output tensor and the residual read go away."""
+    out = {}
+    for k, c2 in enumerate(P.ops):
+        if (c2['op'] != 'conv' or c2['groups'] != 1 or c2['res'][0] is None or c2['in_stride'] != 1 or c2['out_scale'] != 1
+                or c2['out_nchw'] or c2['cin'] % 64 or c2.get('variant') is not None or 'tap_dc' in c2):
+            continue
+        R = c2['res'][0]
+        prods = [j for j in range(k) if P.ops[j]['op'] == 'conv' and any(o.tid == R.tid for o in op_writes(P.ops[j]))]
+        if len(prods) != 1:
+            continue
+        pj = P.ops[prods[0]]
+        ok = (_conv1x1(pj) and not pj['relu'] and pj['cin'] % 64 == 0 and pj['cout'] == c2['cout']
+              and pj['out'][0].coff == R.coff and pj['out'][0].C == R.C and pj.get('variant') is None and _readers(P, R.tid, prods) == [k]
+              and pj['inp'][0].tid == c2['inp'][0].tid and (pj['Hm'], pj['Wm']) == (c2['Hm'], c2['Wm'])
+              and len(c2['taps'][0]) * (c2['cin'] // 64) + pj['cin'] // 64 <= _lib.MAX_TAPS
+              and not any(n.tid == R.tid for n in P.named.values()))
+        # (conv64_halo.hip has no generic taps, conv128_halo.hip no one-tap chunk: with FOLD_PROJECT_C128 the fold takes the generic kernel)
+        kernel = conv_kernel(c2, P.B) if ok else None
+        if ok and kernel != 5 and (kernel != 6 or FOLD_PROJECT_C128):
+            out[k] = prods[0]
+    return out
+
+
+def _folded_conv(c2, pj):
+    cout, cpt, e = c2['cout'], c2['cin'] // 64, pj['cin'] // 64
+    taps, w2, wp = c2['taps'][0], c2['w'][0], pj['w'][0][0]              # w2: (taps, cout, cin), wp: (cout, cin_b)
+    wt = np.zeros((len(taps) * cpt + e, cout, 64), np.float32)
+    tl, dc = [], []
+    for t, (dy, dx) in enumerate(taps):
+        for q in range(cpt):
+            wt[t * cpt + q] = w2[t][:, q * 64:(q + 1) * 64]
+            tl.append((dy, dx)); dc.append(q * 64)
+    delta = pj['inp'][0].coff - c2['inp'][0].coff
+    for q in range(e):
+        wt[len(taps) * cpt + q] = wp[:, q * 64:(q + 1) * 64]
+        tl.append((0, 0)); dc.append(delta + q * 64)
+    op = dict(c2)
+    op.update(cin=64, taps=[tl], tap_dc=[dc], w=wt[None], bias=c2['bias'] + pj['bias'], res=[None], name=c2['name'] + '+project')
+    return op
+
+
+def _neck_up_folds(P, tail, stat_slots):
+    """Neck (models/nets/keypoint_fpn_fusion.py:35-46): x[i-1] = head(proj(cat[up(h), feat])) with up = ConvTranspose2d without
+    bias or non-linearity and proj∘head already composed into ONE 1x1 conv A = [A_up | A_f]:
+        out = A_up (up h) + A_f feat + b  =  up'(h) + A_f feat + b,     up' = the transposed conv with weights A_up W (per tap).
+    Run as ONE launch over the transposed conv's input grid, the 1x1's share of the FEATURE map is Cf / 64 more K-steps per
+    sub-pixel phase - provided the feature pixel (2y + py, 2x + px) can be addressed from grid position (y, x): the feature's
+    producer writes a second, space-to-depth copy into spare channels of the tensor that holds h (rtm3d_conv_desc.tap_dc names
+    them).  The `up` map (0.5 GB at bs=32 for the last level) is never written or read, one launch per level goes away.  (Round 2
+    tried the same algebra with the feature term as an epilogue residual of the transposed conv: slower.  Here it is K-steps.)
+    Matches (deconv D onto channels [0, 256) of T; 1x1 J over all of T = [up | feat]) where feat is written by the root of a
+    fused level tail (conv64_root.hip) or by a plain conv that can run on the 128-pixel kernel (both can emit the copy).
+    Returns [{'up', 'pj', 'hs', 'Cf', 'tail' | 'feat'}]."""
+    out = []
+    for kj, J in enumerate(P.ops):
+        if not _conv1x1(J) or J['relu'] or J['cout'] != 256 or J['cin'] <= 256 or (J['cin'] - 256) % 64 or J.get('variant') is not None:
+            continue
+        T, Cf = J['inp'][0], J['cin'] - 256
+        if T.coff != 0 or P.tensors[T.tid]['C'] != J['cin']:
+            continue
+        ups = [k for k in range(kj) if P.ops[k]['op'] == 'conv' and P.ops[k]['groups'] == 4 and P.ops[k]['out_scale'] == 2
+               and all(o is not None and o.tid == T.tid and o.coff == 0 and o.C == 256 for o in P.ops[k]['out'])]
+        if len(ups) != 1:
+            continue
+        ku = ups[0]
+        D = P.ops[ku]
+        hs = D['inp'][0]
+        ok = (D['cin'] == 256 and D['cout'] == 256 and all(len(tp) == 4 for tp in D['taps']) and not D['relu'] and all(r is None for r in D['res'])
+              and all(i.tid == hs.tid and i.coff == 0 for i in D['inp']) and hs.C == 256 and P.tensors[hs.tid]['C'] == 256
+              and P.tensors[hs.tid]['pad'] >= 1 and ku not in stat_slots and D.get('variant') is None
+              and (2 * D['Hm'], 2 * D['Wm']) == P.dims(J['out'][0]) and J['out'][0].tid not in (T.tid, hs.tid)
+              and ((P.B * D['Hm'] * D['Wm'] + 255) // 256) * 4 >= V2_MIN_TILES and 16 + Cf // 64 <= _lib.MAX_TAPS)
+        # nothing but J reads the `up` slice
+        ok = ok and _readers(P, Slice(T.tid, 0, 256), (ku,)) == [kj]
+        # who writes the feature slice [256, 256 + Cf)
+        fold = {'up': ku, 'pj': kj, 'hs': hs, 'Cf': Cf}
+        if ok:
+            feat = Slice(T.tid, 256, Cf)
+            kt = [k for k, ch in tail.items() if _same(P.ops[ch[0]]['out'][0], feat)]
+            kf = [k for k, o in enumerate(P.ops) if o['op'] == 'conv' and o['groups'] == 1 and o['out_scale'] == 1 and not o['out_nchw'] and o['cin'] % 64 == 0
+                  and o['out'][0] is not None and _same(o['out'][0], feat)
+                  and o.get('variant') is None and o['Hm'] % 2 == 0 and o['Wm'] % 2 == 0 and o['cout'] % 16 == 0
+                  and not any(k in ch for ch in tail.values()) and k not in tail]
+            if len(kt) == 1 and Cf == 64 and kt[0] < ku:
+                fold['tail'] = kt[0]
+            elif len(kf) == 1 and kf[0] < ku and not conv64s2_eligible(P.ops[kf[0]]):
+                fold['feat'] = kf[0]            # (the 128-pixel kernel, or conv64_halo.hip for a 64 -> 64 3x3: both can emit the copy)
+            else:
+                ok = False
+        # between the deconv's place and the 1x1's nothing may write h (the fused op runs at the 1x1's place)
+        ok = ok and not any(o.tid == hs.tid for j in range(ku + 1, kj) for o in op_writes(P.ops[j]))
+        if ok:
+            out.append(fold)
+    return out
+
+
+def _neck_fold_conv(P, f):
+    D, J, hs = P.ops[f['up']], P.ops[f['pj']], f['hs']
+    Cf, e = f['Cf'], f['Cf'] // 64
+
+    def make():
+        A = J['w'][0][0].astype(np.float64)                        # (256, 256 + Cf) = [A_up | A_f]
+        A_up, A_f = A[:, :256], A[:, 256:]
+        ws = []
+        for g in range(4):
+            wt = np.zeros((4 * 4 + e, 256, 64), np.float64)
+            for t in range(4):
+                Wc = A_up @ D['w'][g][t].astype(np.float64)        # (cout, cin) of the composed tap
+                for q in range(4):
+                    wt[t * 4 + q] = Wc[:, q * 64:(q + 1) * 64]
+            for q in range(e):
+                wt[16 + q] = A_f[:, q * 64:(q + 1) * 64]
+            ws.append(wt)
+        return np.stack(ws, 0).astype(np.float32)
+    w = P.cache.get('neckfold:%s|%s' % (D['name'], J['name']), make) if P.cache is not None else make()
+    taps, dcs = [], []
+    base = P.tensors[hs.tid]['C']                                   # the space-to-depth copy sits behind h's own channels
+    for g in range(4):
+        py, px = D['out_off'][g]
+        tl = [(dy, dx) for (dy, dx) in D['taps'][g] for _ in range(4)] + [(0, 0)] * e
+        dc = [q * 64 for _ in range(4) for q in range(4)] + [base + (py * 2 + px) * Cf + q * 64 for q in range(e)]
+        taps.append(tl); dcs.append(dc)
+    bias = J['bias'][0].astype(np.float64) + A_bias(J, D)
+    return {'op': 'conv', 'name': D['name'] + '+' + J['name'], 'inp': [hs] * 4, 'out': [J['out'][0]] * 4, 'res': [None] * 4,
+            'Hm': D['Hm'], 'Wm': D['Wm'], 'in_stride': 1, 'out_scale': 2, 'cin': 64, 'cout': 256, 'groups': 4, 'taps': taps, 'tap_dc': dcs,
+            'out_off': list(D['out_off']), 'relu': False, 'w': w, 'bias': np.tile(bias.astype(np.float32)[None], (4, 1)), 'out_nchw': 0,
+            'out_hw': (2 * D['Hm'], 2 * D['Wm'])}
+
+
+def _s2d_input_conv(op, hs, base, Cf):
+    """A stride-2 conv (taps within +-1) restated on the space-to-depth copy of its input - full-resolution pixel (2y + d, 2x + e)
+    is half-resolution pixel (y + d // 2, x + e // 2), phase (d % 2, e % 2) - as a STRIDE-1 conv over 64-channel pseudo-taps
+    (tap_dc): same products, same order within a tap."""
+    cout, cpt = op['cout'], op['cin'] // 64
+    taps, w = op['taps'][0], op['w'][0]                                  # (taps, cout, cin)
+    wt = np.zeros((len(taps) * cpt, cout, 64), np.float32)
+    tl, dc = [], []
+    for t, (dy, dx) in enumerate(taps):
+        for q in range(cpt):
+            wt[t * cpt + q] = w[t][:, q * 64:(q + 1) * 64]
+            tl.append((dy // 2, dx // 2)); dc.append(base + ((dy % 2) * 2 + (dx % 2)) * Cf + q * 64)
+    new = dict(op)
+    new.update(cin=64, in_stride=1, taps=[tl], tap_dc=[dc], w=wt[None], inp=[Slice(hs.tid, 0, 64)], name=op['name'] + '[s2d]')
+    return new
+
+
+def _plan_s2d_only(P, nfold, tail, folds):
+    """Which feature maps exist ONLY as their space-to-depth copy, and how their remaining readers take it; marks those folds
+    f['s2d_only'].  Returns (s2d_only: {(tid, coff, C) of the map: (Slice of the tensor, channel) of the copy}, s2d_readers:
+    {reader: ('conv64s2' | 'pool' | 'conv', Slice, channel, Cf)}, the plain convs that write such a map)."""
+    # a level tail whose ordinary output has, besides the folded 1x1 and its own pool, ONE reader that can take the space-to-depth
+    # copy instead (the next level's stride-2 entry on conv64s2_halo.hip) does not write the ordinary copy at all
+    s2d_only, s2d_readers, producers = {}, {}, set()
+    for f in nfold:
+        if 'tail' not in f or not S2D_ONLY:
+            continue
+        ro = P.ops[tail[f['tail']][0]]['out'][0]
+        readers = _readers(P, ro, set([f['tail'], f['up'], f['pj']] + list(tail[f['tail']])))
+        r = P.ops[readers[0]] if len(readers) == 1 else None
+        if (r is not None and r['op'] == 'conv' and r.get('variant') is None and conv_kernel(r, P.B) == 7
+                and r['inp'][0].coff == ro.coff and readers[0] not in folds):
+            f['s2d_only'] = True
+            s2d_readers[readers[0]] = ('conv64s2', f['hs'], P.tensors[f['hs'].tid]['C'], f['Cf'])
+            s2d_only[(ro.tid, ro.coff, ro.C)] = (f['hs'], P.tensors[f['hs'].tid]['C'])
+    # likewise a plain conv on the 128-pixel kernel (DLA level3 / level4 roots): every other reader of its output must be a 2x2 / 2
+    # max-pool (-> rtm3d_op_maxpool_s2d) or a stride-2 conv with taps within +-1 (-> the same conv restated on the copy)
+    for f in nfold:
+        if 'feat' not in f or not S2D_ONLY or conv64_eligible(P.ops[f['feat']]):
+            continue
+        ro = P.ops[f['feat']]['out'][0]
+        plan_ = {}
+        for j in _readers(P, ro, {f['feat'], f['up'], f['pj']}):
+            o = P.ops[j]
+            if o['op'] == 'maxpool' and o['k'] == 2 and o['stride'] == 2 and o['pad'] == 0 and _same(o['inp'], ro):
+                plan_[j] = 'pool'
+            elif (o['op'] == 'conv' and o['groups'] == 1 and o['in_stride'] == 2 and o['out_scale'] == 1 and _same(o['inp'][0], ro) and o['cin'] % 64 == 0
+                  and all(abs(dy) <= 1 and abs(dx) <= 1 for dy, dx in o['taps'][0]) and o.get('variant') is None and 'tap_dc' not in o
+                  and (o['res'][0] is None or o['res'][0].tid != ro.tid) and j not in folds
+                  and len(o['taps'][0]) * (o['cin'] // 64) <= _lib.MAX_TAPS and not conv64s2_eligible(o)):
+                plan_[j] = 'conv'
+            else:
+                plan_ = None
+                break
+        if plan_ is None:
+            continue
+        f['s2d_only'] = True
+        producers.add(f['feat'])
+        base = P.tensors[f['hs'].tid]['C']
+        for j, kind in plan_.items():
+            s2d_readers[j] = (kind, f['hs'], base, f['Cf'])
+        s2d_only[(ro.tid, ro.coff, ro.C)] = (f['hs'], base)
+    return s2d_only, s2d_readers, producers
+
+
+_BN_TILE = {7: 128, 6: 128, 5: 64, 2: 256, 3: 0}    # output-channel tile of the kernels that have one size
+
+
+def _conv_launch(P, k, op, ops, stat_slots, s2d_out, in_s2d, write_out):
+    """The launch of conv `op` (plan op k, or the rewrite of it that stands for plan ops `ops`) and every decision it takes:
+    kernel variant, bn tile, the space-to-depth copy it also writes (s2d_out) or reads instead of its input (in_s2d)."""
+    if s2d_out is not None and 'tap_dc' in op:
+        # (ADVICE r04) the producer of a space-to-depth copy was itself rewritten with per-tap channel offsets: no kernel with the
+        # second store takes tap_dc, so the copy would silently stay zero and the neck fold behind it would read zeros
+        raise RuntimeError('plan: %s must write a space-to-depth copy of its output but was rewritten with tap_dc (project fold); '
+                           'the two level rewrites exclude each other' % op['name'])
+    if not write_out and s2d_out is None:
+        raise RuntimeError('plan: %s is marked as writing only a space-to-depth copy but no copy was planned for it' % op['name'])
+    # a conv that writes a space-to-depth copy runs on a kernel whose epilogue has the second store
+    kernel = (5 if conv64_eligible(op) else 0) if s2d_out is not None else conv_kernel(op, P.B)
+    if in_s2d is not None and kernel != 7:
+        # (ADVICE r04) this conv's input exists ONLY as its space-to-depth copy, which kernel 7 alone can read
+        raise RuntimeError('plan: the input of %s exists only as a space-to-depth copy but the conv went to kernel variant %r' % (op['name'], kernel))
+    assert kernel != 7 or conv64s2_eligible(op), op['name']
+    assert kernel != 5 or conv64_eligible(op), op['name']
+    assert kernel != 3 or op['groups'] == 1, op['name']
+    bn = _BN_TILE.get(kernel)
+    if bn is None:                              # the 128-pixel kernel (conv_mfma.hip)
+        if op['cin'] % 64:
+            raise NotImplementedError('no HIP kernel for conv %s (cin=%d)' % (op['name'], op['cin']))
+        kernel = 0
+        bn = op.get('bn_tile') or BN_TILE_OVERRIDE.get(op['name']) or choose_bn_tile(op['cout'], P.B * op['Hm'] * op['Wm'])
+    return _launch('conv', op['name'], ops, op, kernel=kernel, bn_tile=bn, stat_slot=stat_slots.get(k, -1), s2d_out=s2d_out, write_out=write_out,
+                   in_s2d=in_s2d)
+
+
+def _launch(kind, name, ops, op, **decisions):
+    return dict({'kind': kind, 'name': name, 'ops': ops, 'op': op, 's2d_out': None, 'write_out': True}, **decisions)
+
+
+def lower(P):
+    """Plan P -> the runtime launches that record it, with every fusion, rewrite and kernel choice decided (no device).
+
+    Returns {'launches': [...], 'widen': {tensor id: extra channels for a space-to-depth copy}, 'stat_slots': {conv op index:
+    softmax partials slot}, 'unwritten': {(tid, coff, C) of plan output slices no launch writes}, 's2d_only': {(tid, coff, C)
+    of a map: (Slice of the tensor, channel) of the space-to-depth copy that is its only form on the device}}.
+    Each launch is a dict {'kind', 'name' (as recorded: RealizedPlan.op_names), 'ops' (the plan op indices it stands for),
+    'op' (the plan op, or its rewrite), 's2d_out', 'write_out'}; kind 'conv' adds 'kernel', 'bn_tile', 'stat_slot', 'in_s2d',
+    kind 'maxpool_s2d' 'in_s2d'.  Kinds: conv, stem_fused, conv32s2_fused, conv64_root, maxpool_s2d, and the IR op kinds."""
+    stat_slots = _softmax_stat_producers(P)
+    tail = _level_tail_chains(P) if FUSE_LEVEL_TAIL else {}
+    folds = _project_folds(P) if FOLD_PROJECT else {}
+    nfold = _neck_up_folds(P, tail, stat_slots) if FOLD_NECK_UP else []
+    s2d_only, s2d_readers, s2d_only_producers = _plan_s2d_only(P, nfold, tail, folds)
+    stem = _stem_fusion_pairs(P) if FUSE_STEM else {}
+    entry = _level_entry_triples(P) if FUSE_LEVEL_ENTRY else {}
+    copy_of = lambda f: (f['hs'], P.tensors[f['hs'].tid]['C'])           # the space-to-depth copy sits behind h's own channels
+    s2d_out = {f['feat']: copy_of(f) for f in nfold if 'feat' in f}
+    tail_fold = {f['tail']: f for f in nfold if 'tail' in f}
+    neck_by = {f['pj']: f for f in nfold}
+    skip = set(folds.values()) | {f['up'] for f in nfold}
+    # output slices that no launch writes (for verify.range_report): the `up` maps the neck fold composes away, the projected
+    # residuals, feature maps that exist only as their space-to-depth copy
+    unwritten = {(o.tid, o.coff, o.C) for k in skip for o in op_writes(P.ops[k])}
+    launches = []
+    for k, op in enumerate(P.ops):
+        if k in skip:
+            continue
+        name = op['name']
+        if k in stem:
+            launches.append(_launch('stem_fused', '+'.join([name] + [P.ops[j]['name'].split('.')[-1] for j in stem[k]]), [k] + stem[k], op))
+            skip.update(stem[k])
+            continue
+        if k in entry:
+            launches.append(_launch('conv32s2_fused', name + '+project+' + P.ops[entry[k][1]]['name'].split('.', 2)[-1], [k] + entry[k], op))
+            skip.update(entry[k])
+            continue
+        if k in tail:
+            pool = P.ops[tail[k][1]] if len(tail[k]) > 1 else None
+            f = tail_fold.get(k)
+            L = _launch('conv64_root', name + '+root' + ('+' + pool['name'].split('.', 1)[-1] if pool else '') + ('+s2d' if f else ''),
+                        [k] + tail[k], op, s2d_out=copy_of(f) if f else None, write_out=not (f and f.get('s2d_only')))
+            if not L['write_out']:
+                o = P.ops[tail[k][0]]['out'][0]
+                unwritten.add((o.tid, o.coff, o.C))
+            launches.append(L)
+            skip.update(tail[k])
+            continue
+        ops, in_s2d = [k], None
+        if k in folds:
+            op, ops = _folded_conv(op, P.ops[folds[k]]), [k, folds[k]]
+        if k in s2d_readers:
+            kind, hs, base, Cf = s2d_readers[k]
+            if kind == 'pool':
+                launches.append(_launch('maxpool_s2d', name, ops, op, in_s2d=(hs, base)))
+                continue
+            if kind == 'conv':
+                op = _s2d_input_conv(op, hs, base, Cf)
+            else:                               # (conv64s2_halo.hip reads the copy in place of the ordinary input)
+                in_s2d = (hs, base)
+        if k in neck_by:
+            op, ops = _neck_fold_conv(P, neck_by[k]), [neck_by[k]['up'], k]
+        if op['op'] != 'conv':
+            launches.append(_launch(op['op'], name, ops, op))
+            continue
+        L = _conv_launch(P, k, op, ops, stat_slots, s2d_out.get(k), in_s2d, k not in s2d_only_producers)
+        if not L['write_out']:
+            o = op['out'][0]
+            unwritten.add((o.tid, o.coff, o.C))
+        launches.append(L)
+    return {'launches': launches, 'widen': {f['hs'].tid: 4 * f['Cf'] for f in nfold}, 'stat_slots': stat_slots,
+            'unwritten': unwritten, 's2d_only': s2d_only}
+
+
 class RealizedPlan(object):
-    """A Plan recorded into a librtm3d_hip context."""
+    """A Plan recorded into a librtm3d_hip context: the launches of lower(plan), one rtm3d_* call sequence per launch kind."""
     def __init__(self, plan, device_index):
         lib = _lib.load()
-        self.lib, self.plan = lib, plan
-        self.cache = getattr(plan, 'cache', None)
+        self.lib, self.plan, self.cache = lib, plan, plan.cache
+        self.peak, self.yx_blob = None, None
         ctx = ctypes.c_void_p()
         _lib.check(lib.rtm3d_ctx_create(int(device_index), ctypes.byref(ctx)), 'ctx_create')
         self.ctx = ctx
-        self._keep = []
+        self.lowering = lower(plan)
+        self.unwritten = self.lowering['unwritten']
         self.tids = []
-        self._stat_slots = self._softmax_stat_producers()
-        tail = self._level_tail_chains() if FUSE_LEVEL_TAIL else {}
-        nfold = self._neck_up_folds(tail) if FOLD_NECK_UP else []
-        widen = {f['hs'].tid: 4 * f['Cf'] for f in nfold}    # device tensors that also hold a space-to-depth copy of a backbone feature
-        self._s2d_for = {f['feat']: (f['hs'], plan.tensors[f['hs'].tid]['C']) for f in nfold if 'feat' in f}
-        self._plan_s2d_only(nfold, tail)
         for i, t in enumerate(plan.tensors):
             tid = ctypes.c_int()
             if t.get('fmt') == 'mx8':             # (MX8 tensor ids are a namespace of their own)
                 _lib.check(lib.rtm3d_tensor_create_mx8(ctx, plan.B, t['H'], t['W'], t['C'], t['pad'], ctypes.byref(tid)), 'tensor_create_mx8')
             else:
-                _lib.check(lib.rtm3d_tensor_create(ctx, plan.B, t['H'], t['W'], t['C'] + widen.get(i, 0), t['pad'], ctypes.byref(tid)), 'tensor_create')
+                _lib.check(lib.rtm3d_tensor_create(ctx, plan.B, t['H'], t['W'], t['C'] + self.lowering['widen'].get(i, 0), t['pad'],
+                                                   ctypes.byref(tid)), 'tensor_create')
             self.tids.append(tid.value)
         self.op_names = []                      # one entry per RECORDED runtime op (a fused pair records one)
         self.weight_ranges = []                 # per recorded conv: largest |weight| / |bias| as realized (after the level rewrites)
-        fused = self._stem_fusion_pairs() if FUSE_STEM else {}
-        entry = self._level_entry_triples() if FUSE_LEVEL_ENTRY else {}
-        folds = self._project_folds() if FOLD_PROJECT else {}
-        skip = set(folds.values()) | {f['up'] for f in nfold}
-        s2d_of = {f['tail']: f for f in nfold if 'tail' in f}   # conv64_root launch -> the fold its second (space-to-depth) output feeds
-        neck_by = {f['pj']: f for f in nfold}
-        # output slices of the un-rewritten plan that this realization never writes (for verify.range_report): the `up` maps the
-        # neck fold composes away, the projected residuals, feature maps that exist only as their space-to-depth copy
-        self.unwritten = set()
-        for kk in skip:
-            for o in plan.ops[kk]['out'] if plan.ops[kk]['op'] == 'conv' else []:
-                if o is not None:
-                    self.unwritten.add((o.tid, o.coff, o.C))
-        for kk in getattr(self, '_s2d_only_producers', ()):
-            o = plan.ops[kk]['out'][0]
-            self.unwritten.add((o.tid, o.coff, o.C))
-        for kk, f in s2d_of.items():
-            if f.get('s2d_only'):
-                o = plan.ops[tail[kk][0]]['out'][0]
-                self.unwritten.add((o.tid, o.coff, o.C))
-        folded_by = {}
-        for c2k, pjk in folds.items():
-            folded_by[c2k] = self._folded_conv(plan.ops[c2k], plan.ops[pjk])
-        for k, op in enumerate(plan.ops):
-            self._k = k
-            if k in skip:
-                continue
-            if k in fused:
-                chain = [plan.ops[j] for j in fused[k]]
-                self._op_stem_fused(op, *chain)
-                self.op_names.append('+'.join([op['name']] + [c['name'].split('.')[-1] for c in chain]))
-                skip.update(fused[k])
-                continue
-            if k in entry:
-                proj, conv = plan.ops[entry[k][0]], plan.ops[entry[k][1]]
-                self._op_conv32s2_fused(op, proj, conv)
-                self.op_names.append(op['name'] + '+project+' + conv['name'].split('.', 2)[-1])
-                skip.update(entry[k])
-                continue
-            if k in tail:
-                root = plan.ops[tail[k][0]]
-                pool = plan.ops[tail[k][1]] if len(tail[k]) > 1 else None
-                f = s2d_of.get(k)
-                self._op_conv64_root(op, root, pool, s2d=(f['hs'], plan.tensors[f['hs'].tid]['C']) if f else None,
-                                     skip_out=bool(f and f.get('s2d_only')))
-                self.op_names.append(op['name'] + '+root' + ('+' + pool['name'].split('.', 1)[-1] if pool else '') + ('+s2d' if f else ''))
-                skip.update(tail[k])
-                continue
-            if k in folded_by:
-                op = folded_by[k]
-            if k in self._s2d_readers:
-                kind, hs_, base_, cf_ = self._s2d_readers[k]
-                if kind == 'pool':
-                    _lib.check(self.lib.rtm3d_op_maxpool_s2d(self.ctx, self.tids[hs_.tid], base_, self.tids[op['out'].tid], op['out'].coff, cf_), 'op_maxpool_s2d ' + op['name'])
-                    self.op_names.append(op['name'])
-                    continue
-                op = self._s2d_input_conv(op, hs_, base_, cf_)
-            if k in neck_by:
-                op = self._neck_fold_conv(neck_by[k])
-            getattr(self, '_op_' + op['op'])(op)
-            self.op_names.append(op['name'])
-
-    def _plan_s2d_only(self, nfold, tail):
-        """Which feature maps exist ONLY as their space-to-depth copy, and how their remaining readers take it (sets self._in_s2d_for,
-        self._s2d_only, self._s2d_readers, self._s2d_only_producers; marks the folds)."""
-        plan = self.plan
-        # a level tail whose ordinary output has, besides the folded 1x1 and its own pool, ONE reader that can take the space-to-depth
-        # copy instead (the next level's stride-2 entry on conv64s2_halo.hip) does not write the ordinary copy at all
-        self._in_s2d_for, self._s2d_only = {}, {}
-        for f in nfold:
-            if 'tail' not in f or not S2D_ONLY:
-                continue
-            ro = plan.ops[tail[f['tail']][0]]['out'][0]
-            own = set([f['tail'], f['up'], f['pj']] + list(tail[f['tail']]))
-            readers = [j for j, o in enumerate(plan.ops) if j not in own and self._reads(o, ro.tid) and self._reads_slice(o, ro)]
-            if (len(readers) == 1 and conv64s2_eligible(plan.ops[readers[0]]) and plan.ops[readers[0]].get('variant') is None
-                    and plan.B * (plan.ops[readers[0]]['Hm'] // 4) * (plan.ops[readers[0]]['Wm'] // 32) >= 64
-                    and plan.ops[readers[0]]['inp'][0].coff == ro.coff and readers[0] not in folds_pre(self)):
-                f['s2d_only'] = True
-                self._in_s2d_for[readers[0]] = (f['hs'], plan.tensors[f['hs'].tid]['C'])
-                self._s2d_only[(ro.tid, ro.coff, ro.C)] = (f['hs'], plan.tensors[f['hs'].tid]['C'])
-        # likewise a plain conv on the 128-pixel kernel (DLA level3 / level4 roots): every other reader of its output must be a 2x2 / 2
-        # max-pool (-> rtm3d_op_maxpool_s2d) or a stride-2 conv with taps within +-1 (-> the same conv restated on the copy)
-        self._s2d_readers, self._s2d_only_producers = {}, set()
-        for f in nfold:
-            if 'feat' not in f or not S2D_ONLY or conv64_eligible(plan.ops[f['feat']]):
-                continue
-            ro = plan.ops[f['feat']]['out'][0]
-            own = {f['feat'], f['up'], f['pj']}
-            readers = [j for j, o in enumerate(plan.ops) if j not in own and self._reads(o, ro.tid) and self._reads_slice(o, ro)]
-            plan_ = {}
-            for j in readers:
-                o = plan.ops[j]
-                same = lambda sl: sl.tid == ro.tid and sl.coff == ro.coff and sl.C == ro.C
-                if o['op'] == 'maxpool' and o['k'] == 2 and o['stride'] == 2 and o['pad'] == 0 and same(o['inp']):
-                    plan_[j] = 'pool'
-                elif (o['op'] == 'conv' and o['groups'] == 1 and o['in_stride'] == 2 and o['out_scale'] == 1 and same(o['inp'][0]) and o['cin'] % 64 == 0
-                      and all(abs(dy) <= 1 and abs(dx) <= 1 for dy, dx in o['taps'][0]) and o.get('variant') is None and 'tap_dc' not in o
-                      and (o['res'][0] is None or o['res'][0].tid != ro.tid) and j not in folds_pre(self)
-                      and len(o['taps'][0]) * (o['cin'] // 64) <= _lib.MAX_TAPS and not conv64s2_eligible(o)):
-                    plan_[j] = 'conv'
-                else:
-                    plan_ = None
-                    break
-            if plan_ is None:
-                continue
-            f['s2d_only'] = True
-            self._s2d_only_producers.add(f['feat'])
-            base = plan.tensors[f['hs'].tid]['C']
-            for j, kind in plan_.items():
-                self._s2d_readers[j] = (kind, f['hs'], base, f['Cf'])
-            self._s2d_only[(ro.tid, ro.coff, ro.C)] = (f['hs'], base)
-
-    @classmethod
-    def rewrites_only(cls, plan):
-        """An object that can find and build the realize-level rewrites of `plan` (project folds, level tails, neck up-folds)
-        WITHOUT a device context: for the CPU tests of their algebra and tap tables (tests/test_plan_cpu.py)."""
-        self = cls.__new__(cls)
-        self.plan, self.cache, self.ctx = plan, getattr(plan, 'cache', None), None
-        self._stat_slots = self._softmax_stat_producers()
-        return self
-
-    def _neck_up_folds(self, tail):
-        """Neck (models/nets/keypoint_fpn_fusion.py:35-46): x[i-1] = head(proj(cat[up(h), feat])) with up = ConvTranspose2d without
-        bias or non-linearity and proj∘head already composed into ONE 1x1 conv A = [A_up | A_f]:
-            out = A_up (up h) + A_f feat + b  =  up'(h) + A_f feat + b,     up' = the transposed conv with weights A_up W (per tap).
-        Run as ONE launch over the transposed conv's input grid, the 1x1's share of the FEATURE map is Cf / 64 more K-steps per
-        sub-pixel phase - provided the feature pixel (2y + py, 2x + px) can be addressed from grid position (y, x): the feature's
-        producer writes a second, space-to-depth copy into spare channels of the tensor that holds h (rtm3d_conv_desc.tap_dc names
-        them).  The `up` map (0.5 GB at bs=32 for the last level) is never written or read, one launch per level goes away.  (Round 2
-        tried the same algebra with the feature term as an epilogue residual of the transposed conv: slower.  Here it is K-steps.)
-        Matches (deconv D onto channels [0, 256) of T; 1x1 J over all of T = [up | feat]) where feat is written by the root of a
-        fused level tail (conv64_root.hip) or by a plain conv that can run on the 128-pixel kernel (both can emit the copy).
-        Returns [{'up', 'pj', 'hs', 'Cf', 'tail' | 'feat'}]."""
-        P = self.plan
-        out = []
-        for kj, J in enumerate(P.ops):
-            if (J['op'] != 'conv' or J['groups'] != 1 or list(J['taps'][0]) != [(0, 0)] or J['in_stride'] != 1 or J['out_scale'] != 1 or J['relu']
-                    or J['res'][0] is not None or J['out_nchw'] or J['cout'] != 256 or J['cin'] <= 256 or (J['cin'] - 256) % 64 or J.get('variant') is not None):
-                continue
-            T, Cf = J['inp'][0], J['cin'] - 256
-            if T.coff != 0 or P.tensors[T.tid]['C'] != J['cin']:
-                continue
-            ups = [k for k in range(kj) if P.ops[k]['op'] == 'conv' and P.ops[k]['groups'] == 4 and P.ops[k]['out_scale'] == 2
-                   and all(o is not None and o.tid == T.tid and o.coff == 0 and o.C == 256 for o in P.ops[k]['out'])]
-            if len(ups) != 1:
-                continue
-            ku = ups[0]
-            D = P.ops[ku]
-            hs = D['inp'][0]
-            ok = (D['cin'] == 256 and D['cout'] == 256 and all(len(tp) == 4 for tp in D['taps']) and not D['relu'] and all(r is None for r in D['res'])
-                  and all(i.tid == hs.tid and i.coff == 0 for i in D['inp']) and hs.C == 256 and P.tensors[hs.tid]['C'] == 256
-                  and P.tensors[hs.tid]['pad'] >= 1 and self._stat_slots_of(ku) < 0 and D.get('variant') is None
-                  and (2 * D['Hm'], 2 * D['Wm']) == P.dims(J['out'][0]) and J['out'][0].tid not in (T.tid, hs.tid)
-                  and ((P.B * D['Hm'] * D['Wm'] + 255) // 256) * 4 >= V2_MIN_TILES and 16 + Cf // 64 <= _lib.MAX_TAPS)
-            # nothing but J reads the `up` slice
-            readers = [j for j, o in enumerate(P.ops) if j != ku and self._reads_slice(o, Slice(T.tid, 0, 256))]
-            ok = ok and readers == [kj]
-            # who writes the feature slice [256, 256 + Cf)
-            fold = {'up': ku, 'pj': kj, 'hs': hs, 'Cf': Cf}
-            if ok:
-                kt = [k for k, ch in tail.items() if (lambda o: o.tid == T.tid and o.coff == 256 and o.C == Cf)(P.ops[ch[0]]['out'][0])]
-                kf = [k for k, o in enumerate(P.ops) if o['op'] == 'conv' and o['groups'] == 1 and o['out_scale'] == 1 and not o['out_nchw'] and o['cin'] % 64 == 0
-                      and o['out'][0] is not None and o['out'][0].tid == T.tid and o['out'][0].coff == 256 and o['out'][0].C == Cf
-                      and o.get('variant') is None and o['Hm'] % 2 == 0 and o['Wm'] % 2 == 0 and o['cout'] % 16 == 0
-                      and not any(k in ch for ch in tail.values()) and k not in tail]
-                if len(kt) == 1 and Cf == 64 and kt[0] < ku:
-                    fold['tail'] = kt[0]
-                elif len(kf) == 1 and kf[0] < ku and not conv64s2_eligible(P.ops[kf[0]]):
-                    fold['feat'] = kf[0]            # (the 128-pixel kernel, or conv64_halo.hip for a 64 -> 64 3x3: both can emit the copy)
-                else:
-                    ok = False
-            # between the deconv's place and the 1x1's nothing may write h (the fused op runs at the 1x1's place)
-            if ok:
-                for j in range(ku + 1, kj):
-                    o = P.ops[j]
-                    outs = o['out'] if o['op'] == 'conv' else [o.get('out')] if o['op'] == 'maxpool' else [o.get('z_out')] if o['op'] == 'softmax' else []
-                    if any(t is not None and t.tid == hs.tid for t in outs):
-                        ok = False
-            if ok:
-                out.append(fold)
-        return out
-
-    def _stat_slots_of(self, k):
-        return self._stat_slots.get(k, -1)
-
-    def _neck_fold_conv(self, f):
-        P = self.plan
-        D, J, hs = P.ops[f['up']], P.ops[f['pj']], f['hs']
-        Cf, e = f['Cf'], f['Cf'] // 64
-
-        def make():
-            A = J['w'][0][0].astype(np.float64)                        # (256, 256 + Cf) = [A_up | A_f]
-            A_up, A_f = A[:, :256], A[:, 256:]
-            ws = []
-            for g in range(4):
-                wt = np.zeros((4 * 4 + e, 256, 64), np.float64)
-                for t in range(4):
-                    Wc = A_up @ D['w'][g][t].astype(np.float64)        # (cout, cin) of the composed tap
-                    for q in range(4):
-                        wt[t * 4 + q] = Wc[:, q * 64:(q + 1) * 64]
-                for q in range(e):
-                    wt[16 + q] = A_f[:, q * 64:(q + 1) * 64]
-                ws.append(wt)
-            return np.stack(ws, 0).astype(np.float32)
-        w = self.cache.get('neckfold:%s|%s' % (D['name'], J['name']), make) if self.cache is not None else make()
-        taps, dcs = [], []
-        base = P.tensors[hs.tid]['C']                                   # the space-to-depth copy sits behind h's own channels
-        for g in range(4):
-            py, px = D['out_off'][g]
-            tl = [(dy, dx) for (dy, dx) in D['taps'][g] for _ in range(4)] + [(0, 0)] * e
-            dc = [q * 64 for _ in range(4) for q in range(4)] + [base + (py * 2 + px) * Cf + q * 64 for q in range(e)]
-            taps.append(tl); dcs.append(dc)
-        bias = J['bias'][0].astype(np.float64) + A_bias(J, D)
-        return {'op': 'conv', 'name': D['name'] + '+' + J['name'], 'inp': [hs] * 4, 'out': [J['out'][0]] * 4, 'res': [None] * 4,
-                'Hm': D['Hm'], 'Wm': D['Wm'], 'in_stride': 1, 'out_scale': 2, 'cin': 64, 'cout': 256, 'groups': 4, 'taps': taps, 'tap_dc': dcs,
-                'out_off': list(D['out_off']), 'relu': False, 'w': w, 'bias': np.tile(bias.astype(np.float32)[None], (4, 1)), 'out_nchw': 0,
-                'out_hw': (2 * D['Hm'], 2 * D['Wm'])}
-
-    @staticmethod
-    def _s2d_input_conv(op, hs, base, Cf):
-        """A stride-2 conv (taps within +-1) restated on the space-to-depth copy of its input - full-resolution pixel (2y + d, 2x + e)
-        is half-resolution pixel (y + d // 2, x + e // 2), phase (d % 2, e % 2) - as a STRIDE-1 conv over 64-channel pseudo-taps
-        (tap_dc): same products, same order within a tap."""
-        cout, cpt = op['cout'], op['cin'] // 64
-        taps, w = op['taps'][0], op['w'][0]                                  # (taps, cout, cin)
-        wt = np.zeros((len(taps) * cpt, cout, 64), np.float32)
-        tl, dc = [], []
-        for t, (dy, dx) in enumerate(taps):
-            for q in range(cpt):
-                wt[t * cpt + q] = w[t][:, q * 64:(q + 1) * 64]
-                tl.append((dy // 2, dx // 2)); dc.append(base + ((dy % 2) * 2 + (dx % 2)) * Cf + q * 64)
-        new = dict(op)
-        new.update(cin=64, in_stride=1, taps=[tl], tap_dc=[dc], w=wt[None], inp=[Slice(hs.tid, 0, 64)], name=op['name'] + '[s2d]')
-        return new
-
-    def _project_folds(self):
-        """{index of a block's second conv: index of the `project` 1x1 that produces its residual} where the 1x1 (no ReLU, stride
-        1, a multiple of 64 input channels) reads another channel slice of the tensor the conv reads, and nothing else reads its
-        output: conv(t) + bias + project(b) is ONE convolution over [t | b] whose extra taps are the centre pixel of b
-        (models/nets/dla.py:92-99,190-198: out = bn2(conv2(.)) + project(bottom), then ReLU).  Exact in real arithmetic; in fp16
-        storage it saves the rounding of the projected map.  The 1x1 launch, its output tensor and the residual read go away."""
-        P = self.plan
-        out = {}
-        for k, c2 in enumerate(P.ops):
-            if (c2['op'] != 'conv' or c2['groups'] != 1 or c2['res'][0] is None or c2['in_stride'] != 1 or c2['out_scale'] != 1
-                    or c2['out_nchw'] or c2['cin'] % 64 or c2.get('variant') is not None or 'tap_dc' in c2):
-                continue
-            R = c2['res'][0]
-            prods = [j for j in range(k) if P.ops[j]['op'] == 'conv' and any(o is not None and o.tid == R.tid for o in P.ops[j]['out'])]
-            if len(prods) != 1:
-                continue
-            pj = P.ops[prods[0]]
-            users = [j for j, o in enumerate(P.ops) if j != prods[0] and self._reads(o, R.tid)]
-            ok = (pj['groups'] == 1 and list(pj['taps'][0]) == [(0, 0)] and pj['in_stride'] == 1 and pj['out_scale'] == 1 and not pj['relu']
-                  and pj['res'][0] is None and not pj['out_nchw'] and pj['cin'] % 64 == 0 and pj['cout'] == c2['cout']
-                  and pj['out'][0].coff == R.coff and pj['out'][0].C == R.C and pj.get('variant') is None and users == [k]
-                  and pj['inp'][0].tid == c2['inp'][0].tid and (pj['Hm'], pj['Wm']) == (c2['Hm'], c2['Wm'])
-                  and len(c2['taps'][0]) * (c2['cin'] // 64) + pj['cin'] // 64 <= _lib.MAX_TAPS
-                  and not any(n.tid == R.tid for n in P.named.values()))
-            if ok and not FOLD_PROJECT_C128 and USE_CONV128 and conv128_eligible(c2, P.B):
-                ok = False
-            if ok and conv64_eligible(c2):
-                ok = False                      # (the register-resident 64-channel kernel has no generic taps)
-            if ok:
-                out[k] = prods[0]
-        return out
-
-    @staticmethod
-    def _folded_conv(c2, pj):
-        cout, cpt, e = c2['cout'], c2['cin'] // 64, pj['cin'] // 64
-        taps, w2, wp = c2['taps'][0], c2['w'][0], pj['w'][0][0]              # w2: (taps, cout, cin), wp: (cout, cin_b)
-        wt = np.zeros((len(taps) * cpt + e, cout, 64), np.float32)
-        tl, dc = [], []
-        for t, (dy, dx) in enumerate(taps):
-            for q in range(cpt):
-                wt[t * cpt + q] = w2[t][:, q * 64:(q + 1) * 64]
-                tl.append((dy, dx)); dc.append(q * 64)
-        delta = pj['inp'][0].coff - c2['inp'][0].coff
-        for q in range(e):
-            wt[len(taps) * cpt + q] = wp[:, q * 64:(q + 1) * 64]
-            tl.append((0, 0)); dc.append(delta + q * 64)
-        op = dict(c2)
-        op.update(cin=64, taps=[tl], tap_dc=[dc], w=wt[None], bias=c2['bias'] + pj['bias'], res=[None], name=c2['name'] + '+project')
-        return op
-
-    def _level_tail_chains(self):
-        """{index of a 64 -> 64 3x3 conv with a residual (conv64_halo-eligible): [index of the 1x1 128 -> 64 conv over
-        cat[that conv's output | its residual] (the tree's root; the conv's output has no other reader) (, index of a 2x2/2
-        max-pool of the root's output, when it directly follows)]}: one launch (conv64_root.hip); x2 is never written."""
-        P = self.plan
-        out = {}
-        for k, cv in enumerate(P.ops[:-1]):
-            rt = P.ops[k + 1]
-            if cv['op'] != 'conv' or not conv64_eligible(cv) or cv['res'][0] is None or cv.get('variant') is not None:
-                continue
-            x2, x1 = cv['out'][0], cv['res'][0]
-            users = [j for j, o in enumerate(P.ops) if j != k and self._reads(o, x2.tid) and self._reads_slice(o, x2)]
-            ok = (rt['op'] == 'conv' and rt['cin'] == 128 and rt['cout'] == 64 and rt['groups'] == 1 and list(rt['taps'][0]) == [(0, 0)]
-                  and rt['in_stride'] == 1 and rt['out_scale'] == 1 and rt['res'][0] is None and not rt['out_nchw'] and rt.get('variant') is None
-                  and x2.tid == x1.tid and x1.coff == x2.coff + 64 and rt['inp'][0].tid == x2.tid and rt['inp'][0].coff == x2.coff
-                  and users == [k + 1] and rt['out'][0].coff % 8 == 0
-                  and not (rt['out'][0].tid == x2.tid and rt['out'][0].coff < x2.coff + 128 and x2.coff < rt['out'][0].coff + 64)
-                  and rt['out'][0].tid != cv['inp'][0].tid
-                  and not any(n.tid == x2.tid and n.coff < x2.coff + 64 and x2.coff < n.coff + n.C for n in P.named.values()))
-            if not ok:
-                continue
-            chain = [k + 1]
-            if k + 2 < len(P.ops):
-                m = P.ops[k + 2]
-                ro = rt['out'][0]
-                if (m['op'] == 'maxpool' and m['k'] == 2 and m['stride'] == 2 and m['pad'] == 0 and m['inp'].tid == ro.tid
-                        and m['inp'].coff == ro.coff and m['inp'].C == 64 and m['out'].coff % 8 == 0 and m['out'].tid != ro.tid):
-                    chain.append(k + 2)
-            out[k] = chain
-        return out
-
-    @staticmethod
-    def _reads_slice(op, s):
-        """Does `op` read any channel of Slice s (same tensor)?"""
-        def hit(t, C):
-            return t is not None and t.tid == s.tid and t.coff < s.coff + s.C and s.coff < t.coff + C
-        if op['op'] == 'conv':
-            return any(hit(i, op['cin']) for i in op['inp']) or any(hit(r_, op['cout']) for r_ in op['res'])
-        if op['op'] in ('maxpool', 'headout'):
-            return hit(op['inp'], op['inp'].C)
-        if op['op'] == 'patch_mask':
-            return hit(op['t'], op['t'].C)
-        if op['op'] == 'softmax':
-            return hit(op['z_in'], op['z_in'].C) or any(hit(u, u.C) for u in op['us'])
-        if op['op'] == 'quant_mx8':
-            return hit(op['inp'], op['inp'].C)
-        if op['op'] == 'conv_mx8':
-            return any(hit(i, op['cin']) for i in op['inp'])
-        return False
-
-    def _op_conv64_root(self, cv, rt, pool, s2d=None, skip_out=False):
-        f32 = lambda v: self._blob(np.ascontiguousarray(v, np.float32))
-        x, x1, ro = cv['inp'][0], cv['res'][0], rt['out'][0]
-        po = pool['out'] if pool is not None else None
-        wc = self._packed(cv, 0, 'c64', 0, lambda: pack_conv64_weights(cv['w'][0]))
-        wr = self._packed(rt, 0, 'root64', 0, lambda: pack_root64_weights(rt['w'][0][0]))
-        _lib.check(self.lib.rtm3d_op_conv64_root(self.ctx, self.tids[x.tid], x.coff, self.tids[x1.tid], x1.coff, 1 if cv['relu'] else 0,
-                                                 self._blob(wc), f32(cv['bias'][0]), self._blob(wr), f32(rt['bias'][0]),
-                                                 -1 if skip_out else self.tids[ro.tid], ro.coff, 1 if rt['relu'] else 0,
-                                                 self.tids[po.tid] if po is not None else -1, po.coff if po is not None else 0,
-                                                 self.tids[s2d[0].tid] if s2d is not None else -1, s2d[1] if s2d is not None else 0),
-                   'op_conv64_root')
-
-    def _stem_fusion_pairs(self):
-        """{index of the 7x7 NHWC4 stem conv: [index of the 3x3 16->16 conv that is its only consumer (, index of the 3x3
-        stride-2 16->32 conv that is THAT one's only consumer)]}: the chain becomes one launch (conv_stem_fused.hip) and
-        the 16-channel full-resolution maps between the layers never touch HBM.  FUSE_STEM: True = as deep as possible,
-        2 = the first two layers only (A/B, tests), False = off."""
-        P = self.plan
-        taps3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
-
-        def only_user(k, out):
-            users = [j for j, o in enumerate(P.ops) if j != k and self._reads(o, out.tid)]
-            return users[0] if len(users) == 1 and users[0] == k + 1 else None
-
-        def plain3x3(b, src, cin, cout, stride):
-            return (b['op'] == 'conv' and b['cin'] == cin and b['cout'] == cout and b['groups'] == 1 and b['in_stride'] == stride
-                    and b['out_scale'] == 1 and list(b['taps'][0]) == taps3 and b['relu'] and b['res'][0] is None and not b['out_nchw']
-                    and b['inp'][0].tid == src.tid and b['inp'][0].coff == src.coff)
-
-        pairs = {}
-        for k, a in enumerate(P.ops):
-            if a['op'] != 'conv' or a['cin'] != 4 or a['cout'] != 16 or a['in_stride'] != 1 or len(a['taps'][0]) != 49 or not a['relu']:
-                continue
-            if a['Hm'] % 16 or a['Wm'] % 32 or P.tensors[a['inp'][0].tid]['pad'] < 4:
-                continue
-            j = only_user(k, a['out'][0])
-            if j is None or not plain3x3(P.ops[j], a['out'][0], 16, 16, 1):
-                continue
-            chain = [j]
-            j2 = only_user(j, P.ops[j]['out'][0])
-            if FUSE_STEM is True and j2 is not None and plain3x3(P.ops[j2], P.ops[j]['out'][0], 16, 32, 2) and P.ops[j2]['out'][0].coff % 8 == 0:
-                chain.append(j2)
-            pairs[k] = chain
-        return pairs
-
-    def _level_entry_triples(self):
-        """{index of a 2x2/2 max-pool of a 32-channel map: [index of the 1x1 32->64 conv on the pooled map (no ReLU),
-        index of the 3x3 stride-2 32->64 conv (ReLU) on the SAME input]} when the pooled map has no other reader:
-        one launch (conv32s2_fused.hip)."""
-        P = self.plan
-        taps3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
-        out = {}
-        for k, m in enumerate(P.ops[:-2]):
-            if m['op'] != 'maxpool' or m['k'] != 2 or m['stride'] != 2 or m['pad'] != 0 or m['inp'].C != 32:
-                continue
-            pj, cv = P.ops[k + 1], P.ops[k + 2]
-            users = [j for j, o in enumerate(P.ops) if j != k and self._reads(o, m['out'].tid)]
-            Hi, Wi = P.dims(m['inp'])
-            ok = (users == [k + 1] and pj['op'] == 'conv' and cv['op'] == 'conv'
-                  and pj['cin'] == 32 and pj['cout'] == 64 and pj['groups'] == 1 and list(pj['taps'][0]) == [(0, 0)] and pj['in_stride'] == 1
-                  and pj['out_scale'] == 1 and not pj['relu'] and pj['res'][0] is None and not pj['out_nchw']
-                  and pj['inp'][0].tid == m['out'].tid and pj['inp'][0].coff == m['out'].coff
-                  and cv['cin'] == 32 and cv['cout'] == 64 and cv['groups'] == 1 and list(cv['taps'][0]) == taps3 and cv['in_stride'] == 2
-                  and cv['out_scale'] == 1 and cv['relu'] and cv['res'][0] is None and not cv['out_nchw']
-                  and cv['inp'][0].tid == m['inp'].tid and cv['inp'][0].coff == m['inp'].coff
-                  and Hi % 16 == 0 and Wi % 64 == 0 and P.tensors[m['inp'].tid]['pad'] >= 1
-                  and pj['out'][0].coff % 8 == 0 and cv['out'][0].coff % 8 == 0)
-            if ok:
-                out[k] = [k + 1, k + 2]
-        return out
-
-    def _op_conv32s2_fused(self, pool, proj, conv):
-        def pack_conv():
-            w = conv['w'][0].reshape(9, 4, 16, 4, 8)                  # tap, ct, row, fk, j   (cin = fk * 8 + j)
-            return np.ascontiguousarray(w.transpose(0, 1, 3, 2, 4)).astype(np.float16).reshape(-1)     # [tap][ct][fk*16+row][8]
-
-        def pack_proj():
-            w = proj['w'][0].reshape(4, 16, 4, 8)                     # (1 tap) ct, row, fk, j
-            return np.ascontiguousarray(w.transpose(0, 2, 1, 3)).astype(np.float16).reshape(-1)
-        f32 = lambda v: self._blob(np.ascontiguousarray(v, np.float32))
-        x, oc, op = pool['inp'], conv['out'][0], proj['out'][0]
-        _lib.check(self.lib.rtm3d_op_conv32s2_fused(self.ctx, self.tids[x.tid], x.coff, self.tids[oc.tid], oc.coff, self.tids[op.tid], op.coff,
-                                                    self._blob(self._packed(conv, 0, 'c32s2', 0, pack_conv)), f32(conv['bias'][0]),
-                                                    self._blob(self._packed(proj, 0, 'c32p', 0, pack_proj)), f32(proj['bias'][0])),
-                   'op_conv32s2_fused')
-
-    @staticmethod
-    def _reads(op, tid):
-        if op['op'] == 'conv':
-            return any(s.tid == tid for s in op['inp']) or any(r is not None and r.tid == tid for r in op['res'])
-        if op['op'] in ('maxpool', 'headout'):
-            return op['inp'].tid == tid
-        if op['op'] == 'patch_mask':
-            return op['t'].tid == tid
-        if op['op'] == 'softmax':
-            return op['z_in'].tid == tid or any(u.tid == tid for u in op['us'])
-        if op['op'] == 'quant_mx8':
-            return op['inp'].tid == tid
-        if op['op'] == 'conv_mx8':
-            return any(s.tid == tid for s in op['inp'])
-        return False
-
-    def _op_stem_fused(self, a, b, c=None):
-        wb = self._packed(a, 0, 'smallc0', 0, lambda: pack_smallc_weights(a['w'][0], rows=False))
-        wl = self._packed(b, 0, 'smallc0', 0, lambda: pack_smallc_weights(b['w'][0], rows=False))
-        f32 = lambda v: self._blob(np.ascontiguousarray(v, np.float32))
-        last = c if c is not None else b
-        out = last['out'][0]
-        w1, b1 = -1, -1
-        if c is not None:
-            w1 = self._blob(self._packed(c, 0, 'smallc0', 0, lambda: pack_smallc_weights(c['w'][0], rows=False)))
-            b1 = f32(c['bias'][0])
-        _lib.check(self.lib.rtm3d_op_stem_fused(self.ctx, self.tids[a['inp'][0].tid], self.tids[out.tid], out.coff,
-                                                self._blob(wb), f32(a['bias'][0]), self._blob(wl), f32(b['bias'][0]), w1, b1),
-                   'op_stem_fused')
-
-    def _softmax_stat_producers(self):
-        """{conv op index: slot} for the convolutions whose epilogue can emit the spatial-softmax partials of a
-        fusion operand (rtm3d_conv_desc.softmax_stat_slot): every operand of a fusion must be the whole 256-channel
-        output of a conv that takes the halo-tile kernel (stride 1, taps within +-1 pixel, 8x32 tiles cover the
-        iteration domain, kernel variant 2), otherwise the fusion keeps its own reduction pass."""
-        P = self.plan
-        slots = {}
-        for si, sop in enumerate(P.ops):
-            if sop['op'] != 'softmax':
-                continue
-            prods = []
-            for u in sop['us']:
-                cand = [k for k in range(si) if P.ops[k]['op'] == 'conv'
-                        and any(o is not None and o.tid == u.tid for o in P.ops[k]['out'])]
-                if not cand or u.coff != 0 or u.C != 256 or P.tensors[u.tid]['C'] != 256:
-                    prods = None
-                    break
-                prods.append(cand[-1])
-            if prods is None or len(set(prods)) != len(prods) or len(prods) > 3:
-                continue
-            ok = True
-            for k in prods:
-                op = P.ops[k]
-                G = op['groups']
-                M = P.B * op['Hm'] * op['Wm']
-                variant = op.get('variant')
-                if variant is None:
-                    variant = choose_variant(op['cin'], op['cout'], M, G, op['out_nchw'], len(op['taps'][0]), op['in_stride'])
-                ok = ok and variant == 2 and op['cout'] == 256 and G <= 4 and op['in_stride'] == 1 and not op['out_nchw']
-                ok = ok and op['Hm'] % 8 == 0 and op['Wm'] % 32 == 0 and len(op['taps'][0]) in (4, 9)
-                ok = ok and all(r is None for r in op['res']) and all(o.coff == 0 and o.C == 256 for o in op['out'])
-                ok = ok and all(abs(dy) <= 1 and abs(dx) <= 1 for tp in op['taps'] for dy, dx in tp)
-                ok = ok and P.tensors[op['inp'][0].tid]['pad'] >= 1 and op['cin'] % 64 == 0 and op['cin'] * len(op['taps'][0]) // 64 >= 4
-            if ok:
-                for i, k in enumerate(prods):
-                    slots[k] = i
-        return slots
+        for L in self.lowering['launches']:
+            getattr(self, '_rec_' + L['kind'])(L)
+            self.op_names.append(L['name'])
 
     def _packed(self, op, g, kind, bn, make):
         """Packed weights of (layer, group, kernel variant): from the model's WeightCache when there is one."""
@@ -1240,7 +1221,59 @@ class RealizedPlan(object):
         _lib.check(self.lib.rtm3d_blob_create(self.ctx, arr.ctypes.data_as(ctypes.c_void_p), arr.nbytes, ctypes.byref(bid)), 'blob_create')
         return bid.value
 
-    def _op_conv(self, op):
+    def _f32(self, v):
+        return self._blob(np.ascontiguousarray(v, np.float32))
+
+    def _rec_stem_fused(self, L):
+        a, b, c = ([self.plan.ops[j] for j in L['ops']] + [None])[:3]
+        wb = self._packed(a, 0, 'smallc0', 0, lambda: pack_smallc_weights(a['w'][0], rows=False))
+        wl = self._packed(b, 0, 'smallc0', 0, lambda: pack_smallc_weights(b['w'][0], rows=False))
+        last = c if c is not None else b
+        out = last['out'][0]
+        w1, b1 = -1, -1
+        if c is not None:
+            w1 = self._blob(self._packed(c, 0, 'smallc0', 0, lambda: pack_smallc_weights(c['w'][0], rows=False)))
+            b1 = self._f32(c['bias'][0])
+        _lib.check(self.lib.rtm3d_op_stem_fused(self.ctx, self.tids[a['inp'][0].tid], self.tids[out.tid], out.coff,
+                                                self._blob(wb), self._f32(a['bias'][0]), self._blob(wl), self._f32(b['bias'][0]), w1, b1),
+                   'op_stem_fused')
+
+    def _rec_conv32s2_fused(self, L):
+        pool, proj, conv = [self.plan.ops[j] for j in L['ops']]
+
+        def pack_conv():
+            w = conv['w'][0].reshape(9, 4, 16, 4, 8)                  # tap, ct, row, fk, j   (cin = fk * 8 + j)
+            return np.ascontiguousarray(w.transpose(0, 1, 3, 2, 4)).astype(np.float16).reshape(-1)     # [tap][ct][fk*16+row][8]
+
+        def pack_proj():
+            w = proj['w'][0].reshape(4, 16, 4, 8)                     # (1 tap) ct, row, fk, j
+            return np.ascontiguousarray(w.transpose(0, 2, 1, 3)).astype(np.float16).reshape(-1)
+        x, oc, op = pool['inp'], conv['out'][0], proj['out'][0]
+        _lib.check(self.lib.rtm3d_op_conv32s2_fused(self.ctx, self.tids[x.tid], x.coff, self.tids[oc.tid], oc.coff, self.tids[op.tid], op.coff,
+                                                    self._blob(self._packed(conv, 0, 'c32s2', 0, pack_conv)), self._f32(conv['bias'][0]),
+                                                    self._blob(self._packed(proj, 0, 'c32p', 0, pack_proj)), self._f32(proj['bias'][0])),
+                   'op_conv32s2_fused')
+
+    def _rec_conv64_root(self, L):
+        cv, rt, pool = ([self.plan.ops[j] for j in L['ops']] + [None])[:3]
+        x, x1, ro = cv['inp'][0], cv['res'][0], rt['out'][0]
+        po, s2d = pool['out'] if pool is not None else None, L['s2d_out']
+        wc = self._packed(cv, 0, 'c64', 0, lambda: pack_conv64_weights(cv['w'][0]))
+        wr = self._packed(rt, 0, 'root64', 0, lambda: pack_root64_weights(rt['w'][0][0]))
+        _lib.check(self.lib.rtm3d_op_conv64_root(self.ctx, self.tids[x.tid], x.coff, self.tids[x1.tid], x1.coff, 1 if cv['relu'] else 0,
+                                                 self._blob(wc), self._f32(cv['bias'][0]), self._blob(wr), self._f32(rt['bias'][0]),
+                                                 self.tids[ro.tid] if L['write_out'] else -1, ro.coff, 1 if rt['relu'] else 0,
+                                                 self.tids[po.tid] if po is not None else -1, po.coff if po is not None else 0,
+                                                 self.tids[s2d[0].tid] if s2d is not None else -1, s2d[1] if s2d is not None else 0),
+                   'op_conv64_root')
+
+    def _rec_maxpool_s2d(self, L):
+        (hs, base), out = L['in_s2d'], L['op']['out']
+        _lib.check(self.lib.rtm3d_op_maxpool_s2d(self.ctx, self.tids[hs.tid], base, self.tids[out.tid], out.coff, out.C),
+                   'op_maxpool_s2d ' + L['name'])
+
+    def _rec_conv(self, L):
+        op, kernel, bn = L['op'], L['kernel'], L['bn_tile']
         # what this recorded conv stores as fp16 (the REALIZED weights: composed neck taps A_up W, summed fold biases ...):
         # Model.check_range reports them next to the un-rewritten plan's rows (verify.range_report(realized=...))
         self.weight_ranges.append({'op': op['name'], 'max_abs_w': float(np.abs(op['w']).max()) if np.size(op['w']) else 0.0,
@@ -1248,7 +1281,7 @@ class RealizedPlan(object):
         d = _lib.ConvDesc()
         G = op['groups']
         d.in_tensor = self.tids[op['inp'][0].tid]
-        d.out_tensor = self.tids[op['out'][0].tid] if op['out'][0] is not None else -1
+        d.out_tensor = self.tids[op['out'][0].tid] if op['out'][0] is not None and L['write_out'] else -1
         d.res_tensor = self.tids[op['res'][0].tid] if op['res'][0] is not None else -1
         d.Hm, d.Wm, d.in_stride, d.out_scale = op['Hm'], op['Wm'], op['in_stride'], op['out_scale']
         d.cin, d.cout, d.groups, d.ntaps = op['cin'], op['cout'], G, len(op['taps'][0])
@@ -1262,86 +1295,50 @@ class RealizedPlan(object):
                 d.tap_dy[g][t], d.tap_dx[g][t] = dy, dx
                 d.tap_dc[g][t] = op['tap_dc'][g][t] if 'tap_dc' in op else 0
         d.relu = 1 if op['relu'] else 0
-        d.softmax_stat_slot = self._stat_slots.get(self._k, -1)
+        d.softmax_stat_slot = L['stat_slot']
         d.out_nchw_f32 = op['out_nchw']
         d.out_H, d.out_W = op['out_hw']
         d.s2d_tensor, d.s2d_coff, d.in_s2d = 0, 0, 0              # s2d_tensor: tensor id + 1, 0 = none
-        M = self.plan.B * op['Hm'] * op['Wm']
-        variant = op.get('variant')
-        s2d = getattr(self, '_s2d_for', {}).get(self._k)
-        if s2d is not None and 'tap_dc' in op:
-            #  the producer of a space-to-depth copy was itself rewritten with per-tap channel offsets: no kernel with the
-            # second store takes tap_dc, so the copy would silently stay zero and the neck fold behind it would read zeros
-            raise RuntimeError('plan: %s must write a space-to-depth copy of its output but was rewritten with tap_dc (project fold); '
-                               'the two level rewrites exclude each other' % op['name'])
-        if self._k in getattr(self, '_s2d_only_producers', ()) and s2d is None:
-            raise RuntimeError('plan: %s is marked as writing only a space-to-depth copy but no copy was planned for it' % op['name'])
-        if s2d is not None:
-            # this conv's output feeds a neck up-fold: second copy in space-to-depth layout, 128-pixel kernel (the one whose epilogue has it)
-            d.s2d_tensor, d.s2d_coff = self.tids[s2d[0].tid] + 1, s2d[1]
-            variant = 5 if conv64_eligible(op) else 0
-            if self._k in getattr(self, '_s2d_only_producers', ()):
-                d.out_tensor = -1                 # every reader takes the copy: the ordinary output is not written
-        if variant is None:
-            variant = (5 if conv64_eligible(op) else 7 if conv64s2_eligible(op) and self.plan.B * (op['Hm'] // 4) * (op['Wm'] // 32) >= 64
-                       else 6 if USE_CONV128 and conv128_eligible(op, self.plan.B)
-                       else choose_variant(op['cin'], op['cout'], M, G, op['out_nchw'], len(op['taps'][0]), op['in_stride']))
-        if self._k in getattr(self, '_in_s2d_for', {}) and variant != 7:
-            #  this conv's input exists ONLY as its space-to-depth copy, which kernel 7 alone can read
-            raise RuntimeError('plan: the input of %s exists only as a space-to-depth copy but the conv went to kernel variant %r' % (op['name'], variant))
-        if variant == 7:
-            assert conv64s2_eligible(op), op['name']
-            d.kernel, d.bn_tile = 7, 128
-            src = getattr(self, '_in_s2d_for', {}).get(self._k)
-            if src is not None:                   # the producer wrote only the space-to-depth copy of this conv's input
-                d.in_tensor, d.in_coff[0], d.in_s2d = self.tids[src[0].tid], src[1], 1
-            d.w_blob = self._blob(self._packed(op, 0, 'c64s2', 0, lambda: pack_conv64s2_weights(op['w'][0])))
-            d.bias_blob = self._blob(np.ascontiguousarray(op['bias'][0], np.float32))
-        elif variant == 6:
-            d.kernel, d.bn_tile = 6, 128
-            d.w_blob = self._blob(self._packed(op, 0, 'mfma', 128, lambda: pack_mfma_weights(op['w'][0], 128)[0]))
-            d.bias_blob = self._blob(np.ascontiguousarray(op['bias'][0], np.float32))
-        elif variant == 5:
-            assert conv64_eligible(op), op['name']
-            d.kernel, d.bn_tile = 5, 64
-            d.w_blob = self._blob(self._packed(op, 0, 'c64', 0, lambda: pack_conv64_weights(op['w'][0])))
-            d.bias_blob = self._blob(np.ascontiguousarray(op['bias'][0], np.float32))
-        elif variant == 2:
+        if L['s2d_out'] is not None:
+            d.s2d_tensor, d.s2d_coff = self.tids[L['s2d_out'][0].tid] + 1, L['s2d_out'][1]
+        if L['in_s2d'] is not None:             # the producer wrote only the space-to-depth copy of this conv's input
+            d.in_tensor, d.in_coff[0], d.in_s2d = self.tids[L['in_s2d'][0].tid], L['in_s2d'][1], 1
+        d.kernel, d.bn_tile = kernel, bn
+        if kernel in (5, 6, 7):                 # conv64_halo / conv128_halo / conv64s2_halo: one group
+            kind, key_bn, pack = {5: ('c64', 0, pack_conv64_weights), 6: ('mfma', 128, lambda w: pack_mfma_weights(w, 128)[0]),
+                                  7: ('c64s2', 0, pack_conv64s2_weights)}[kernel]
+            d.w_blob = self._blob(self._packed(op, 0, kind, key_bn, lambda: pack(op['w'][0])))
+            d.bias_blob = self._f32(op['bias'][0])
+        elif kernel == 2:
             packed = [self._packed(op, g, 'mfma', 256, lambda g=g: pack_mfma_weights(op['w'][g], 256)[0]) for g in range(G)]
-            d.kernel, d.bn_tile = 2, 256
             d.w_blob, d.bias_blob = self._blob(np.concatenate(packed)), self._blob(np.ascontiguousarray(op['bias'], np.float32).reshape(-1))
-        elif variant == 3:
-            assert G == 1
-            d.kernel, d.bn_tile = 3, 0
+        elif kernel == 3:
             rows = op['cin'] == 16 and op['cout'] == 16 and op['in_stride'] == 1 and op['out_scale'] == 1 and len(op['taps'][0]) == 9
             d.w_blob = self._blob(self._packed(op, 0, 'smallc%d' % rows, 0, lambda: pack_smallc_weights(op['w'][0], rows=rows)))
             d.bias_blob = self._blob(op['bias'][0])
-        elif op['cin'] % 64 == 0:
-            bn = op.get('bn_tile') or BN_TILE_OVERRIDE.get(op['name']) or choose_bn_tile(op['cout'], M)
+        else:
             packed, biases = [], []
             for g in range(G):
-                pw = self._packed(op, g, 'mfma', bn, lambda g=g: pack_mfma_weights(op['w'][g], bn)[0])
-                cout_pad = (op['cout'] + bn - 1) // bn * bn
-                packed.append(pw)
-                bb = np.zeros(cout_pad, np.float32)
+                packed.append(self._packed(op, g, 'mfma', bn, lambda g=g: pack_mfma_weights(op['w'][g], bn)[0]))
+                bb = np.zeros((op['cout'] + bn - 1) // bn * bn, np.float32)
                 bb[:op['cout']] = op['bias'][g]
                 biases.append(bb)
-            d.kernel, d.bn_tile = 0, bn
             d.w_blob, d.bias_blob = self._blob(np.concatenate(packed)), self._blob(np.concatenate(biases))
-        else:
-            raise NotImplementedError('no HIP kernel for conv %s (cin=%d)' % (op['name'], op['cin']))
         _lib.check(self.lib.rtm3d_op_conv(self.ctx, ctypes.byref(d)), 'op_conv ' + op['name'])
 
-    def _op_headout(self, op):
+    def _rec_headout(self, L):
+        op = L['op']
         w, b = pack_headout_weights(op['w'], op['bias'])
         co = (ctypes.c_int * 4)(*([x.shape[0] for x in op['w']] + [0] * (4 - len(op['w']))))
         _lib.check(self.lib.rtm3d_op_headout(self.ctx, self.tids[op['inp'].tid], self._blob(w), self._blob(b), len(op['w']), co), 'op_headout')
 
-    def _op_quant_mx8(self, op):
+    def _rec_quant_mx8(self, L):
+        op = L['op']
         _lib.check(self.lib.rtm3d_op_quant_mx8(self.ctx, self.tids[op['inp'].tid], op['inp'].coff, self.tids[op['out'].tid], op['out'].coff,
                                                op['inp'].C), 'op_quant_mx8 ' + op['name'])
 
-    def _op_conv_mx8(self, op):
+    def _rec_conv_mx8(self, L):
+        op = L['op']
         self.weight_ranges.append({'op': op['name'], 'max_abs_w': float(np.abs(op['w']).max()), 'max_abs_bias': float(np.abs(op['bias']).max())})
         d = _lib.ConvMx8Desc()
         G = op['groups']
@@ -1361,18 +1358,25 @@ class RealizedPlan(object):
         d.bias_blob = self._blob(np.ascontiguousarray(op['bias'], np.float32).reshape(-1))
         _lib.check(self.lib.rtm3d_op_conv_mx8(self.ctx, ctypes.byref(d)), 'op_conv_mx8 ' + op['name'])
 
-    def _op_input4(self, op):
-        _lib.check(self.lib.rtm3d_op_input_nhwc4(self.ctx, self.tids[op['out'].tid]), 'op_input_nhwc4')
+    def _rec_input4(self, L):
+        _lib.check(self.lib.rtm3d_op_input_nhwc4(self.ctx, self.tids[L['op']['out'].tid]), 'op_input_nhwc4')
 
-    def _op_maxpool(self, op):
+    def _rec_maxpool(self, L):
+        op = L['op']
         _lib.check(self.lib.rtm3d_op_maxpool(self.ctx, self.tids[op['inp'].tid], op['inp'].coff, self.tids[op['out'].tid],
                                              op['out'].coff, op['inp'].C, op['k'], op['stride'], op['pad']), 'op_maxpool ' + op['name'])
 
-    def _op_patch_mask(self, op):
-        if getattr(self, 'yx_blob', None) is None:
+    def _rec_patch_mask(self, L):
+        if self.yx_blob is None:
             self.yx_blob = self._blob(np.full((self.plan.B, 2), -1, np.int32))
         Hm, Wm = self.plan.map_hw
-        _lib.check(self.lib.rtm3d_op_patch_mask(self.ctx, self.tids[op['t'].tid], self.yx_blob, Hm, Wm, op['origin']), 'op_patch_mask')
+        _lib.check(self.lib.rtm3d_op_patch_mask(self.ctx, self.tids[L['op']['t'].tid], self.yx_blob, Hm, Wm, L['op']['origin']), 'op_patch_mask')
+
+    def _rec_softmax(self, L):
+        op = L['op']
+        us = (ctypes.c_int * len(op['us']))(*[self.tids[u.tid] for u in op['us']])
+        _lib.check(self.lib.rtm3d_op_softmax_fuse(self.ctx, self.tids[op['z_in'].tid], self.tids[op['z_out'].tid], len(op['us']), us),
+                   'op_softmax_fuse')
 
     def tensor_info(self, s):
         """(device address of padded element [0][0][0][0], B, H, W, C, border) of the tensor a Slice lives in."""
@@ -1390,11 +1394,6 @@ class RealizedPlan(object):
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         _lib.check(self.lib.rtm3d_blob_address(self.ctx, bid, ctypes.byref(p), ctypes.byref(n)), 'blob_address')
         return int(n.value)
-
-    def _op_softmax(self, op):
-        us = (ctypes.c_int * len(op['us']))(*[self.tids[u.tid] for u in op['us']])
-        _lib.check(self.lib.rtm3d_op_softmax_fuse(self.ctx, self.tids[op['z_in'].tid], self.tids[op['z_out'].tid], len(op['us']), us),
-                   'op_softmax_fuse')
 
     # ---- execution
     def forward(self, stream, d_in, d_out4):
@@ -1461,7 +1460,7 @@ class RealizedPlan(object):
     def download(self, s):
         """Debug: fp32 NCHW copy of a Slice."""
         t = self.plan.tensors[s.tid]
-        src = getattr(self, '_s2d_only', {}).get((s.tid, s.coff, s.C))
+        src = self.lowering['s2d_only'].get((s.tid, s.coff, s.C))
         if src is not None:
             # only the space-to-depth copy of this map exists on the device: gather its four phase slices back
             out = np.empty((self.plan.B, s.C, t['H'], t['W']), np.float32)
@@ -1480,9 +1479,8 @@ class RealizedPlan(object):
         return out
 
     def close(self):
-        peak = getattr(self, 'peak', None)
-        if peak is not None:
-            peak.close()
+        if self.peak is not None:
+            self.peak.close()
             self.peak = None
         if self.ctx:
             self.lib.rtm3d_ctx_destroy(self.ctx)

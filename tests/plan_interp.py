@@ -6,8 +6,12 @@ graph wiring and BatchNorm folding can be validated against the oracle without a
 With ``half=True`` weights and stored activations are rounded to fp16 (fp32 accumulate), which
 predicts the numerical error of the fp16 MFMA path.
 """
+import copy
+
 import numpy as np
 import torch
+
+from rtm3d_amd.plan import _s2d_input_conv
 
 
 def run_plan(plan, x_nchw, half=False, prefill=None, yx=None):
@@ -62,7 +66,7 @@ def run_plan(plan, x_nchw, half=False, prefill=None, yx=None):
                     obuf, Po, Ho, Wo = view(o)
                     obuf[:, Po + oy: Po + oy + (Hm - 1) * sc + 1: sc, Po + ox: Po + ox + (Wm - 1) * sc + 1: sc, o.coff:o.coff + o.C] = rnd(acc)
         elif op['op'] == 's2d_copy':
-            # the second, space-to-depth output of a feature's producer (RealizedPlan._neck_up_folds): pixel (y, x) of `src` ->
+            # the second, space-to-depth output of a feature's producer (plan._neck_up_folds): pixel (y, x) of `src` ->
             # pixel (y >> 1, x >> 1), channels coff + ((y & 1) * 2 + (x & 1)) * C + c of tensor `tid`
             src = op['src']
             sbuf, Ps, Hs, Ws = view(src)
@@ -136,3 +140,31 @@ def run_plan(plan, x_nchw, half=False, prefill=None, yx=None):
         P = t['pad']
         return bufs[s.tid][:, P:P + t['H'], P:P + t['W'], s.coff:s.coff + s.C].permute(0, 3, 1, 2).contiguous()
     return outs, fetch
+
+
+def lowered_plan(plan, lowering):
+    """The plan as the launches of plan.lower(plan) run it, for run_plan: tensors widened for the space-to-depth copies, a fused
+    launch as its constituent plan ops, a rewritten conv as rewritten, plus what happens inside a launch: the producer's
+    second, space-to-depth output (s2d_copy) and, for a map that exists only as that copy, a wipe of the ordinary one
+    (zero_slice: a reader of it would see zeros)."""
+    Q = copy.copy(plan)
+    Q.tensors = [dict(t) for t in plan.tensors]
+    for tid, extra in lowering['widen'].items():
+        Q.tensors[tid]['C'] += extra
+    Q.ops = []
+    for L in lowering['launches']:
+        op = L['op']
+        if L['kind'] in ('stem_fused', 'conv32s2_fused', 'conv64_root'):
+            Q.ops += [plan.ops[j] for j in L['ops']]
+        elif L['kind'] == 'maxpool_s2d':
+            Q.ops.append({'op': 'maxpool_s2d', 'tid': L['in_s2d'][0].tid, 'coff': L['in_s2d'][1], 'out': op['out']})
+        elif L['kind'] == 'conv' and L['in_s2d'] is not None:       # (conv64s2_halo.hip reading the copy: the same conv restated on it)
+            Q.ops.append(_s2d_input_conv(op, L['in_s2d'][0], L['in_s2d'][1], op['cin']))
+        else:
+            Q.ops.append(op)
+        src = plan.ops[L['ops'][1]]['out'][0] if L['kind'] == 'conv64_root' else op['out'][0] if L['kind'] == 'conv' else None
+        if L['s2d_out'] is not None:
+            Q.ops.append({'op': 's2d_copy', 'src': src, 'tid': L['s2d_out'][0].tid, 'coff': L['s2d_out'][1]})
+        if not L['write_out']:
+            Q.ops.append({'op': 'zero_slice', 'slice': src})
+    return Q

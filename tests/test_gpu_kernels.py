@@ -330,7 +330,7 @@ def test_softmax_fuse_with_epilogue_partials():
     zin = rng.standard_normal((B, 256, 2 * H, 2 * W)).astype(np.float32)
     xin = [rng.standard_normal((B, 256, H, W)).astype(np.float32) for _ in range(3)]
     R = plan_mod.RealizedPlan(P, 0)
-    assert sorted(R._stat_slots.values()) == [0, 1, 2]
+    assert sorted(R.lowering['stat_slots'].values()) == [0, 1, 2]
     for s_, arr in [(z0, zin)] + list(zip(xs, xin)):
         _lib.check(R.lib.rtm3d_tensor_upload(R.ctx, R.tids[s_.tid], s_.coff, s_.C, np.ascontiguousarray(arr).ctypes.data_as(ctypes.c_void_p)))
     dummy = torch.zeros(16, device='cuda'); outs = [torch.zeros(16, device='cuda') for _ in range(4)]
@@ -547,7 +547,7 @@ def test_fused_level_tail_vs_torch(shape):
 
 @pytest.mark.parametrize('case', [(2, 24, 80, 128, 256, 64), (1, 12, 40, 256, 512, 0), (8, 48, 160, 64, 128, 0), (32, 24, 80, 128, 256, 0), (1, 6, 10, 256, 512, 64)])
 def test_project_fold_vs_torch(case):
-    """RealizedPlan._project_folds: a DLA block's `project` 1x1 (on the pooled input, another channel slice of the tensor the
+    """plan._project_folds: a DLA block's `project` 1x1 (on the pooled input, another channel slice of the tensor the
     block's second conv reads) as extra K-steps of that conv (rtm3d_conv_desc.tap_dc) instead of a launch + residual read:
     against plain PyTorch fp32 on fp16-rounded operands and against the two-launch path, on the 128-pixel kernel (incl. its
     small-launch split-K form) and the persistent 256-pixel one."""

@@ -440,7 +440,7 @@ def test_forward_stages_vs_oracle(dev, bb, shape):
 
 
 def test_neck_up_fold_vs_oracle(dev):
-    """RealizedPlan._neck_up_folds (round 4): the neck's composed proj3 + head2 1x1 folded INTO the transposed conv kfpn_up3 (the
+    """plan._neck_up_folds (round 4): the neck's composed proj3 + head2 1x1 folded INTO the transposed conv kfpn_up3 (the
     1x1's share of the backbone feature as one more K-step per sub-pixel phase, read from a space-to-depth copy that the fused
     level-2 tail writes): fused map z and logits against the oracle with the fold on and off - the fold must really have been
     taken (one launch fewer, kernel names) and both forms meet the same bars."""
@@ -465,7 +465,7 @@ def test_neck_up_fold_vs_oracle(dev):
             assert any('+s2d' in n for n in names) == fold, names
             z = plan.download(plan.plan.named['z'])
             # (with the fold the level-2 feature exists only as its space-to-depth copy: download() gathers the phases back)
-            assert bool(plan._s2d_only) == fold
+            assert bool(plan.lowering['s2d_only']) == fold
             errs = {'feat0': _rel_err(plan.download(plan.plan.named['feat0']), st['feats'][0].numpy()),
                     'feat1': _rel_err(plan.download(plan.plan.named['feat1']), st['feats'][1].numpy()),
                     'z': _rel_err(z, st['z'].numpy()), 'z_p999': float(np.percentile(np.abs(z - st['z'].numpy()), 99.9) / max(1.0, float(np.abs(st['z'].numpy()).max())))}

@@ -8,7 +8,7 @@ import torch
 
 from oracle import rtm3d_ref
 from rtm3d_amd import plan as plan_mod, weights
-from tests.plan_interp import run_plan
+from tests.plan_interp import lowered_plan, run_plan
 
 
 @pytest.mark.parametrize('bb', ['DLA-34', 'RESNET-18'])
@@ -44,73 +44,42 @@ def test_plan_header_depths_match_oracle(nconv):
 
 
 @pytest.mark.parametrize('bb', ['DLA-34', 'RESNET-18'])
-def test_realize_level_rewrites_keep_the_function(bb):
-    """Round 4: the rewrites RealizedPlan applies when it records a plan - a DLA block's `project` 1x1 as extra K-steps of the block's
+def test_lowered_launches_keep_the_function(bb, monkeypatch):
+    """Round 4: the rewrites the lowering applies when a plan is recorded - a DLA block's `project` 1x1 as extra K-steps of the block's
     second conv (rtm3d_conv_desc.tap_dc), the neck's proj+head 1x1 folded into the transposed conv in front of it with the feature read
-    from a space-to-depth copy - are exact in real arithmetic.  Checked WITHOUT a GPU: the rewritten op list (the same builders the
-    device path uses: _project_folds / _folded_conv / _neck_up_folds / _neck_fold_conv) through the CPU interpreter against the
-    original plan: fused map and logits to fp32 round-off; every fold really present."""
-    import copy
+    from a space-to-depth copy - are exact in real arithmetic.  Checked WITHOUT a GPU: the launches plan.lower returns (the ones
+    RealizedPlan records) through the CPU interpreter against the original plan: fused map and logits to fp32 round-off; every fold
+    really present."""
     sd = weights.synth_state_dict(bb, 3, 'trained')
     x = weights.synth_images(1, 64, 128, seed=5)
     P = plan_mod.build_plan(sd, bb, 1, 64, 128)
     outs0, fetch0 = run_plan(P, x)
-    v2_min = plan_mod.V2_MIN_TILES
-    plan_mod.V2_MIN_TILES = 1                   # (the neck fold is gated on a launch size the 64 x 128 test image does not reach)
-    try:
-        R = plan_mod.RealizedPlan.rewrites_only(P)
-        tail = R._level_tail_chains()
-        nfold = R._neck_up_folds(tail)
-        folds = R._project_folds()
-        R._plan_s2d_only(nfold, tail)
-    finally:
-        plan_mod.V2_MIN_TILES = v2_min
+    for k in ('FOLD_PROJECT', 'FUSE_LEVEL_TAIL', 'FOLD_NECK_UP', 'S2D_ONLY'):
+        monkeypatch.setattr(plan_mod, k, True)
+    monkeypatch.setattr(plan_mod, 'V2_MIN_TILES', 1)       # (the neck fold is gated on a launch size the 64 x 128 test image does not reach)
+    lowering = plan_mod.lower(P)
+    launches = lowering['launches']
+    folds = [L for L in launches if L['name'].endswith('+project')]
+    tails = [L for L in launches if L['kind'] == 'conv64_root']
+    necks = [L for L in launches if '+kfpn_proj' in L['name']]
     if bb == 'DLA-34':
-        assert len(folds) == 3 and len(tail) == 1 and len(nfold) == 3, (folds, tail, nfold)
+        assert len(folds) == 3 and len(tails) == 1 and len(necks) == 3, [L['name'] for L in launches]
     else:
-        assert len(folds) == 0 and len(nfold) >= 1, (folds, nfold)          # (ResNet's downsample 1x1s are stride 2: not foldable)
-    # rewritten plan: wider tensors for the space-to-depth copies, ops replaced
-    Q = copy.copy(P)
-    Q.tensors = [dict(t) for t in P.tensors]
-    for f in nfold:
-        Q.tensors[f['hs'].tid]['C'] += 4 * f['Cf']
-    skip = set(folds.values()) | {f['up'] for f in nfold}
-    neck_by = {f['pj']: f for f in nfold}
-    copy_after = {}
-    for f in nfold:
-        prod = tail[f['tail']][0] if 'tail' in f else f['feat']          # the op that writes the feature (the root of a fused tail, or a conv)
-        copy_after[prod] = {'op': 's2d_copy', 'src': P.ops[prod]['out'][0], 'tid': f['hs'].tid, 'coff': P.tensors[f['hs'].tid]['C']}
-    # features that exist only as their space-to-depth copy: the ordinary copy is wiped right after the copy is made, the readers
-    # are rewritten exactly as the device path rewrites them (a reader of the ordinary copy would then see zeros)
-    wipe_after = {}
-    for f in nfold:
-        if f.get('s2d_only'):
-            prod = tail[f['tail']][0] if 'tail' in f else f['feat']
-            wipe_after[prod] = {'op': 'zero_slice', 'slice': P.ops[prod]['out'][0]}
+        assert len(folds) == 0 and len(necks) >= 1, [L['name'] for L in launches]   # (ResNet's downsample 1x1s are stride 2: not foldable)
+    for L in necks:
+        assert len(L['op']['taps'][0]) == 16 + (P.ops[L['ops'][1]]['cin'] - 256) // 64 and L['op']['cin'] == 64
+    assert sum(L['s2d_out'] is not None for L in launches) == len(necks)        # one space-to-depth copy per neck fold
+    # features that exist only as their space-to-depth copy: the interpreted plan wipes the ordinary copy right after the copy is
+    # made, the readers take the copy as the launches do (a reader of the ordinary copy would then see zeros)
+    wiped = [L for L in launches if not L['write_out']]
     if bb == 'DLA-34':
-        assert len(wipe_after) == 2 and len(R._s2d_readers) == 4, (wipe_after.keys(), R._s2d_readers)     # level3 / level4 roots: pool + entry conv each
-    ops = []
-    for k, op in enumerate(P.ops):
-        if k in skip:
-            continue
-        if k in folds:
-            op = R._folded_conv(P.ops[k], P.ops[folds[k]])
-        if k in R._s2d_readers:
-            kind, hs_, base_, cf_ = R._s2d_readers[k]
-            op = {'op': 'maxpool_s2d', 'tid': hs_.tid, 'coff': base_, 'out': op['out']} if kind == 'pool' else R._s2d_input_conv(op, hs_, base_, cf_)
-        if k in neck_by:
-            op = R._neck_fold_conv(neck_by[k])
-            assert len(op['taps'][0]) == 16 + neck_by[k]['Cf'] // 64 and op['cin'] == 64
-        ops.append(op)
-        if k in copy_after:
-            ops.append(copy_after[k])
-        if k in wipe_after:
-            ops.append(wipe_after[k])
-    Q.ops = ops
-    assert len(Q.ops) == len(P.ops) - len(folds) + len(wipe_after)        # project ops gone; each neck fold: -2 ops + 1 copy op
+        s2d_readers = [L['name'] for L in launches if L['kind'] == 'maxpool_s2d' or L['name'].endswith('[s2d]')]
+        assert len(wiped) == 2 and len(s2d_readers) == 4, ([L['name'] for L in wiped], s2d_readers)   # level3 / level4 roots: pool + entry conv each
+    Q = lowered_plan(P, lowering)
+    assert len(Q.ops) == len(P.ops) - len(folds) + len(wiped)        # project ops gone; each neck fold: -2 ops + 1 copy op
     outs1, fetch1 = run_plan(Q, x)
     np.testing.assert_allclose(fetch1(P.named['z']).numpy(), fetch0(P.named['z']).numpy(), atol=2e-5, rtol=1e-5)
-    wiped = {(w['slice'].tid, w['slice'].coff) for w in wipe_after.values()}
+    wiped = {(o['slice'].tid, o['slice'].coff) for o in Q.ops if o['op'] == 'zero_slice'}
     for i in range(4):
         sl = P.named['feat%d' % i]
         if (sl.tid, sl.coff) in wiped:
