@@ -101,11 +101,7 @@ typedef struct rtm3d_conv_desc {
                                               map the conv is stated on (Hm, Wm, taps, stride as for the ordinary map) */
     int relu;
     int w_blob, bias_blob;                 /* packed fp16 weights (layout depends on `kernel`), fp32 bias [groups][cout_pad] */
-    int kernel;                            /* 0 = MFMA implicit GEMM 128-px tile (cin % 64 == 0), 2 = MFMA 256x256 tile
-                                              (cout % 256 == 0), 3 = register-direct MFMA (cin 4/16/32), 5 = 64->64 3x3 halo kernel,
-                                              filter bank in registers (W % 32 == 0, H % 8 == 0), 6 = 3x3 halo kernel for cin, cout % 128 == 0, weights
-                                              in the bn_tile = 128 packing of kernel 0 (W % 32 == 0, H % 8 == 0), 7 = 64->128 3x3 STRIDE-2 halo kernel, filter bank in
-                                              registers (output W % 32 == 0, H % 4 == 0; weights fp16 [9 taps][2 k halves][8 tiles][64 lanes][8]); 1 is retired */
+    int kernel;                            /* one of RTM3D_CONV_* below */
     int bn_tile;                           /* MFMA: cout tile the weights were packed for (16/32/64/128) */
     int out_nchw_f32;                      /* 0, or 1..4 = index+1 into rtm3d_forward's out_logits[] */
     int out_H, out_W;                      /* only for out_nchw_f32 */
@@ -116,6 +112,15 @@ typedef struct rtm3d_conv_desc {
                                               (taps within +-1 pixel, stride 1, Hm % 8 == 0, Wm % 32 == 0) with cout = 256 written at
                                               channel offset 0 of a 256-channel tensor; anything else is refused. */
 } rtm3d_conv_desc;
+/* rtm3d_conv_desc.kernel (1 and 4 are retired and refused) */
+#define RTM3D_CONV_MFMA128 0      /* MFMA implicit GEMM, 128-px tile (cin % 64 == 0) */
+#define RTM3D_CONV_MFMA256 2      /* MFMA 256x256 tile (cout % 256 == 0) */
+#define RTM3D_CONV_SMALLC 3       /* register-direct MFMA (cin 4/16/32) */
+#define RTM3D_CONV_C64_HALO 5     /* 64->64 3x3 halo kernel, filter bank in registers (W % 32 == 0, H % 8 == 0) */
+#define RTM3D_CONV_C128_HALO 6    /* 3x3 halo kernel for cin, cout % 128 == 0, weights in the bn_tile = 128 packing of RTM3D_CONV_MFMA128
+                                     (W % 32 == 0, H % 8 == 0) */
+#define RTM3D_CONV_C64S2_HALO 7   /* 64->128 3x3 STRIDE-2 halo kernel, filter bank in registers (output W % 32 == 0, H % 4 == 0; weights fp16
+                                     [9 taps][2 k halves][8 tiles][64 lanes][8]) */
 int rtm3d_op_conv(rtm3d_ctx* ctx, const rtm3d_conv_desc* desc);
 
 /* DLA-34 stem, fused (models/nets/dla.py:259-279): base_layer 7x7 3->16 + BN + ReLU, level0 3x3 16->16 + BN + ReLU and - when

@@ -10,6 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, '_C', 'librtm3d_hip.so')
 ABI_VERSION = 9
 MAX_GROUPS, MAX_TAPS = 4, 80
+# rtm3d_conv_desc.kernel (RTM3D_CONV_* in rtm3d_hip.h)
+CONV_MFMA128, CONV_MFMA256, CONV_SMALLC, CONV_C64_HALO, CONV_C128_HALO, CONV_C64S2_HALO = 0, 2, 3, 5, 6, 7
 
 c_int, c_void_p, c_float, c_size_t = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_size_t
 c_double = ctypes.c_double

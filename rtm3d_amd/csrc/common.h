@@ -59,12 +59,6 @@ static __device__ __forceinline__ const void* rt_uniform_ptr(const void* p) {
 #define RT_MAX_GROUPS 4
 #define RT_MAX_TAPS 80
 
-// Geometry of one padded NHWC fp16 activation tensor as the kernels see it.
-struct TensorView {
-    f16* base;          // element [n=0][yp=0][xp=0][c=0] of the padded buffer
-    int Hp, Wp, C, P;   // padded height/width, channel pitch, border width
-};
-
 struct ConvGroupArgs {
     int in_coff, out_coff, res_coff;
     int out_oy, out_ox;
@@ -98,14 +92,10 @@ struct ConvKArgs {
     ConvGroupArgs g[RT_MAX_GROUPS];
 };
 
-struct StemKArgs {
-    const float* in;      // fp32 NCHW (B,3,H,W)
-    const float* wgt;     // fp32 [ky][kx][ci][co]
-    const float* bias;    // fp32 [co]
-    f16* out;
-    int B, H, W, Ho, Wo, stride, pad;
-    int out_Hp, out_Wp, out_C, out_P;
-};
+// halo-tile conv256 kernels (conv_mfma256.hip dispatches, conv_mfma256_halo.hip runs): per group, all taps packed into one
+// 64-bit word (4 bits per tap: dy+1 in bits 0-1, dx+1 in bits 2-3) that lives in SGPRs for the whole tile: an s_load per
+// K-tile would put its latency in front of the operand reads
+struct HaloTaps { unsigned long long taps[RT_MAX_GROUPS]; };
 
 struct PoolKArgs {
     const f16* in; f16* out;
@@ -224,6 +214,11 @@ struct QuantMx8Args {
     int out_Hp, out_Wp, out_C, out_P, out_coff;
     int nblk;               // channels / 32
 };
+
+// Launch size of a persistent kernel over `total` tiles: at most one workgroup per CU; single = every workgroup owns exactly
+// one tile and draws no ticket
+struct PersistentGrid { int grid, single; };
+inline PersistentGrid persistent_grid(int total, int cu_count) { return {cu_count < total ? cu_count : total, total <= cu_count ? 1 : 0}; }
 
 // kernel launchers (each returns hipGetLastError())
 hipError_t launch_patch_mask(const PatchMaskArgs& a, hipStream_t s);

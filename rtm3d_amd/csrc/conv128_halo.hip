@@ -269,8 +269,8 @@ bool conv128_halo_supported(const ConvKArgs& a, int groups) {
 
 hipError_t launch_conv128_halo(const ConvKArgs& a, int cu_count, unsigned int* ticket_ctr, hipStream_t s) {
     const int total = (a.M / a.HmWm) * (a.Wm >> 5) * ((a.HmWm / a.Wm) >> 3) * (a.cout / 128);
-    const int grid = cu_count < total ? cu_count : total;
-    if (a.res) hipLaunchKernelGGL(conv128_halo_kernel<1>, dim3(grid), dim3(512), 0, s, a, ticket_ctr, total <= cu_count ? 1 : 0);
-    else hipLaunchKernelGGL(conv128_halo_kernel<0>, dim3(grid), dim3(512), 0, s, a, ticket_ctr, total <= cu_count ? 1 : 0);
+    const auto [grid, single] = persistent_grid(total, cu_count);
+    if (a.res) hipLaunchKernelGGL(conv128_halo_kernel<1>, dim3(grid), dim3(512), 0, s, a, ticket_ctr, single);
+    else hipLaunchKernelGGL(conv128_halo_kernel<0>, dim3(grid), dim3(512), 0, s, a, ticket_ctr, single);
     return hipGetLastError();
 }

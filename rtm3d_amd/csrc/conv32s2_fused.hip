@@ -161,7 +161,7 @@ __global__ __launch_bounds__(512) void conv32s2_fused_kernel(const Conv32S2Args 
 
 hipError_t launch_conv32s2_fused(const Conv32S2Args& a, int cu_count, unsigned int* ticket_ctr, hipStream_t s) {
     const int total = a.B * (a.Wo >> 5) * (a.Ho >> 3);
-    const int grid = cu_count < total ? cu_count : total;
-    hipLaunchKernelGGL(conv32s2_fused_kernel, dim3(grid), dim3(512), 0, s, a, ticket_ctr, total <= cu_count ? 1 : 0);
+    const auto [grid, single] = persistent_grid(total, cu_count);
+    hipLaunchKernelGGL(conv32s2_fused_kernel, dim3(grid), dim3(512), 0, s, a, ticket_ctr, single);
     return hipGetLastError();
 }

@@ -227,8 +227,7 @@ bool conv64_halo_supported(const ConvKArgs& a, int groups) {
 
 hipError_t launch_conv64_halo(const ConvKArgs& a, int cu_count, unsigned int* ticket_ctr, hipStream_t s) {
     const int total = (a.M / a.HmWm) * (a.Wm >> 5) * ((a.HmWm / a.Wm) >> 3);
-    int grid = cu_count < total ? cu_count : total;
-    const int single = total <= cu_count ? 1 : 0;
+    const auto [grid, single] = persistent_grid(total, cu_count);
     if (a.res && a.s2d) hipLaunchKernelGGL((conv64_halo_kernel<1, 1>), dim3(grid), dim3(512), 0, s, a, ticket_ctr, single);
     else if (a.res) hipLaunchKernelGGL((conv64_halo_kernel<1, 0>), dim3(grid), dim3(512), 0, s, a, ticket_ctr, single);
     else if (a.s2d) hipLaunchKernelGGL((conv64_halo_kernel<0, 1>), dim3(grid), dim3(512), 0, s, a, ticket_ctr, single);

@@ -316,12 +316,9 @@ __global__ __launch_bounds__(512) void conv64_root_kernel(const ConvKArgs a, con
     }
 }
 
-bool conv64_halo_supported(const ConvKArgs& a, int groups);
-
 hipError_t launch_conv64_root(const ConvKArgs& a, const RootKArgs& r, int cu_count, unsigned int* ticket_ctr, hipStream_t s) {
     const int total = (a.M / a.HmWm) * (a.Wm >> 5) * ((a.HmWm / a.Wm) >> 3);
-    const int grid = cu_count < total ? cu_count : total;
-    const int single = total <= cu_count ? 1 : 0;
+    const auto [grid, single] = persistent_grid(total, cu_count);
     if (!r.out && !r.s2d) return hipErrorInvalidValue;
     if (r.pool && r.s2d && !r.out) hipLaunchKernelGGL((conv64_root_kernel<1, 1, 0>), dim3(grid), dim3(512), 0, s, a, r, ticket_ctr, single);
     else if (r.s2d && !r.out) hipLaunchKernelGGL((conv64_root_kernel<0, 1, 0>), dim3(grid), dim3(512), 0, s, a, r, ticket_ctr, single);

@@ -248,7 +248,7 @@ bool conv64s2_halo_supported(const ConvKArgs& a, int groups) {
 
 hipError_t launch_conv64s2_halo(const ConvKArgs& a, int cu_count, unsigned int* ticket_ctr, hipStream_t s) {
     const int total = (a.M / a.HmWm) * (a.Wm / S2_TW) * ((a.HmWm / a.Wm) / S2_TH);
-    const int grid = cu_count < total ? cu_count : total;
-    hipLaunchKernelGGL(conv64s2_halo_kernel, dim3(grid), dim3(512), 0, s, a, ticket_ctr, total <= cu_count ? 1 : 0);
+    const auto [grid, single] = persistent_grid(total, cu_count);
+    hipLaunchKernelGGL(conv64s2_halo_kernel, dim3(grid), dim3(512), 0, s, a, ticket_ctr, single);
     return hipGetLastError();
 }

@@ -710,7 +710,6 @@ __global__ __launch_bounds__(512) void conv_mfma256_persistent_kernel(const Conv
 #endif
 }
 
-struct HaloTaps { unsigned long long taps[RT_MAX_GROUPS]; };
 bool conv_mfma256_halo_supported(const ConvKArgs& a, int groups, HaloTaps* ht);
 hipError_t launch_conv_mfma256_halo(const ConvKArgs& a, const HaloTaps& ht, int groups, int nbias, int cu_count, unsigned int* tile_ctr, float* stat_out, hipStream_t s);
 // conv_mfma256_lattice.hip: the halo form for dilated 3x3 layers (tiles on the row sub-lattice of the dilation)

@@ -38,10 +38,6 @@
 #define H_STAMP_KT 3                          // (diagnostic build -DC256_STAMPS only; the LDS has 1 KB to spare: K-tiles 4..6)
 #define H_STAMP_N 20
 
-// per group, all taps packed into one 64-bit word (4 bits per tap: dy+1 in bits 0-1, dx+1 in bits 2-3) that lives
-// in SGPRs for the whole tile: an s_load per K-tile would put its latency in front of the operand reads
-struct HaloTaps { unsigned long long taps[RT_MAX_GROUPS]; };
-
 // LDS-DMA as inline asm (m0 = LDS base of the wave's run, one 16-byte piece per active lane).  The compiler
 // must not know these write LDS: its waitcnt pass treats every visible ds_read as possibly aliasing a pending
 // LDS-DMA and puts s_waitcnt vmcnt(0) in front of it, draining the DMA ring in every phase; ordering against

@@ -44,10 +44,11 @@ struct Op {
     OpKind kind;
     std::string name;
     double flops, bytes;
-    ConvKArgs conv; int groups, bn_tile, epi_nchw, out_slot, ksize;
-    int ticket_slot = -1;           // conv64_halo: index of this op's ticket counter (ctx->tile_ctr + 8 + slot)
+    ConvKArgs conv; int groups, bn_tile, epi_nchw, out_slot;
+    int ticket_slot = -1;           // persistent kernels: index of this op's ticket counter (ticket_ctr)
     float* stat_out = nullptr;      // softmax partials written by this conv's epilogue (halo kernel), or null
-    StemKArgs stem; int stem_cout;
+    Tensor input4;                  // OP_INPUT4: the NHWC4 tensor the caller's fp32 batch is converted into
+    bool input4_unread = false;     // OP_INPUT4: its only reader is the fused stem, which reads the fp32 batch itself: no launch
     PoolKArgs pool;
     SoftmaxKArgs sm;
     HeadOutArgs ho;
@@ -72,8 +73,8 @@ struct rtm3d_ctx {
     float* stat_buf = nullptr;
     int stat_chunks = 0, stat_B = 0;
     int stat_tensor[3] = {-1, -1, -1};
-    unsigned int* tile_ctr = nullptr;   // [0,8): per-XCD ticket counters of the persistent conv256 kernels (self-resetting);
-                                        // [8, 8+TICKET_SLOTS): one counter per conv64_halo op; all zeroed at the head of every forward
+    unsigned int* tile_ctr = nullptr;   // [0,8): per-XCD ticket counters of the persistent conv256 kernels (self-resetting), then
+                                        // ticket_ctr() and split_ctrs(); all zeroed at the head of every forward
     int ticket_slots_used = 0;
     float* slab = nullptr;             // split-K partial sums (shared by all split ops of the plan: they run one after the other)
     size_t slab_floats = 0;
@@ -113,6 +114,21 @@ static int ensure_tile_ctr(rtm3d_ctx* ctx) {
     ctx->extra.push_back(ctx->tile_ctr);
     return 0;
 }
+// the ticket counter of a persistent op (one of TICKET_SLOTS behind the conv256 kernels' 8)
+static unsigned int* ticket_ctr(rtm3d_ctx* ctx, const Op& op) { return ctx->tile_ctr + 8 + op.ticket_slot; }
+// the split-K arrival counters (SPLIT_CTRS, behind the ticket counters)
+static unsigned int* split_ctrs(rtm3d_ctx* ctx) { return ctx->tile_ctr + 8 + TICKET_SLOTS; }
+
+// gives `op` a ticket counter of its own (`what`: the recorder, for the message)
+static int claim_ticket(rtm3d_ctx* ctx, Op& op, const char* what) {
+    if (ctx->ticket_slots_used >= TICKET_SLOTS) RT_FAIL("%s: out of ticket counters", what);
+    if (ensure_tile_ctr(ctx)) return 1;
+    op.ticket_slot = ctx->ticket_slots_used++;
+    return 0;
+}
+
+// n channels at channel offset coff of a C-channel tensor: inside it, starting on an 8-channel (16-byte) boundary
+static bool slice_ok(int coff, int n, int C) { return coff >= 0 && coff + n <= C && coff % 8 == 0; }
 
 extern "C" const char* rtm3d_last_error(void) { return g_err; }
 extern "C" int rtm3d_abi_version(void) { return RTM3D_ABI_VERSION; }
@@ -241,6 +257,137 @@ static void* get_blob(rtm3d_ctx* ctx, int id, size_t* bytes) {
     return ctx->blobs[id];
 }
 
+// Admission of one rtm3d_op_conv launch per kernel id: the checks of what that kernel takes, its tile counts, weight / bias
+// offsets, ticket claim and op name.  rtm3d_op_conv has filled the kernel-independent part of op.conv.
+static int admit_mfma128(rtm3d_ctx* ctx, const rtm3d_conv_desc* d, size_t wbytes, size_t bbytes, Op& op) {
+    ConvKArgs& a = op.conv;
+    const int BN = d->bn_tile;
+    if (BN != 16 && BN != 32 && BN != 64 && BN != 128) RT_FAIL("op_conv: bn_tile must be 16/32/64/128");
+    if (d->cin % 64) RT_FAIL("op_conv(mfma): cin=%d is not a multiple of 64", d->cin);
+    if (!d->out_nchw_f32 && (d->cout % BN)) RT_FAIL("op_conv(mfma): cout=%d is not a multiple of the tile %d", d->cout, BN);
+    const int cout_pad = (d->cout + BN - 1) / BN * BN;
+    a.cpt = d->cin / 64; a.ksteps = d->ntaps * a.cpt;
+    a.MT = (a.M + 127) / 128; a.NT = cout_pad / BN;
+    const size_t per_group = (size_t)cout_pad * a.ksteps * 64;
+    if (wbytes != per_group * d->groups * sizeof(f16)) RT_FAIL("op_conv(mfma): packed weight blob has %zu bytes, expected %zu", wbytes, per_group * d->groups * sizeof(f16));
+    if (bbytes != (size_t)cout_pad * d->groups * sizeof(float)) RT_FAIL("op_conv(mfma): bias blob has %zu bytes, expected %zu", bbytes, (size_t)cout_pad * d->groups * sizeof(float));
+    for (int g = 0; g < d->groups; ++g) { a.g[g].w_off = (uint32_t)(per_group * g); a.g[g].bias_off = cout_pad * g; }
+    op.kind = OP_CONV_MFMA; op.bn_tile = BN;
+    op.name = d->ntaps == 1 ? "conv1x1_mfma" : (d->ntaps == 4 ? "deconv4x4_phase_mfma" : "conv3x3_mfma");
+    // Small launches (no more workgroups than CUs: small batches; bs=1 gives DLA level5 four pixel tiles) run on
+    // conv_mfma_deep_kernel: a 4-slot LDS ring instead of one stage in flight.  When the launch would fill fewer than
+    // half the CUs and has a K loop of >= 8 steps, K is also cut into ranges of >= 4 steps so that the grid about fills
+    // the chip (filling it twice measured slower); the partial tiles go through an fp32 slab and the last workgroup of
+    // a tile to arrive sums them in split order (deterministic).
+    if (d->out_nchw_f32 || (BN != 64 && BN != 128)) return 0;
+    const long long wgs = (long long)a.MT * a.NT * d->groups;
+    if (wgs > ctx->n_cus) return 0;
+    a.deep = 1;
+    op.name += "_deep";
+    if (ensure_tile_ctr(ctx)) return 1;
+    if (wgs * 2 > ctx->n_cus || wgs > SPLIT_CTRS || a.ksteps < 8) return 0;
+    int ks = (int)(ctx->n_cus / wgs);
+    if (ks > a.ksteps / 4) ks = a.ksteps / 4;
+    if (ks > 16) ks = 16;
+    if (ks < 2) return 0;
+    const size_t need = (size_t)ks * wgs * 128 * BN;
+    if (need > ctx->slab_floats) {
+        // (re)allocate; earlier ops keep a stale pointer, so patch every split op recorded so far
+        float* nslab = nullptr;
+        RT_HIP(hipMalloc((void**)&nslab, need * sizeof(float)));
+        ctx->extra.push_back(nslab);
+        for (auto& prev : ctx->ops) if (prev.kind == OP_CONV_MFMA && prev.conv.ksplit > 1) prev.conv.slab = nslab;
+        ctx->slab = nslab; ctx->slab_floats = need;
+    }
+    a.ksplit = ks; a.slab = ctx->slab;
+    op.name += "_splitk";
+    return 0;
+}
+
+static int admit_mfma256(rtm3d_ctx* ctx, const rtm3d_conv_desc* d, size_t wbytes, size_t bbytes, Op& op) {
+    ConvKArgs& a = op.conv;
+    if (d->cin % 64 || d->cout % 256 || d->out_nchw_f32) RT_FAIL("op_conv(mfma256): needs cin %% 64 == 0, cout %% 256 == 0, NHWC output (cin=%d cout=%d)", d->cin, d->cout);
+    a.cpt = d->cin / 64; a.ksteps = d->ntaps * a.cpt;
+    a.MT = (a.M + 255) / 256; a.NT = d->cout / 256;
+    const size_t per_group = (size_t)d->cout * a.ksteps * 64;
+    if (wbytes != per_group * d->groups * sizeof(f16)) RT_FAIL("op_conv(mfma256): packed weight blob has %zu bytes, expected %zu", wbytes, per_group * d->groups * sizeof(f16));
+    if (bbytes != (size_t)d->cout * d->groups * sizeof(float)) RT_FAIL("op_conv(mfma256): bias blob size mismatch");
+    for (int g = 0; g < d->groups; ++g) { a.g[g].w_off = (uint32_t)(per_group * g); a.g[g].bias_off = d->cout * g; }
+    op.kind = OP_CONV_MFMA256; op.bn_tile = 256;
+    if (ensure_tile_ctr(ctx)) return 1;
+    op.name = d->ntaps == 1 ? "conv1x1_mfma256" : (d->ntaps == 4 ? "deconv4x4_phase_mfma256" : (conv_mfma256_uses_lattice(a, d->groups) ? "conv3x3_mfma256_lattice" : "conv3x3_mfma256"));
+    return 0;
+}
+
+static int admit_smallc(rtm3d_ctx*, const rtm3d_conv_desc* d, size_t wbytes, size_t bbytes, Op& op) {
+    ConvKArgs& a = op.conv;
+    if (d->groups != 1 || d->out_nchw_f32 || a.res) RT_FAIL("op_conv(smallc): groups/NCHW output/residual unsupported");
+    if (!conv_smallc_supported(d->cin, d->cout, d->ntaps)) RT_FAIL("op_conv(smallc): no kernel for cin=%d cout=%d ntaps=%d", d->cin, d->cout, d->ntaps);
+    int S = d->cin == 16 ? 5 : (d->cin == 32 ? d->ntaps : 7);
+    // cin=16 also comes packed by filter rows (6 k-steps: taps (ky,0),(ky,1) | (ky,2),zero) for the
+    // vertical-walk kernel of stride-1 layers; the blob size tells the two layouts apart
+    if (d->cin == 16 && d->cout == 16 && d->in_stride == 1 && d->out_scale == 1 && wbytes == (size_t)(d->cout / 16) * 6 * 64 * 8 * sizeof(f16)) S = 6;
+    if (wbytes != (size_t)(d->cout / 16) * S * 64 * 8 * sizeof(f16)) RT_FAIL("op_conv(smallc): weight blob size mismatch");
+    a.ksteps = S;
+    if (bbytes != (size_t)d->cout * sizeof(float)) RT_FAIL("op_conv(smallc): bias blob size mismatch");
+    if (d->cin == 4 && a.in_P < 4) RT_FAIL("op_conv(smallc): the NHWC4 stem input needs a border of 4");
+    a.g[0].w_off = 0; a.g[0].bias_off = 0;
+    op.kind = OP_CONV_SMALLC;
+    op.name = d->cin == 4 ? "stem7x7_regmfma" : "conv_smallc_regmfma";
+    return 0;
+}
+
+// 64 -> 64 channel 3x3 halo kernel with the filter bank in registers (conv64_halo.hip)
+static int admit_c64_halo(rtm3d_ctx* ctx, const rtm3d_conv_desc* d, size_t wbytes, size_t bbytes, Op& op) {
+    ConvKArgs& a = op.conv;
+    if (d->out_nchw_f32) RT_FAIL("op_conv(conv64): NCHW output unsupported");
+    if (!a.out) RT_FAIL("op_conv: writing ONLY the space-to-depth copy needs kernel 0");
+    a.cpt = 1; a.ksteps = 9; a.MT = 0; a.NT = 1;
+    if (!conv64_halo_supported(a, d->groups)) RT_FAIL("op_conv(conv64): needs one 64->64 3x3 stride-1 conv on a map with W %% 32 == 0, H %% 8 == 0");
+    if (wbytes != (size_t)9 * 64 * 64 * sizeof(f16) || bbytes != 64 * sizeof(float)) RT_FAIL("op_conv(conv64): weight/bias blob size mismatch");
+    if (claim_ticket(ctx, op, "op_conv(conv64)")) return 1;
+    a.g[0].w_off = 0; a.g[0].bias_off = 0;
+    op.kind = OP_CONV64_HALO; op.bn_tile = 64;
+    op.name = "conv3x3_c64_halo";
+    return 0;
+}
+
+// 3x3 halo kernel for multiples of 128 channels, weights streamed through an LDS ring (conv128_halo.hip); the weight blob is
+// the 128-pixel kernel's packing for 128-channel tiles
+static int admit_c128_halo(rtm3d_ctx* ctx, const rtm3d_conv_desc* d, size_t wbytes, size_t bbytes, Op& op) {
+    ConvKArgs& a = op.conv;
+    if (d->out_nchw_f32) RT_FAIL("op_conv(conv128): NCHW output unsupported");
+    a.cpt = d->cin / 64; a.ksteps = 9 * a.cpt; a.MT = 0; a.NT = 1;
+    if (!conv128_halo_supported(a, d->groups)) RT_FAIL("op_conv(conv128): needs one 3x3 stride-1 conv with cin, cout %% 128 == 0 on a map with W %% 32 == 0, H %% 8 == 0");
+    if (d->bn_tile != 128 || wbytes != (size_t)9 * d->cin * d->cout * sizeof(f16) || bbytes != (size_t)d->cout * sizeof(float))
+        RT_FAIL("op_conv(conv128): weight/bias blob size mismatch (expects the bn_tile = 128 packing)");
+    if (claim_ticket(ctx, op, "op_conv(conv128)")) return 1;
+    a.g[0].w_off = 0; a.g[0].bias_off = 0;
+    op.kind = OP_CONV128_HALO; op.bn_tile = 128;
+    op.name = "conv3x3_c128_halo";
+    return 0;
+}
+
+// 64 -> 128 channel 3x3 STRIDE-2 halo kernel with the filter bank in registers (conv64s2_halo.hip); the one kernel that reads a
+// space-to-depth input
+static int admit_c64s2_halo(rtm3d_ctx* ctx, const rtm3d_conv_desc* d, size_t wbytes, size_t bbytes, Op& op) {
+    ConvKArgs& a = op.conv;
+    if (d->in_s2d) {
+        if (d->groups != 1) RT_FAIL("op_conv: a space-to-depth INPUT is read by kernel 7 only");
+        if (!slice_ok(d->in_coff[0], 4 * d->cin, a.in_C) || a.in_P < 1) RT_FAIL("op_conv: the space-to-depth input needs 4 x cin channels behind in_coff and a border >= 1");
+    }
+    if (d->out_nchw_f32 || a.res) RT_FAIL("op_conv(conv64s2): NCHW output / residual unsupported");
+    a.cpt = 1; a.ksteps = 9; a.MT = 0; a.NT = 1;
+    a.in_s2d = d->in_s2d ? 1 : 0;
+    if (!conv64s2_halo_supported(a, d->groups)) RT_FAIL("op_conv(conv64s2): needs one 64->128 3x3 stride-2 conv onto a map with W %% 32 == 0, H %% 4 == 0 (input border >= 1)");
+    if (wbytes != (size_t)9 * 64 * 128 * sizeof(f16) || bbytes != 128 * sizeof(float)) RT_FAIL("op_conv(conv64s2): weight/bias blob size mismatch");
+    if (claim_ticket(ctx, op, "op_conv(conv64s2)")) return 1;
+    a.g[0].w_off = 0; a.g[0].bias_off = 0;
+    op.kind = OP_CONV64S2_HALO; op.bn_tile = 128;
+    op.name = "conv3x3s2_c64_halo";
+    return 0;
+}
+
 extern "C" int rtm3d_op_conv(rtm3d_ctx* ctx, const rtm3d_conv_desc* d) {
     if (!ctx || !d) RT_FAIL("op_conv: null argument");
     Tensor* in = get_tensor(ctx, d->in_tensor);
@@ -272,6 +419,7 @@ extern "C" int rtm3d_op_conv(rtm3d_ctx* ctx, const rtm3d_conv_desc* d) {
     else { a.out_C = d->cout * d->groups; a.out_H = d->out_H; a.out_W = d->out_W; }
     if (res) { a.res_Hp = res->Hp; a.res_Wp = res->Wp; a.res_C = res->C; a.res_P = res->P; }
     a.cin = d->cin; a.cout = d->cout; a.ntaps = d->ntaps; a.relu = d->relu;
+    const int k = d->kernel;
     // bounds: every tap of every iteration pixel must stay inside the padded input
     for (int g = 0; g < d->groups; ++g) {
         for (int t = 0; t < d->ntaps; ++t) {
@@ -283,21 +431,21 @@ extern "C" int rtm3d_op_conv(rtm3d_ctx* ctx, const rtm3d_conv_desc* d) {
             if (ylo < -Pin || xlo < -Pin || yhi >= Hin + Pin || xhi >= Win + Pin)
                 RT_FAIL("op_conv: tap (%d,%d) leaves the padded input (H=%d W=%d pad=%d, Hm=%d Wm=%d stride=%d)", dy, dx, in->H, in->W, in->P, d->Hm, d->Wm, d->in_stride);
             const int dc = d->tap_dc[g][t];
-            if (dc && d->kernel != 0 && d->kernel != 2) RT_FAIL("op_conv: per-tap channel offsets need kernel 0 or 2");
-            if ((dc % 8) || d->in_coff[g] + dc < 0 || d->in_coff[g] + dc + d->cin > in->C) RT_FAIL("op_conv: tap %d names channels [%d, %d) outside the %d-channel input tensor", t, d->in_coff[g] + dc, d->in_coff[g] + dc + d->cin, in->C);
+            if (dc && k != RTM3D_CONV_MFMA128 && k != RTM3D_CONV_MFMA256) RT_FAIL("op_conv: per-tap channel offsets need kernel 0 or 2");
+            if (!slice_ok(d->in_coff[g] + dc, d->cin, in->C)) RT_FAIL("op_conv: tap %d names channels [%d, %d) outside the %d-channel input tensor", t, d->in_coff[g] + dc, d->in_coff[g] + dc + d->cin, in->C);
             a.g[g].tap_off[t] = (dy * in->Wp + dx) * in->C + dc;
         }
-        if (d->in_coff[g] < 0 || d->in_coff[g] + d->cin > in->C || (d->in_coff[g] % 8)) RT_FAIL("op_conv: input channel slice out of range");
+        if (!slice_ok(d->in_coff[g], d->cin, in->C)) RT_FAIL("op_conv: input channel slice out of range");
         const int oyhi = (d->Hm - 1) * d->out_scale + d->out_oy[g], oxhi = (d->Wm - 1) * d->out_scale + d->out_ox[g];
         if (out) {
-            if (d->out_coff[g] < 0 || d->out_coff[g] + d->cout > out->C || (d->out_coff[g] % 8)) RT_FAIL("op_conv: output channel slice out of range");
+            if (!slice_ok(d->out_coff[g], d->cout, out->C)) RT_FAIL("op_conv: output channel slice out of range");
             if (oyhi >= out->H || oxhi >= out->W || d->out_oy[g] < 0 || d->out_ox[g] < 0) RT_FAIL("op_conv: output pixel out of range");
             if (out->B != in->B) RT_FAIL("op_conv: batch mismatch");
         } else if (!s2d_only) {
             if (oyhi >= d->out_H || oxhi >= d->out_W) RT_FAIL("op_conv: NCHW output pixel out of range");
         }
         if (res) {
-            if (d->res_coff[g] < 0 || d->res_coff[g] + d->cout > res->C || (d->res_coff[g] % 8)) RT_FAIL("op_conv: residual channel slice out of range");
+            if (!slice_ok(d->res_coff[g], d->cout, res->C)) RT_FAIL("op_conv: residual channel slice out of range");
             if (oyhi >= res->H || oxhi >= res->W) RT_FAIL("op_conv: residual pixel out of range");
             // a residual must not alias the output ("in place"): partial pixel tiles are padded with copies of their last pixel,
             // and a copy that loads the residual after another copy has stored would add it twice
@@ -310,137 +458,34 @@ extern "C" int rtm3d_op_conv(rtm3d_ctx* ctx, const rtm3d_conv_desc* d) {
     if (s2d_id >= 0) {
         Tensor* s2 = get_tensor(ctx, s2d_id);
         if (!s2 || (!out && !s2d_only)) RT_FAIL("op_conv: bad space-to-depth tensor %d", s2d_id);
-        if (s2d_only && d->kernel != 0) RT_FAIL("op_conv: writing ONLY the space-to-depth copy needs kernel 0");
-        if ((d->kernel != 0 && d->kernel != 5) || d->groups != 1 || d->out_scale != 1 || d->out_oy[0] || d->out_ox[0] || (d->Hm & 1) || (d->Wm & 1) || (d->cout % 8))
+        if ((k != RTM3D_CONV_MFMA128 && k != RTM3D_CONV_C64_HALO) || d->groups != 1 || d->out_scale != 1 || d->out_oy[0] || d->out_ox[0] || (d->Hm & 1) || (d->Wm & 1) || (d->cout % 8))
             RT_FAIL("op_conv: the space-to-depth copy needs kernel 0 or 5, one group, out_scale 1 and an even output height / width");
-        if (s2->B != in->B || s2->H * 2 != d->Hm || s2->W * 2 != d->Wm || d->s2d_coff < 0 || d->s2d_coff + 4 * d->cout > s2->C || (d->s2d_coff % 8))
+        if (s2->B != in->B || s2->H * 2 != d->Hm || s2->W * 2 != d->Wm || !slice_ok(d->s2d_coff, 4 * d->cout, s2->C))
             RT_FAIL("op_conv: space-to-depth slice mismatch (half resolution, 4 x cout channels)");
         if (s2 == out || s2 == in || s2 == res) RT_FAIL("op_conv: the space-to-depth copy aliases an operand");
         a.s2d = s2->base; a.s_Hp = s2->Hp; a.s_Wp = s2->Wp; a.s_C = s2->C; a.s_P = s2->P; a.s_coff = d->s2d_coff;
     }
-    if (d->in_s2d) {
-        if (d->kernel != 7 || d->groups != 1) RT_FAIL("op_conv: a space-to-depth INPUT is read by kernel 7 only");
-        if (d->in_coff[0] + 4 * d->cin > in->C || in->P < 1) RT_FAIL("op_conv: the space-to-depth input needs 4 x cin channels behind in_coff and a border >= 1");
-    }
+    if (d->in_s2d && k != RTM3D_CONV_C64S2_HALO) RT_FAIL("op_conv: a space-to-depth INPUT is read by kernel 7 only");
     op.groups = d->groups; op.epi_nchw = d->out_nchw_f32 ? 1 : 0; op.out_slot = d->out_nchw_f32 - 1;
-    int stat_slot = -1;
     const double M = (double)a.M;
     op.flops = 2.0 * M * d->groups * (double)d->cin * d->ntaps * d->cout;
     op.bytes = 2.0 * M * d->groups * (d->cin + d->cout * (d->out_nchw_f32 ? 2 : 1)) + (res ? 2.0 * M * d->groups * d->cout : 0.0)
                + (s2d_id >= 0 && !s2d_only ? 2.0 * M * d->cout : 0.0);
-    if (d->kernel == 2) {
-        if (d->cin % 64 || d->cout % 256 || d->out_nchw_f32) RT_FAIL("op_conv(mfma256): needs cin %% 64 == 0, cout %% 256 == 0, NHWC output (cin=%d cout=%d)", d->cin, d->cout);
-        a.cpt = d->cin / 64; a.ksteps = d->ntaps * a.cpt;
-        a.MT = (a.M + 255) / 256; a.NT = d->cout / 256;
-        const size_t per_group = (size_t)d->cout * a.ksteps * 64;
-        if (wbytes != per_group * d->groups * sizeof(f16)) RT_FAIL("op_conv(mfma256): packed weight blob has %zu bytes, expected %zu", wbytes, per_group * d->groups * sizeof(f16));
-        if (bbytes != (size_t)d->cout * d->groups * sizeof(float)) RT_FAIL("op_conv(mfma256): bias blob size mismatch");
-        for (int g = 0; g < d->groups; ++g) { a.g[g].w_off = (uint32_t)(per_group * g); a.g[g].bias_off = d->cout * g; }
-        op.kind = OP_CONV_MFMA256; op.bn_tile = 256;
-        stat_slot = d->softmax_stat_slot;
-        if (ensure_tile_ctr(ctx)) return 1;
-        op.name = d->ntaps == 1 ? "conv1x1_mfma256" : (d->ntaps == 4 ? "deconv4x4_phase_mfma256" : (conv_mfma256_uses_lattice(a, d->groups) ? "conv3x3_mfma256_lattice" : "conv3x3_mfma256"));
-    } else if (d->kernel == 5) {
-        // 64 -> 64 channel 3x3 halo kernel with the filter bank in registers (conv64_halo.hip)
-        if (d->out_nchw_f32) RT_FAIL("op_conv(conv64): NCHW output unsupported");
-        a.cpt = 1; a.ksteps = 9; a.MT = 0; a.NT = 1;
-        if (!conv64_halo_supported(a, d->groups)) RT_FAIL("op_conv(conv64): needs one 64->64 3x3 stride-1 conv on a map with W %% 32 == 0, H %% 8 == 0");
-        if (wbytes != (size_t)9 * 64 * 64 * sizeof(f16) || bbytes != 64 * sizeof(float)) RT_FAIL("op_conv(conv64): weight/bias blob size mismatch");
-        if (ctx->ticket_slots_used >= TICKET_SLOTS) RT_FAIL("op_conv(conv64): out of ticket counters");
-        if (ensure_tile_ctr(ctx)) return 1;
-        a.g[0].w_off = 0; a.g[0].bias_off = 0;
-        op.kind = OP_CONV64_HALO; op.bn_tile = 64; op.ticket_slot = ctx->ticket_slots_used++;
-        op.name = "conv3x3_c64_halo";
-    } else if (d->kernel == 7) {
-        // 64 -> 128 channel 3x3 STRIDE-2 halo kernel with the filter bank in registers (conv64s2_halo.hip)
-        if (d->out_nchw_f32 || res) RT_FAIL("op_conv(conv64s2): NCHW output / residual unsupported");
-        a.cpt = 1; a.ksteps = 9; a.MT = 0; a.NT = 1;
-        a.in_s2d = d->in_s2d ? 1 : 0;
-        if (!conv64s2_halo_supported(a, d->groups)) RT_FAIL("op_conv(conv64s2): needs one 64->128 3x3 stride-2 conv onto a map with W %% 32 == 0, H %% 4 == 0 (input border >= 1)");
-        if (wbytes != (size_t)9 * 64 * 128 * sizeof(f16) || bbytes != 128 * sizeof(float)) RT_FAIL("op_conv(conv64s2): weight/bias blob size mismatch");
-        if (ctx->ticket_slots_used >= TICKET_SLOTS) RT_FAIL("op_conv(conv64s2): out of ticket counters");
-        if (ensure_tile_ctr(ctx)) return 1;
-        a.g[0].w_off = 0; a.g[0].bias_off = 0;
-        op.kind = OP_CONV64S2_HALO; op.bn_tile = 128; op.ticket_slot = ctx->ticket_slots_used++;
-        op.name = "conv3x3s2_c64_halo";
-    } else if (d->kernel == 6) {
-        // 3x3 halo kernel for multiples of 128 channels, weights streamed through an LDS ring (conv128_halo.hip); the weight
-        // blob is the generic kernel's packing for 128-channel tiles
-        if (d->out_nchw_f32) RT_FAIL("op_conv(conv128): NCHW output unsupported");
-        a.cpt = d->cin / 64; a.ksteps = 9 * a.cpt; a.MT = 0; a.NT = 1;
-        if (!conv128_halo_supported(a, d->groups)) RT_FAIL("op_conv(conv128): needs one 3x3 stride-1 conv with cin, cout %% 128 == 0 on a map with W %% 32 == 0, H %% 8 == 0");
-        if (d->bn_tile != 128 || wbytes != (size_t)9 * d->cin * d->cout * sizeof(f16) || bbytes != (size_t)d->cout * sizeof(float))
-            RT_FAIL("op_conv(conv128): weight/bias blob size mismatch (expects the bn_tile = 128 packing)");
-        if (ctx->ticket_slots_used >= TICKET_SLOTS) RT_FAIL("op_conv(conv128): out of ticket counters");
-        if (ensure_tile_ctr(ctx)) return 1;
-        a.g[0].w_off = 0; a.g[0].bias_off = 0;
-        op.kind = OP_CONV128_HALO; op.bn_tile = 128; op.ticket_slot = ctx->ticket_slots_used++;
-        op.name = "conv3x3_c128_halo";
-    } else if (d->kernel == 0) {
-        const int BN = d->bn_tile;
-        if (BN != 16 && BN != 32 && BN != 64 && BN != 128) RT_FAIL("op_conv: bn_tile must be 16/32/64/128");
-        if (d->cin % 64) RT_FAIL("op_conv(mfma): cin=%d is not a multiple of 64", d->cin);
-        if (!d->out_nchw_f32 && (d->cout % BN)) RT_FAIL("op_conv(mfma): cout=%d is not a multiple of the tile %d", d->cout, BN);
-        const int cout_pad = (d->cout + BN - 1) / BN * BN;
-        a.cpt = d->cin / 64; a.ksteps = d->ntaps * a.cpt;
-        a.MT = (a.M + 127) / 128; a.NT = cout_pad / BN;
-        const size_t per_group = (size_t)cout_pad * a.ksteps * 64;
-        if (wbytes != per_group * d->groups * sizeof(f16)) RT_FAIL("op_conv(mfma): packed weight blob has %zu bytes, expected %zu", wbytes, per_group * d->groups * sizeof(f16));
-        if (bbytes != (size_t)cout_pad * d->groups * sizeof(float)) RT_FAIL("op_conv(mfma): bias blob has %zu bytes, expected %zu", bbytes, (size_t)cout_pad * d->groups * sizeof(float));
-        for (int g = 0; g < d->groups; ++g) { a.g[g].w_off = (uint32_t)(per_group * g); a.g[g].bias_off = cout_pad * g; }
-        op.kind = OP_CONV_MFMA; op.bn_tile = BN;
-        op.name = d->ntaps == 1 ? "conv1x1_mfma" : (d->ntaps == 4 ? "deconv4x4_phase_mfma" : "conv3x3_mfma");
-        // Small launches (no more workgroups than CUs: small batches; bs=1 gives DLA level5 four pixel tiles) run on
-        // conv_mfma_deep_kernel: a 4-slot LDS ring instead of one stage in flight.  When the launch would fill fewer than
-        // half the CUs and has a K loop of >= 8 steps, K is also cut into ranges of >= 4 steps so that the grid about fills
-        // the chip (filling it twice measured slower); the partial tiles go through an fp32 slab and the last workgroup of
-        // a tile to arrive sums them in split order (deterministic).
-        if (!d->out_nchw_f32 && (BN == 64 || BN == 128)) {
-            const long long wgs = (long long)a.MT * a.NT * d->groups;
-            if (wgs <= ctx->n_cus) {
-                a.deep = 1;
-                op.name += "_deep";
-                if (ensure_tile_ctr(ctx)) return 1;
-            }
-            if (a.deep && wgs * 2 <= ctx->n_cus && wgs <= SPLIT_CTRS && a.ksteps >= 8) {
-                int ks = (int)(ctx->n_cus / wgs);
-                if (ks > a.ksteps / 4) ks = a.ksteps / 4;
-                if (ks > 16) ks = 16;
-                if (ks >= 2) {
-                    const size_t need = (size_t)ks * wgs * 128 * BN;
-                    if (need > ctx->slab_floats) {
-                        // (re)allocate; earlier ops keep a stale pointer, so patch every split op recorded so far
-                        float* nslab = nullptr;
-                        RT_HIP(hipMalloc((void**)&nslab, need * sizeof(float)));
-                        ctx->extra.push_back(nslab);
-                        for (auto& prev : ctx->ops) if (prev.kind == OP_CONV_MFMA && prev.conv.ksplit > 1) prev.conv.slab = nslab;
-                        ctx->slab = nslab; ctx->slab_floats = need;
-                    }
-                    a.ksplit = ks; a.slab = ctx->slab;
-                    op.name += "_splitk";
-                }
-            }
-        }
-    } else if (d->kernel == 3) {
-        if (d->groups != 1 || d->out_nchw_f32 || res) RT_FAIL("op_conv(smallc): groups/NCHW output/residual unsupported");
-        if (!conv_smallc_supported(d->cin, d->cout, d->ntaps)) RT_FAIL("op_conv(smallc): no kernel for cin=%d cout=%d ntaps=%d", d->cin, d->cout, d->ntaps);
-        int S = d->cin == 16 ? 5 : (d->cin == 32 ? d->ntaps : 7);
-        // cin=16 also comes packed by filter rows (6 k-steps: taps (ky,0),(ky,1) | (ky,2),zero) for the
-        // vertical-walk kernel of stride-1 layers; the blob size tells the two layouts apart
-        if (d->cin == 16 && d->cout == 16 && d->in_stride == 1 && d->out_scale == 1 && wbytes == (size_t)(d->cout / 16) * 6 * 64 * 8 * sizeof(f16)) S = 6;
-        if (wbytes != (size_t)(d->cout / 16) * S * 64 * 8 * sizeof(f16)) RT_FAIL("op_conv(smallc): weight blob size mismatch");
-        a.ksteps = S;
-        if (bbytes != (size_t)d->cout * sizeof(float)) RT_FAIL("op_conv(smallc): bias blob size mismatch");
-        if (d->cin == 4 && in->P < 4) RT_FAIL("op_conv(smallc): the NHWC4 stem input needs a border of 4");
-        a.g[0].w_off = 0; a.g[0].bias_off = 0;
-        op.kind = OP_CONV_SMALLC;
-        op.name = d->cin == 4 ? "stem7x7_regmfma" : "conv_smallc_regmfma";
-    } else {
-        RT_FAIL("op_conv: unknown kernel %d (0 = MFMA 128-px tile, 2 = MFMA 256x256 tile, 3 = register-direct MFMA, 5 / 6 / 7 = halo kernels)", d->kernel);
+    int rc;
+    switch (k) {
+        case RTM3D_CONV_MFMA128: rc = admit_mfma128(ctx, d, wbytes, bbytes, op); break;
+        case RTM3D_CONV_MFMA256: rc = admit_mfma256(ctx, d, wbytes, bbytes, op); break;
+        case RTM3D_CONV_SMALLC: rc = admit_smallc(ctx, d, wbytes, bbytes, op); break;
+        case RTM3D_CONV_C64_HALO: rc = admit_c64_halo(ctx, d, wbytes, bbytes, op); break;
+        case RTM3D_CONV_C128_HALO: rc = admit_c128_halo(ctx, d, wbytes, bbytes, op); break;
+        case RTM3D_CONV_C64S2_HALO: rc = admit_c64s2_halo(ctx, d, wbytes, bbytes, op); break;
+        default: RT_FAIL("op_conv: unknown kernel %d (0 = MFMA 128-px tile, 2 = MFMA 256x256 tile, 3 = register-direct MFMA, 5 / 6 / 7 = halo kernels)", k);
     }
-    if (d->softmax_stat_slot >= 0 && stat_slot < 0) RT_FAIL("op_conv: softmax_stat_slot needs kernel = 2");
+    if (rc) return rc;
+    const int stat_slot = d->softmax_stat_slot;
     if (stat_slot >= 0) {
         // epilogue-emitted spatial-softmax partials: [slot][image][chunk][256][2] floats, chunk = 128-pixel run
+        if (op.kind != OP_CONV_MFMA256) RT_FAIL("op_conv: softmax_stat_slot needs kernel = 2");
         if (stat_slot > 2) RT_FAIL("op_conv: softmax_stat_slot out of range");
         if (!conv_mfma256_uses_halo(a, d->groups)) RT_FAIL("op_conv: softmax_stat_slot set on a conv that does not take the halo-tile kernel");
         if (d->cout != 256 || out->C != 256) RT_FAIL("op_conv: softmax partials need a 256-channel output tensor");
@@ -534,7 +579,7 @@ extern "C" int rtm3d_op_quant_mx8(rtm3d_ctx* ctx, int in_tensor, int in_coff, in
     MxTensor* o = ctx ? get_mx8(ctx, out_tensor) : nullptr;
     if (!in || !o) RT_FAIL("op_quant_mx8: bad tensors (fp16 input %d, MX8 output %d)", in_tensor, out_tensor);
     if (in->B != o->B || in->H != o->H || in->W != o->W) RT_FAIL("op_quant_mx8: input and output maps differ in shape");
-    if (channels <= 0 || channels % 32 || in_coff < 0 || in_coff % 8 || in->C % 8 || in_coff + channels > in->C)
+    if (channels <= 0 || channels % 32 || in->C % 8 || !slice_ok(in_coff, channels, in->C))
         RT_FAIL("op_quant_mx8: input slice [%d, %d) of a %d-channel tensor (multiples of 32 channels from a multiple of 8)", in_coff, in_coff + channels, in->C);
     if (out_coff < 0 || out_coff % 32 || out_coff + channels > o->C) RT_FAIL("op_quant_mx8: output slice [%d, %d) (32-channel blocks)", out_coff, out_coff + channels);
     Op op;
@@ -617,10 +662,8 @@ extern "C" int rtm3d_op_input_nhwc4(rtm3d_ctx* ctx, int out_tensor) {
     Tensor* o = ctx ? get_tensor(ctx, out_tensor) : nullptr;
     if (!o || o->C != 4) RT_FAIL("op_input_nhwc4: output tensor must have 4 channels");
     Op op;
-    op.kind = OP_INPUT4; op.name = "nchw_f32_to_nhwc4_f16"; op.stem_cout = 0;
-    memset(&op.stem, 0, sizeof(op.stem));
-    op.stem.out = o->base; op.stem.B = o->B; op.stem.H = o->H; op.stem.W = o->W;
-    op.stem.out_Hp = o->Hp; op.stem.out_Wp = o->Wp; op.stem.out_P = o->P;
+    op.kind = OP_INPUT4; op.name = "nchw_f32_to_nhwc4_f16";
+    op.input4 = *o;
     op.flops = 0; op.bytes = (double)o->B * o->H * o->W * (12.0 + 8.0);
     ctx->ops.push_back(op);
     return 0;
@@ -634,7 +677,7 @@ extern "C" int rtm3d_op_stem_fused(rtm3d_ctx* ctx, int x4_tensor, int out_tensor
     const bool three = w_l1_blob >= 0;
     const int oc = three ? 32 : 16, sc = three ? 2 : 1;
     if (x->C != 4 || x->P < 4) RT_FAIL("op_stem_fused: the input must be the NHWC4 image tensor with a border >= 4");
-    if (o->H * sc != x->H || o->W * sc != x->W || o->B != x->B || out_coff < 0 || out_coff + oc > o->C || (out_coff % 8)) RT_FAIL("op_stem_fused: output slice mismatch");
+    if (o->H * sc != x->H || o->W * sc != x->W || o->B != x->B || !slice_ok(out_coff, oc, o->C)) RT_FAIL("op_stem_fused: output slice mismatch");
     if (x->H % 16 || x->W % 32) RT_FAIL("op_stem_fused: needs H %% 16 == 0 and W %% 32 == 0 (got %dx%d)", x->H, x->W);
     // the kernel addresses one image (3 fp32 planes) through a buffer descriptor with 32-bit byte offsets
     if ((long long)x->H * x->W * 3 * 4 >= (1LL << 31)) RT_FAIL("op_stem_fused: image of %dx%d exceeds the 2 GiB the stem addresses per image", x->H, x->W);
@@ -650,7 +693,7 @@ extern "C" int rtm3d_op_stem_fused(rtm3d_ctx* ctx, int x4_tensor, int out_tensor
     if (three && (!w2 || !b2 || w1b != 2 * 5 * 64 * 8 * sizeof(f16) || b1b != 32 * sizeof(float))) RT_FAIL("op_stem_fused: level1 weight/bias blob size mismatch");
     // the conversion pass in front of this op becomes unnecessary: the kernel reads the caller's fp32 batch directly
     for (auto& prev : ctx->ops)
-        if (prev.kind == OP_INPUT4 && prev.stem.out == x->base) prev.stem_cout = -1;
+        if (prev.kind == OP_INPUT4 && prev.input4.base == x->base) prev.input4_unread = true;
     Op op;
     op.kind = OP_STEM_FUSED; op.name = three ? "stem7x7+3x3+3x3s2_fused" : "stem7x7+conv3x3_fused";
     StemFusedArgs& a = op.sf;
@@ -674,11 +717,11 @@ extern "C" int rtm3d_op_conv32s2_fused(rtm3d_ctx* ctx, int in_tensor, int in_cof
     Tensor* oc = ctx ? get_tensor(ctx, conv_tensor) : nullptr;
     Tensor* op_ = ctx ? get_tensor(ctx, proj_tensor) : nullptr;
     if (!x || !oc || !op_) RT_FAIL("op_conv32s2_fused: bad tensors");
-    if (x->P < 1 || in_coff < 0 || in_coff + 32 > x->C || (in_coff % 8)) RT_FAIL("op_conv32s2_fused: input slice mismatch (32 channels, border >= 1)");
+    if (x->P < 1 || !slice_ok(in_coff, 32, x->C)) RT_FAIL("op_conv32s2_fused: input slice mismatch (32 channels, border >= 1)");
     if (x->H % 16 || x->W % 64) RT_FAIL("op_conv32s2_fused: needs H %% 16 == 0 and W %% 64 == 0 (got %dx%d)", x->H, x->W);
     for (Tensor* o : {oc, op_})
         if (o->H * 2 != x->H || o->W * 2 != x->W || o->B != x->B) RT_FAIL("op_conv32s2_fused: outputs must have half the input resolution");
-    if (conv_coff < 0 || conv_coff + 64 > oc->C || (conv_coff % 8) || proj_coff < 0 || proj_coff + 64 > op_->C || (proj_coff % 8)) RT_FAIL("op_conv32s2_fused: output slice mismatch");
+    if (!slice_ok(conv_coff, 64, oc->C) || !slice_ok(proj_coff, 64, op_->C)) RT_FAIL("op_conv32s2_fused: output slice mismatch");
     size_t wc = 0, bc = 0, wp = 0, bp = 0;
     const f16* w0 = (const f16*)get_blob(ctx, w_conv_blob, &wc);
     const float* b0 = (const float*)get_blob(ctx, b_conv_blob, &bc);
@@ -686,10 +729,9 @@ extern "C" int rtm3d_op_conv32s2_fused(rtm3d_ctx* ctx, int in_tensor, int in_cof
     const float* b1 = (const float*)get_blob(ctx, b_proj_blob, &bp);
     if (!w0 || !b0 || !w1 || !b1 || wc != 9 * 4 * 64 * 8 * sizeof(f16) || wp != 4 * 64 * 8 * sizeof(f16) || bc != 64 * sizeof(float) || bp != 64 * sizeof(float))
         RT_FAIL("op_conv32s2_fused: weight/bias blob size mismatch");
-    if (ctx->ticket_slots_used >= TICKET_SLOTS) RT_FAIL("op_conv32s2_fused: out of ticket counters");
-    if (ensure_tile_ctr(ctx)) return 1;
     Op op;
-    op.kind = OP_CONV32S2_FUSED; op.name = "pool+proj1x1+conv3x3s2_fused"; op.ticket_slot = ctx->ticket_slots_used++;
+    if (claim_ticket(ctx, op, "op_conv32s2_fused")) return 1;
+    op.kind = OP_CONV32S2_FUSED; op.name = "pool+proj1x1+conv3x3s2_fused";
     Conv32S2Args& a = op.c32;
     memset(&a, 0, sizeof(a));
     a.in = x->base; a.out_conv = oc->base; a.out_proj = op_->base; a.w_conv = w0; a.w_proj = w1; a.b_conv = b0; a.b_proj = b1;
@@ -716,19 +758,19 @@ extern "C" int rtm3d_op_conv64_root(rtm3d_ctx* ctx, int in_tensor, int in_coff, 
     if (!in || !res || (out_tensor >= 0 && !out) || (pool_tensor >= 0 && !pool) || (s2d_tensor >= 0 && !s2d)) RT_FAIL("op_conv64_root: bad tensors");
     if (!out && !s2d) RT_FAIL("op_conv64_root: out_tensor < 0 (no ordinary copy of the root output) needs a space-to-depth copy");
     if (s2d) {
-        if (s2d->H * 2 != in->H || s2d->W * 2 != in->W || s2d->B != in->B || s2d_coff < 0 || s2d_coff + 256 > s2d->C || (s2d_coff % 8))
+        if (s2d->H * 2 != in->H || s2d->W * 2 != in->W || s2d->B != in->B || !slice_ok(s2d_coff, 256, s2d->C))
             RT_FAIL("op_conv64_root: space-to-depth output slice mismatch (half resolution, 4 x 64 channels)");
         if (s2d == out || s2d == res || s2d == in) RT_FAIL("op_conv64_root: the space-to-depth copy aliases an operand");
     }
-    if (in->P < 1 || in_coff < 0 || in_coff + 64 > in->C || (in_coff % 8)) RT_FAIL("op_conv64_root: input slice mismatch (64 channels, border >= 1)");
+    if (in->P < 1 || !slice_ok(in_coff, 64, in->C)) RT_FAIL("op_conv64_root: input slice mismatch (64 channels, border >= 1)");
     if (in->H % 8 || in->W % 32) RT_FAIL("op_conv64_root: needs H %% 8 == 0 and W %% 32 == 0 (got %dx%d)", in->H, in->W);
     for (Tensor* t : {res, out})
         if (t && (t->H != in->H || t->W != in->W || t->B != in->B)) RT_FAIL("op_conv64_root: residual / output shape mismatch");
-    if (res_coff < 0 || res_coff + 64 > res->C || (res_coff % 8) || (out && (out_coff < 0 || out_coff + 64 > out->C || (out_coff % 8)))) RT_FAIL("op_conv64_root: residual / output slice mismatch");
+    if (!slice_ok(res_coff, 64, res->C) || (out && !slice_ok(out_coff, 64, out->C))) RT_FAIL("op_conv64_root: residual / output slice mismatch");
     if (out && res == out && res_coff < out_coff + 64 && out_coff < res_coff + 64) RT_FAIL("op_conv64_root: the root output overlaps x1 (another workgroup may still read it)");
     if (out && in == out && in_coff < out_coff + 64 && out_coff < in_coff + 64) RT_FAIL("op_conv64_root: the root output overlaps the conv input");
     if (pool) {
-        if (pool->H * 2 != in->H || pool->W * 2 != in->W || pool->B != in->B || pool_coff < 0 || pool_coff + 64 > pool->C || (pool_coff % 8))
+        if (pool->H * 2 != in->H || pool->W * 2 != in->W || pool->B != in->B || !slice_ok(pool_coff, 64, pool->C))
             RT_FAIL("op_conv64_root: pooled output slice mismatch (half resolution, 64 channels)");
         // the pooled map and the space-to-depth copy are both half resolution and may be slices of ONE tensor: different lanes of
         // one launch write them, so their channel ranges must not meet
@@ -743,9 +785,8 @@ extern "C" int rtm3d_op_conv64_root(rtm3d_ctx* ctx, int in_tensor, int in_coff, 
     const float* b1 = (const float*)get_blob(ctx, b_root_blob, &br);
     if (!w0 || !b0 || !w1 || !b1 || wc != (size_t)9 * 64 * 64 * sizeof(f16) || bc != 64 * sizeof(float) || wr != (size_t)64 * 128 * sizeof(f16) || br != 64 * sizeof(float))
         RT_FAIL("op_conv64_root: weight/bias blob size mismatch");
-    if (ctx->ticket_slots_used >= TICKET_SLOTS) RT_FAIL("op_conv64_root: out of ticket counters");
-    if (ensure_tile_ctr(ctx)) return 1;
     Op op;
+    if (claim_ticket(ctx, op, "op_conv64_root")) return 1;
     ConvKArgs& a = op.conv;
     memset(&a, 0, sizeof(a));
     a.in = in->base; a.wgt = w0; a.bias = b0; a.res = res->base; a.out = nullptr;
@@ -762,7 +803,7 @@ extern "C" int rtm3d_op_conv64_root(rtm3d_ctx* ctx, int in_tensor, int in_coff, 
     r.relu = root_relu ? 1 : 0;
     if (pool) { r.pool = pool->base; r.p_Hp = pool->Hp; r.p_Wp = pool->Wp; r.p_C = pool->C; r.p_P = pool->P; r.p_coff = pool_coff; }
     if (s2d) { r.s2d = s2d->base; r.s_Hp = s2d->Hp; r.s_Wp = s2d->Wp; r.s_C = s2d->C; r.s_P = s2d->P; r.s_coff = s2d_coff; }
-    op.kind = OP_CONV64_ROOT; op.groups = 1; op.bn_tile = 64; op.epi_nchw = 0; op.out_slot = -1; op.ticket_slot = ctx->ticket_slots_used++;
+    op.kind = OP_CONV64_ROOT; op.groups = 1; op.bn_tile = 64; op.epi_nchw = 0; op.out_slot = -1;
     op.name = pool ? "conv3x3_c64+root1x1+pool_fused" : "conv3x3_c64+root1x1_fused";
     if (s2d) op.name += "+s2d";
     const double M = (double)a.M;
@@ -841,7 +882,7 @@ extern "C" int rtm3d_op_maxpool_s2d(rtm3d_ctx* ctx, int in_tensor, int in_coff, 
     Tensor* in = ctx ? get_tensor(ctx, in_tensor) : nullptr;
     Tensor* out = ctx ? get_tensor(ctx, out_tensor) : nullptr;
     if (!in || !out) RT_FAIL("op_maxpool_s2d: bad tensors");
-    if (channels % 8 || in_coff % 8 || out_coff % 8 || in_coff < 0 || out_coff < 0 || in_coff + 4 * channels > in->C || out_coff + channels > out->C) RT_FAIL("op_maxpool_s2d: bad channel slices (input: 4 x channels)");
+    if (channels % 8 || !slice_ok(in_coff, 4 * channels, in->C) || !slice_ok(out_coff, channels, out->C)) RT_FAIL("op_maxpool_s2d: bad channel slices (input: 4 x channels)");
     if (in->H != out->H || in->W != out->W || in->B != out->B) RT_FAIL("op_maxpool_s2d: the space-to-depth copy and the pooled map have one resolution");
     if (in == out && in_coff < out_coff + channels && out_coff < in_coff + 4 * channels) RT_FAIL("op_maxpool_s2d: output overlaps the input slices");
     Op op;
@@ -923,26 +964,25 @@ static int launch_op(rtm3d_ctx* ctx, Op& op, hipStream_t s, const float* d_in, f
         case OP_CONV_MFMA: {
             ConvKArgs a = op.conv;
             if (op.epi_nchw) a.out = d_out[op.out_slot];
-            e = a.deep ? launch_conv_mfma_deep(a, op.bn_tile, op.groups, ctx->tile_ctr + 8 + TICKET_SLOTS, s)
+            e = a.deep ? launch_conv_mfma_deep(a, op.bn_tile, op.groups, split_ctrs(ctx), s)
                        : launch_conv_mfma(a, op.bn_tile, op.groups, op.epi_nchw, s);
             break;
         }
         case OP_CONV_MFMA256: e = launch_conv_mfma256(op.conv, op.groups, ctr256, op.stat_out, s); break;
-        case OP_CONV64_HALO: e = launch_conv64_halo(op.conv, ctx->n_cus, ctx->tile_ctr + 8 + op.ticket_slot, s); break;
-        case OP_CONV64S2_HALO: e = launch_conv64s2_halo(op.conv, ctx->n_cus, ctx->tile_ctr + 8 + op.ticket_slot, s); break;
-        case OP_CONV64_ROOT: e = launch_conv64_root(op.conv, op.root, ctx->n_cus, ctx->tile_ctr + 8 + op.ticket_slot, s); break;
-        case OP_CONV128_HALO: e = launch_conv128_halo(op.conv, ctx->n_cus, ctx->tile_ctr + 8 + op.ticket_slot, s); break;
+        case OP_CONV64_HALO: e = launch_conv64_halo(op.conv, ctx->n_cus, ticket_ctr(ctx, op), s); break;
+        case OP_CONV64S2_HALO: e = launch_conv64s2_halo(op.conv, ctx->n_cus, ticket_ctr(ctx, op), s); break;
+        case OP_CONV64_ROOT: e = launch_conv64_root(op.conv, op.root, ctx->n_cus, ticket_ctr(ctx, op), s); break;
+        case OP_CONV128_HALO: e = launch_conv128_halo(op.conv, ctx->n_cus, ticket_ctr(ctx, op), s); break;
         case OP_STEM_FUSED: {
             StemFusedArgs a = op.sf;
             a.x_nchw = d_in;                     // null: the NHWC4 tensor was filled by rtm3d_preprocess_batch
             e = launch_stem_fused(a, s);
             break;
         }
-        case OP_CONV32S2_FUSED: e = launch_conv32s2_fused(op.c32, ctx->n_cus, ctx->tile_ctr + 8 + op.ticket_slot, s); break;
+        case OP_CONV32S2_FUSED: e = launch_conv32s2_fused(op.c32, ctx->n_cus, ticket_ctr(ctx, op), s); break;
         case OP_CONV_SMALLC: e = launch_conv_smallc(op.conv, s); break;
-        case OP_INPUT4: if (!d_in || op.stem_cout == -1) break;   // filled by rtm3d_preprocess_batch (out_mode 1), or its only
-                                                                  // consumer is the fused stem, which reads the fp32 batch itself
-            e = launch_nchw_to_nhwc4(d_in, op.stem.out, op.stem.B, op.stem.H, op.stem.W, op.stem.out_Hp, op.stem.out_Wp, op.stem.out_P, s); break;
+        case OP_INPUT4: if (!d_in || op.input4_unread) break;    // filled by rtm3d_preprocess_batch (out_mode 1), or unread
+            e = launch_nchw_to_nhwc4(d_in, op.input4.base, op.input4.B, op.input4.H, op.input4.W, op.input4.Hp, op.input4.Wp, op.input4.P, s); break;
         case OP_HEADOUT: {
             HeadOutArgs a = op.ho;
             for (int i = 0; i < 4; ++i) a.out[i] = d_out[i];
@@ -1092,7 +1132,7 @@ extern "C" int rtm3d_input_tensor(rtm3d_ctx* ctx, void** d_base, int* B, int* H,
     if (!ctx || !d_base || !B || !H || !W || !border) RT_FAIL("input_tensor: null argument");
     for (auto& op : ctx->ops)
         if (op.kind == OP_INPUT4) {
-            *d_base = op.stem.out; *B = op.stem.B; *H = op.stem.H; *W = op.stem.W; *border = op.stem.out_P;
+            *d_base = op.input4.base; *B = op.input4.B; *H = op.input4.H; *W = op.input4.W; *border = op.input4.P;
             return 0;
         }
     RT_FAIL("input_tensor: the plan has no NHWC4 input tensor");

@@ -22,6 +22,7 @@ import os
 import numpy as np
 
 from . import _lib
+from ._lib import CONV_MFMA128, CONV_MFMA256, CONV_SMALLC, CONV_C64_HALO, CONV_C128_HALO, CONV_C64S2_HALO
 from . import mx8
 from .weights import parse_backbone, DLA34_CHANNELS, DLA34_LEVELS, RESNET_BLOCKS, head_table
 
@@ -554,13 +555,13 @@ V2_MIN_TILES_SHALLOW = 512   # layers with a short K loop (1x1 convs) or stride 
 
 
 def choose_variant(cin, cout, M, groups, out_nchw, ntaps=9, stride=1):
-    """2 = 256x256-tile 8-wave kernel (conv_mfma256.hip) when the layer has enough tiles to fill the
-    chip at one workgroup per CU; 0 = 128-pixel-tile kernel (conv_mfma.hip); 3 = register-direct MFMA kernel for the
-    4/16/32-channel layers of the stems (conv_smallc.hip)."""
+    """CONV_MFMA256 = 256x256-tile 8-wave kernel (conv_mfma256.hip) when the layer has enough tiles to fill the
+    chip at one workgroup per CU; CONV_MFMA128 = 128-pixel-tile kernel (conv_mfma.hip); CONV_SMALLC = register-direct MFMA
+    kernel for the 4/16/32-channel layers of the stems (conv_smallc.hip)."""
     if cin % 64:
         if cin not in (4, 16, 32):
             raise NotImplementedError('no HIP kernel for a convolution with %d input channels (supported: 4, 16, 32, multiples of 64)' % cin)
-        return 3
+        return CONV_SMALLC
     if not out_nchw and cout % 256 == 0:
         # one persistent workgroup per CU (256 CUs): at least ~a round of tiles.  History: up to the end of round 2 the bar was two
         # full rounds (512): a single nearly full round - DLA level4, 240 tiles - was 12 % faster per launch on this kernel but
@@ -572,8 +573,8 @@ def choose_variant(cin, cout, M, groups, out_nchw, ntaps=9, stride=1):
         # 0.019 / 0.049 on the 128-pixel one: the single-round bar is for stride-1 layers with at least 8 K-steps)
         deep = stride == 1 and ntaps * cin // 64 >= 8
         if ((M + 255) // 256) * (cout // 256) * groups >= (V2_MIN_TILES if deep else max(V2_MIN_TILES, V2_MIN_TILES_SHALLOW)):
-            return 2
-    return 0
+            return CONV_MFMA256
+    return CONV_MFMA128
 
 
 # ------------------------------------------------------------------------------------------ kernels and weight packing
@@ -669,16 +670,16 @@ def conv64s2_eligible(op):
 
 def conv_kernel(op, B):
     """Kernel variant (rtm3d_conv_desc.kernel) of a conv at batch B: the op's own 'variant' when it names one (tests), else
-    5 = conv64_halo.hip, 7 = conv64s2_halo.hip (with at least 64 of its 4 x 32-pixel tiles), 6 = conv128_halo.hip, else
-    choose_variant's 2 / 0 / 3."""
+    CONV_C64_HALO = conv64_halo.hip, CONV_C64S2_HALO = conv64s2_halo.hip (with at least 64 of its 4 x 32-pixel tiles),
+    CONV_C128_HALO = conv128_halo.hip, else choose_variant's choice."""
     if op.get('variant') is not None:
         return op['variant']
     if conv64_eligible(op):
-        return 5
+        return CONV_C64_HALO
     if conv64s2_eligible(op) and B * (op['Hm'] // 4) * (op['Wm'] // 32) >= 64:
-        return 7
+        return CONV_C64S2_HALO
     if USE_CONV128 and conv128_eligible(op, B):
-        return 6
+        return CONV_C128_HALO
     return choose_variant(op['cin'], op['cout'], B * op['Hm'] * op['Wm'], op['groups'], op['out_nchw'], len(op['taps'][0]), op['in_stride'])
 
 
@@ -769,7 +770,7 @@ def _softmax_stat_producers(P):
     """{conv op index: slot} for the convolutions whose epilogue can emit the spatial-softmax partials of a
     fusion operand (rtm3d_conv_desc.softmax_stat_slot): every operand of a fusion must be the whole 256-channel
     output of a conv that takes the halo-tile kernel (stride 1, taps within +-1 pixel, 8x32 tiles cover the
-    iteration domain, kernel variant 2), otherwise the fusion keeps its own reduction pass."""
+    iteration domain, kernel variant CONV_MFMA256), otherwise the fusion keeps its own reduction pass."""
     slots = {}
     for si, sop in enumerate(P.ops):
         if sop['op'] != 'softmax':
@@ -783,7 +784,7 @@ def _softmax_stat_producers(P):
             prods.append(cand[-1])
         if prods is None or len(set(prods)) != len(prods) or len(prods) > 3:
             continue
-        if all(conv_kernel(op, P.B) == 2 and op['cout'] == 256 and op['groups'] <= 4 and op['in_stride'] == 1 and not op['out_nchw']
+        if all(conv_kernel(op, P.B) == CONV_MFMA256 and op['cout'] == 256 and op['groups'] <= 4 and op['in_stride'] == 1 and not op['out_nchw']
                and op['Hm'] % 8 == 0 and op['Wm'] % 32 == 0 and len(op['taps'][0]) in (4, 9)
                and all(r is None for r in op['res']) and all(o.coff == 0 and o.C == 256 for o in op['out'])
                and all(abs(dy) <= 1 and abs(dx) <= 1 for tp in op['taps'] for dy, dx in tp)
@@ -898,7 +899,7 @@ def _project_folds(P):
               and not any(n.tid == R.tid for n in P.named.values()))
         # (conv64_halo.hip has no generic taps, conv128_halo.hip no one-tap chunk: with FOLD_PROJECT_C128 the fold takes the generic kernel)
         kernel = conv_kernel(c2, P.B) if ok else None
-        if ok and kernel != 5 and (kernel != 6 or FOLD_PROJECT_C128):
+        if ok and kernel != CONV_C64_HALO and (kernel != CONV_C128_HALO or FOLD_PROJECT_C128):
             out[k] = prods[0]
     return out
 
@@ -1039,7 +1040,7 @@ def _plan_s2d_only(P, nfold, tail, folds):
         ro = P.ops[tail[f['tail']][0]]['out'][0]
         readers = _readers(P, ro, set([f['tail'], f['up'], f['pj']] + list(tail[f['tail']])))
         r = P.ops[readers[0]] if len(readers) == 1 else None
-        if (r is not None and r['op'] == 'conv' and r.get('variant') is None and conv_kernel(r, P.B) == 7
+        if (r is not None and r['op'] == 'conv' and r.get('variant') is None and conv_kernel(r, P.B) == CONV_C64S2_HALO
                 and r['inp'][0].coff == ro.coff and readers[0] not in folds):
             f['s2d_only'] = True
             s2d_readers[readers[0]] = ('conv64s2', f['hs'], P.tensors[f['hs'].tid]['C'], f['Cf'])
@@ -1074,7 +1075,8 @@ def _plan_s2d_only(P, nfold, tail, folds):
     return s2d_only, s2d_readers, producers
 
 
-_BN_TILE = {7: 128, 6: 128, 5: 64, 2: 256, 3: 0}    # output-channel tile of the kernels that have one size
+# output-channel tile of the kernels that have one size
+_BN_TILE = {CONV_C64S2_HALO: 128, CONV_C128_HALO: 128, CONV_C64_HALO: 64, CONV_MFMA256: 256, CONV_SMALLC: 0}
 
 
 def _conv_launch(P, k, op, ops, stat_slots, s2d_out, in_s2d, write_out):
@@ -1088,18 +1090,18 @@ def _conv_launch(P, k, op, ops, stat_slots, s2d_out, in_s2d, write_out):
     if not write_out and s2d_out is None:
         raise RuntimeError('plan: %s is marked as writing only a space-to-depth copy but no copy was planned for it' % op['name'])
     # a conv that writes a space-to-depth copy runs on a kernel whose epilogue has the second store
-    kernel = (5 if conv64_eligible(op) else 0) if s2d_out is not None else conv_kernel(op, P.B)
-    if in_s2d is not None and kernel != 7:
-        #  this conv's input exists ONLY as its space-to-depth copy, which kernel 7 alone can read
+    kernel = (CONV_C64_HALO if conv64_eligible(op) else CONV_MFMA128) if s2d_out is not None else conv_kernel(op, P.B)
+    if in_s2d is not None and kernel != CONV_C64S2_HALO:
+        #  this conv's input exists ONLY as its space-to-depth copy, which conv64s2_halo alone can read
         raise RuntimeError('plan: the input of %s exists only as a space-to-depth copy but the conv went to kernel variant %r' % (op['name'], kernel))
-    assert kernel != 7 or conv64s2_eligible(op), op['name']
-    assert kernel != 5 or conv64_eligible(op), op['name']
-    assert kernel != 3 or op['groups'] == 1, op['name']
+    assert kernel != CONV_C64S2_HALO or conv64s2_eligible(op), op['name']
+    assert kernel != CONV_C64_HALO or conv64_eligible(op), op['name']
+    assert kernel != CONV_SMALLC or op['groups'] == 1, op['name']
     bn = _BN_TILE.get(kernel)
     if bn is None:                              # the 128-pixel kernel (conv_mfma.hip)
         if op['cin'] % 64:
             raise NotImplementedError('no HIP kernel for conv %s (cin=%d)' % (op['name'], op['cin']))
-        kernel = 0
+        kernel = CONV_MFMA128
         bn = op.get('bn_tile') or BN_TILE_OVERRIDE.get(op['name']) or choose_bn_tile(op['cout'], P.B * op['Hm'] * op['Wm'])
     return _launch('conv', op['name'], ops, op, kernel=kernel, bn_tile=bn, stat_slot=stat_slots.get(k, -1), s2d_out=s2d_out, write_out=write_out,
                    in_s2d=in_s2d)
@@ -1181,6 +1183,26 @@ def lower(P):
         launches.append(L)
     return {'launches': launches, 'widen': {f['hs'].tid: 4 * f['Cf'] for f in nfold}, 'stat_slots': stat_slots,
             'unwritten': unwritten, 's2d_only': s2d_only}
+
+
+def _smallc_rows(op):
+    """16 -> 16 channel stride-1 3x3 layers are packed by filter rows for conv_smallc.hip's vertical-walk kernel."""
+    return op['cin'] == 16 and op['cout'] == 16 and op['in_stride'] == 1 and op['out_scale'] == 1 and len(op['taps'][0]) == 9
+
+
+def _mfma_packing(op, bn):
+    return 'mfma', bn, lambda w: pack_mfma_weights(w, bn)[0]
+
+
+# rtm3d_conv_desc.kernel -> (op, bn tile) -> (weight-cache kind, weight-cache bn, packing of one group's weights)
+_CONV_PACKING = {
+    CONV_MFMA128: _mfma_packing,
+    CONV_MFMA256: _mfma_packing,
+    CONV_C128_HALO: _mfma_packing,            # the 128-pixel kernel's bn_tile = 128 packing
+    CONV_SMALLC: lambda op, bn: ('smallc%d' % _smallc_rows(op), 0, lambda w: pack_smallc_weights(w, rows=_smallc_rows(op))),
+    CONV_C64_HALO: lambda op, bn: ('c64', 0, pack_conv64_weights),
+    CONV_C64S2_HALO: lambda op, bn: ('c64s2', 0, pack_conv64s2_weights),
+}
 
 
 class RealizedPlan(object):
@@ -1304,26 +1326,12 @@ class RealizedPlan(object):
         if L['in_s2d'] is not None:             # the producer wrote only the space-to-depth copy of this conv's input
             d.in_tensor, d.in_coff[0], d.in_s2d = self.tids[L['in_s2d'][0].tid], L['in_s2d'][1], 1
         d.kernel, d.bn_tile = kernel, bn
-        if kernel in (5, 6, 7):                 # conv64_halo / conv128_halo / conv64s2_halo: one group
-            kind, key_bn, pack = {5: ('c64', 0, pack_conv64_weights), 6: ('mfma', 128, lambda w: pack_mfma_weights(w, 128)[0]),
-                                  7: ('c64s2', 0, pack_conv64s2_weights)}[kernel]
-            d.w_blob = self._blob(self._packed(op, 0, kind, key_bn, lambda: pack(op['w'][0])))
-            d.bias_blob = self._f32(op['bias'][0])
-        elif kernel == 2:
-            packed = [self._packed(op, g, 'mfma', 256, lambda g=g: pack_mfma_weights(op['w'][g], 256)[0]) for g in range(G)]
-            d.w_blob, d.bias_blob = self._blob(np.concatenate(packed)), self._blob(np.ascontiguousarray(op['bias'], np.float32).reshape(-1))
-        elif kernel == 3:
-            rows = op['cin'] == 16 and op['cout'] == 16 and op['in_stride'] == 1 and op['out_scale'] == 1 and len(op['taps'][0]) == 9
-            d.w_blob = self._blob(self._packed(op, 0, 'smallc%d' % rows, 0, lambda: pack_smallc_weights(op['w'][0], rows=rows)))
-            d.bias_blob = self._blob(op['bias'][0])
-        else:
-            packed, biases = [], []
-            for g in range(G):
-                packed.append(self._packed(op, g, 'mfma', bn, lambda g=g: pack_mfma_weights(op['w'][g], bn)[0]))
-                bb = np.zeros((op['cout'] + bn - 1) // bn * bn, np.float32)
-                bb[:op['cout']] = op['bias'][g]
-                biases.append(bb)
-            d.w_blob, d.bias_blob = self._blob(np.concatenate(packed)), self._blob(np.concatenate(biases))
+        # weights: each group packed for the kernel, groups one after the other; biases: fp32, each group padded to the bn tile
+        kind, key_bn, pack = _CONV_PACKING[kernel](op, bn)
+        packed = [self._packed(op, g, kind, key_bn, lambda g=g: pack(op['w'][g])) for g in range(G)]
+        cout_pad = -(-op['cout'] // bn) * bn if bn else op['cout']
+        biases = [np.pad(np.asarray(op['bias'][g], np.float32), (0, cout_pad - op['cout'])) for g in range(G)]
+        d.w_blob, d.bias_blob = self._blob(np.concatenate(packed)), self._blob(np.concatenate(biases))
         _lib.check(self.lib.rtm3d_op_conv(self.ctx, ctypes.byref(d)), 'op_conv ' + op['name'])
 
     def _rec_headout(self, L):

@@ -37,37 +37,37 @@ def h(t):
 
 CONV_CASES = [
     # B, H, W, cin, cout, k, stride, dil, relu, residual, variant, in_extra_ch
-    (2, 24, 40, 64, 64, 3, 1, 1, True, True, 0, 0),        # v1 BN=64, residual
-    (1, 13, 21, 128, 128, 3, 1, 1, True, False, 0, 64),     # ragged M (273 px), input slice of a wider tensor
-    (2, 16, 24, 64, 128, 3, 2, 1, False, False, 0, 0),      # stride 2
-    (1, 12, 20, 256, 64, 1, 1, 1, True, False, 0, 0),       # 1x1
-    (1, 20, 36, 64, 256, 3, 1, 6, True, False, 0, 0),       # dilation 6 (head conv)
-    (4, 96, 160, 64, 128, 3, 1, 1, True, True, 0, 0),       # v1 on a full-chip launch (480 tiles: the one-stage-in-flight kernel)
-    (1, 12, 40, 512, 512, 3, 1, 1, True, True, 0, 0),       # deep ring + split-K (32 tiles, 72 K-steps in 8 ranges), residual
-    (1, 12, 40, 512, 256, 1, 1, 1, False, False, 0, 64),    # deep ring + split-K of a 1x1 (8 K-steps in 2 ranges)
-    (2, 13, 21, 256, 128, 3, 1, 1, True, False, 0, 0),      # deep ring + split-K, ragged M (546 px = 4.27 tiles)
-    (3, 24, 40, 64, 256, 3, 1, 1, True, True, 2, 0),        # mfma256, ragged M (2880 = 11.25 tiles), residual
-    (1, 16, 20, 128, 512, 3, 1, 6, False, False, 2, 0),     # mfma256 persistent, NT=2, M=320: six XCDs get no tile
-    (3, 24, 40, 64, 256, 3, 1, 1, True, False, 2, 0),       # mfma256 persistent, ragged M (11.25 tiles), 9 K-tiles
-    (2, 12, 20, 256, 256, 1, 1, 1, False, False, 2, 64),    # mfma256 persistent, 1x1: the minimum of 4 K-tiles
-    (4, 96, 160, 256, 256, 1, 1, 1, True, False, 2, 0),     # mfma256 persistent, 240 tiles: every workgroup draws several tickets
-    (2, 24, 64, 64, 64, 3, 1, 1, True, True, 5, 64),        # conv64 halo: residual, input slice of a wider tensor, 12 tiles
-    (3, 40, 96, 64, 64, 3, 1, 1, False, False, 5, 0),       # conv64 halo: no ReLU, 45 tiles
-    (1, 8, 32, 64, 64, 3, 1, 1, True, False, 5, 0),         # conv64 halo: a single tile
-    (4, 96, 320, 64, 64, 3, 1, 1, True, True, 5, 0),        # conv64 halo: 480 tiles on 256 workgroups (ticket hand-out)
-    (2, 16, 64, 128, 128, 3, 1, 1, True, True, 6, 0),       # conv128 halo: residual, 8 tiles (fewer than workgroups)
-    (3, 24, 96, 128, 128, 3, 1, 1, False, False, 6, 64),    # conv128 halo: no ReLU, input slice of a wider tensor, 27 tiles
-    (1, 8, 32, 128, 128, 3, 1, 1, True, False, 6, 0),       # conv128 halo: a single tile
-    (8, 96, 160, 128, 128, 3, 1, 1, True, True, 6, 0),      # conv128 halo: 480 tiles on 256 workgroups (ticket hand-out)
-    (2, 16, 64, 256, 256, 3, 1, 1, True, True, 6, 0),       # conv128 halo: two channel tiles per pixel tile, 4 input chunks, residual
-    (2, 16, 64, 64, 128, 3, 2, 1, True, False, 7, 0),       # conv64s2 halo: 8 x 32 output map, 4 tiles
-    (3, 24, 128, 64, 128, 3, 2, 1, False, False, 7, 64),    # conv64s2 halo: no ReLU, input slice of a wider tensor, 18 tiles
-    (1, 8, 64, 64, 128, 3, 2, 1, True, False, 7, 0),        # conv64s2 halo: a single tile
-    (8, 96, 320, 64, 128, 3, 2, 1, True, False, 7, 0),      # conv64s2 halo: 480 tiles on 256 workgroups (ticket hand-out)
-    (2, 16, 24, 16, 16, 3, 1, 1, True, False, 3, 0),        # smallc 16->16
-    (2, 16, 24, 16, 32, 3, 2, 1, True, False, 3, 0),        # smallc 16->32 s2
-    (1, 18, 26, 32, 64, 3, 2, 1, True, False, 3, 0),        # smallc 32->64 s2
-    (1, 9, 13, 32, 64, 1, 1, 1, False, False, 3, 0),        # smallc 1x1
+    (2, 24, 40, 64, 64, 3, 1, 1, True, True, _lib.CONV_MFMA128, 0),         # v1 BN=64, residual
+    (1, 13, 21, 128, 128, 3, 1, 1, True, False, _lib.CONV_MFMA128, 64),     # ragged M (273 px), input slice of a wider tensor
+    (2, 16, 24, 64, 128, 3, 2, 1, False, False, _lib.CONV_MFMA128, 0),      # stride 2
+    (1, 12, 20, 256, 64, 1, 1, 1, True, False, _lib.CONV_MFMA128, 0),       # 1x1
+    (1, 20, 36, 64, 256, 3, 1, 6, True, False, _lib.CONV_MFMA128, 0),       # dilation 6 (head conv)
+    (4, 96, 160, 64, 128, 3, 1, 1, True, True, _lib.CONV_MFMA128, 0),       # v1 on a full-chip launch (480 tiles: the one-stage-in-flight kernel)
+    (1, 12, 40, 512, 512, 3, 1, 1, True, True, _lib.CONV_MFMA128, 0),       # deep ring + split-K (32 tiles, 72 K-steps in 8 ranges), residual
+    (1, 12, 40, 512, 256, 1, 1, 1, False, False, _lib.CONV_MFMA128, 64),    # deep ring + split-K of a 1x1 (8 K-steps in 2 ranges)
+    (2, 13, 21, 256, 128, 3, 1, 1, True, False, _lib.CONV_MFMA128, 0),      # deep ring + split-K, ragged M (546 px = 4.27 tiles)
+    (3, 24, 40, 64, 256, 3, 1, 1, True, True, _lib.CONV_MFMA256, 0),        # mfma256, ragged M (2880 = 11.25 tiles), residual
+    (1, 16, 20, 128, 512, 3, 1, 6, False, False, _lib.CONV_MFMA256, 0),     # mfma256 persistent, NT=2, M=320: six XCDs get no tile
+    (3, 24, 40, 64, 256, 3, 1, 1, True, False, _lib.CONV_MFMA256, 0),       # mfma256 persistent, ragged M (11.25 tiles), 9 K-tiles
+    (2, 12, 20, 256, 256, 1, 1, 1, False, False, _lib.CONV_MFMA256, 64),    # mfma256 persistent, 1x1: the minimum of 4 K-tiles
+    (4, 96, 160, 256, 256, 1, 1, 1, True, False, _lib.CONV_MFMA256, 0),     # mfma256 persistent, 240 tiles: every workgroup draws several tickets
+    (2, 24, 64, 64, 64, 3, 1, 1, True, True, _lib.CONV_C64_HALO, 64),       # conv64 halo: residual, input slice of a wider tensor, 12 tiles
+    (3, 40, 96, 64, 64, 3, 1, 1, False, False, _lib.CONV_C64_HALO, 0),      # conv64 halo: no ReLU, 45 tiles
+    (1, 8, 32, 64, 64, 3, 1, 1, True, False, _lib.CONV_C64_HALO, 0),        # conv64 halo: a single tile
+    (4, 96, 320, 64, 64, 3, 1, 1, True, True, _lib.CONV_C64_HALO, 0),       # conv64 halo: 480 tiles on 256 workgroups (ticket hand-out)
+    (2, 16, 64, 128, 128, 3, 1, 1, True, True, _lib.CONV_C128_HALO, 0),     # conv128 halo: residual, 8 tiles (fewer than workgroups)
+    (3, 24, 96, 128, 128, 3, 1, 1, False, False, _lib.CONV_C128_HALO, 64),  # conv128 halo: no ReLU, input slice of a wider tensor, 27 tiles
+    (1, 8, 32, 128, 128, 3, 1, 1, True, False, _lib.CONV_C128_HALO, 0),     # conv128 halo: a single tile
+    (8, 96, 160, 128, 128, 3, 1, 1, True, True, _lib.CONV_C128_HALO, 0),    # conv128 halo: 480 tiles on 256 workgroups (ticket hand-out)
+    (2, 16, 64, 256, 256, 3, 1, 1, True, True, _lib.CONV_C128_HALO, 0),     # conv128 halo: two channel tiles per pixel tile, 4 input chunks, residual
+    (2, 16, 64, 64, 128, 3, 2, 1, True, False, _lib.CONV_C64S2_HALO, 0),    # conv64s2 halo: 8 x 32 output map, 4 tiles
+    (3, 24, 128, 64, 128, 3, 2, 1, False, False, _lib.CONV_C64S2_HALO, 64), # conv64s2 halo: no ReLU, input slice of a wider tensor, 18 tiles
+    (1, 8, 64, 64, 128, 3, 2, 1, True, False, _lib.CONV_C64S2_HALO, 0),     # conv64s2 halo: a single tile
+    (8, 96, 320, 64, 128, 3, 2, 1, True, False, _lib.CONV_C64S2_HALO, 0),   # conv64s2 halo: 480 tiles on 256 workgroups (ticket hand-out)
+    (2, 16, 24, 16, 16, 3, 1, 1, True, False, _lib.CONV_SMALLC, 0),         # smallc 16->16
+    (2, 16, 24, 16, 32, 3, 2, 1, True, False, _lib.CONV_SMALLC, 0),         # smallc 16->32 s2
+    (1, 18, 26, 32, 64, 3, 2, 1, True, False, _lib.CONV_SMALLC, 0),         # smallc 32->64 s2
+    (1, 9, 13, 32, 64, 1, 1, 1, False, False, _lib.CONV_SMALLC, 0),         # smallc 1x1
 ]
 
 
@@ -118,7 +118,7 @@ def test_halo_conv256_vs_torch(shape):
         P.conv(xt, yt, ws[0], bs[0], relu=True, name='t')
     else:
         P.grouped_conv([P.sub(xt, g * cin, cin) for g in range(G)], [P.sub(yt, g * 256, 256) for g in range(G)], ws, bs, relu=True, name='t')
-    P.ops[-1]['variant'] = 2
+    P.ops[-1]['variant'] = _lib.CONV_MFMA256
     x = rng.standard_normal((B, cin * G, H, W)).astype(np.float32)
     (got,), _ = _run(P, [(xt, x)], [yt])
     ref = torch.cat([F.conv2d(h(torch.from_numpy(x[:, g * cin:(g + 1) * cin])), h(torch.from_numpy(ws[g])), torch.from_numpy(bs[g]), 1, 1)
@@ -144,7 +144,7 @@ def test_lattice_conv256_vs_torch(shape):
     w = (rng.standard_normal((cout, cin, 3, 3)) / np.sqrt(cin * 9)).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)
     P.conv(xs, yt, w, b, dil=6, relu=True, name='t')
-    P.ops[-1]['variant'] = 2
+    P.ops[-1]['variant'] = _lib.CONV_MFMA256
     x = rng.standard_normal((B, cin, H, W)).astype(np.float32)
     (got,), _ = _run(P, [(xs, x)], [yt], expect_kernel='conv3x3_mfma256_lattice')
     ref = h(F.conv2d(h(torch.from_numpy(x)), h(torch.from_numpy(w)), torch.from_numpy(b), 1, 6, 6).relu()).numpy()
@@ -162,7 +162,7 @@ def test_lattice_kernel_is_not_taken_for_other_shapes():
     w = (rng.standard_normal((cout, cin, 3, 3)) / np.sqrt(cin * 9)).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)
     P.conv(xt, yt, w, b, dil=6, relu=True, name='t')
-    P.ops[-1]['variant'] = 2
+    P.ops[-1]['variant'] = _lib.CONV_MFMA256
     x = rng.standard_normal((B, cin, H, W)).astype(np.float32)
     R = plan_mod.RealizedPlan(P, 0)
     names = R.kernel_names()
@@ -189,7 +189,7 @@ def test_conv256_input_beyond_4gb():
     w = (rng.standard_normal((cout, cin, 1, 1)) / np.sqrt(cin)).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)
     P.conv(xs, ys, w, b, relu=True, name='t')
-    P.ops[-1]['variant'] = 2
+    P.ops[-1]['variant'] = _lib.CONV_MFMA256
     # every image different, so that reading image (n - 7.8) instead of image n cannot go unnoticed
     x = rng.standard_normal((B, cin, H, W)).astype(np.float32)
     (got,), _ = _run(P, [(xs, x)], [ys])
@@ -210,7 +210,7 @@ def test_split_k_chain_is_deterministic():
     P.conv(xt, mt, w1, b1, relu=True, name='a')
     P.conv(mt, yt, w2, b2, relu=True, res=xt, name='b')
     for op in P.ops:
-        op['variant'] = 0
+        op['variant'] = _lib.CONV_MFMA128
     R = plan_mod.RealizedPlan(P, 0)
     assert R.kernel_names() == ['conv3x3_mfma_deep_splitk'] * 2
     x = rng.standard_normal((B, C, H, W)).astype(np.float32)
@@ -242,7 +242,7 @@ def test_persistent_conv_replays_identically():
         xt = P.tensor(96, 160, 256, 1)
         yt = P.tensor(96, 160, 256, 1)
         P.conv(xt, yt, (np.random.default_rng(1).standard_normal((256, 256, 3, 3)) / 48).astype(np.float32), np.zeros(256, np.float32), relu=True, name='t')
-        P.ops[-1]['variant'] = 2
+        P.ops[-1]['variant'] = _lib.CONV_MFMA256
         R = plan_mod.RealizedPlan(P, 0)
         x = np.random.default_rng(2).standard_normal((2, 256, 96, 160)).astype(np.float32)
         _lib.check(R.lib.rtm3d_tensor_upload(R.ctx, R.tids[xt.tid], 0, 256, x.ctypes.data_as(ctypes.c_void_p)))
@@ -259,7 +259,8 @@ def test_persistent_conv_replays_identically():
 
 
 # (the last two: maps covered by 8 x 32 tiles - the four sub-pixel phases run on the halo-tile kernel, three halo rows per K-tile)
-@pytest.mark.parametrize('shape', [(2, 6, 10, 0), (1, 12, 40, 0), (4, 24, 80, 2), (32, 12, 40, 2), (2, 16, 64, 2), (5, 24, 96, 2)])
+@pytest.mark.parametrize('shape', [(2, 6, 10, _lib.CONV_MFMA128), (1, 12, 40, _lib.CONV_MFMA128), (4, 24, 80, _lib.CONV_MFMA256),
+                                   (32, 12, 40, _lib.CONV_MFMA256), (2, 16, 64, _lib.CONV_MFMA256), (5, 24, 96, _lib.CONV_MFMA256)])
 def test_deconv_phases_vs_torch(shape):
     B, H, W, variant = shape
     rng = np.random.default_rng(B * 1000 + H)
@@ -324,7 +325,7 @@ def test_softmax_fuse_with_epilogue_partials():
     ws = [(rng.standard_normal((256, 256, 4, 4)) * sc / 32).astype(np.float32) for sc in (1.0, 2.5, 6.0)]
     for x, u, w in zip(xs, us, ws):
         P.deconv(x, u, w, name='up')
-        P.ops[-1]['variant'] = 2
+        P.ops[-1]['variant'] = _lib.CONV_MFMA256
     z = P.tensor(2 * H, 2 * W, 256, 6)
     P.softmax_fuse(z0, z, us, name='fuse')
     zin = rng.standard_normal((B, 256, 2 * H, 2 * W)).astype(np.float32)
@@ -651,7 +652,7 @@ def test_round4_entry_points_refuse_bad_arguments():
         t_a, t_b = tensor(1, 8, 16, 128, 1), tensor(1, 8, 16, 128, 1)
         d.in_tensor, d.out_tensor, d.res_tensor, d.s2d_tensor, d.softmax_stat_slot = t_a, t_b, -1, 0, -1
         d.Hm, d.Wm, d.in_stride, d.out_scale, d.cin, d.cout, d.groups, d.ntaps = 8, 16, 1, 1, 64, 128, 1, 2
-        d.kernel, d.bn_tile = 0, 128
+        d.kernel, d.bn_tile = _lib.CONV_MFMA128, 128
         d.w_blob, d.bias_blob = blob(2 * 128 * 64 * 2), blob(128 * 4)
         d.tap_dc[0][1] = 64
         assert lib.rtm3d_op_conv(ctx, ctypes.byref(d)) == 0, lib.rtm3d_last_error()
@@ -663,8 +664,64 @@ def test_round4_entry_points_refuse_bad_arguments():
         assert lib.rtm3d_op_conv(ctx, ctypes.byref(d)) == 0, lib.rtm3d_last_error()
         d.s2d_coff = 8
         assert lib.rtm3d_op_conv(ctx, ctypes.byref(d)) != 0 and b'space-to-depth' in lib.rtm3d_last_error()
-        d.s2d_coff, d.kernel = 0, 2
+        d.s2d_coff, d.kernel = 0, _lib.CONV_MFMA256
         assert lib.rtm3d_op_conv(ctx, ctypes.byref(d)) != 0
+
+        # every kernel id: one minimal descriptor it accepts (op name), and refusals that record nothing
+        def n_ops():
+            n = 0
+            while lib.rtm3d_op_info(ctx, n, None, None, None) == 0:
+                n += 1
+            return n
+
+        def conv(kernel, t_i, t_o, cin, cout, stride, k, bn, wbytes, bbytes, **fields):
+            c = _lib.ConvDesc()
+            c.in_tensor, c.out_tensor, c.res_tensor, c.s2d_tensor, c.softmax_stat_slot = t_i, t_o, -1, 0, -1
+            (_, H, W, _, _), (_, Ho, Wo, _, _) = tshape[t_i], tshape[t_o]
+            c.Hm, c.Wm, c.in_stride, c.out_scale, c.cin, c.cout, c.groups, c.ntaps = Ho, Wo, stride, 1, cin, cout, 1, k * k
+            for t in range(k * k):
+                c.tap_dy[0][t], c.tap_dx[0][t] = (t // k - k // 2, t % k - k // 2)
+            c.kernel, c.bn_tile, c.w_blob, c.bias_blob = kernel, bn, blob(wbytes), blob(bbytes)
+            for f, v in fields.items():
+                setattr(c, f, v)
+            return c
+
+        def refused(c, what):
+            n = n_ops()
+            rc = lib.rtm3d_op_conv(ctx, ctypes.byref(c))
+            err = lib.rtm3d_last_error()
+            assert rc != 0 and what in err, (c.kernel, what, err)
+            assert n_ops() == n
+
+        tshape = {t_a: (1, 8, 16, 128, 1), t_b: (1, 8, 16, 128, 1)}
+
+        def shaped(*args):
+            tshape[tensor(*args)] = args
+            return list(tshape)[-1]
+        t32, t256, t64, t64b, t128, t128b, t64w, t128h = (shaped(*a) for a in (
+            (1, 8, 16, 32, 1), (1, 8, 16, 256, 1), (1, 8, 32, 64, 1), (1, 8, 32, 64, 1), (1, 8, 32, 128, 1), (1, 8, 32, 128, 1),
+            (1, 8, 64, 64, 1), (1, 4, 32, 128, 1)))
+        accepted = (  # kernel, input, output, cin, cout, stride, k, bn_tile, weight bytes, bias bytes, op name
+            (_lib.CONV_MFMA128, t_a, t_b, 64, 64, 1, 1, 32, 64 * 64 * 2, 64 * 4, b'conv1x1_mfma'),
+            (_lib.CONV_MFMA256, t_a, t256, 64, 256, 1, 1, 256, 256 * 64 * 2, 256 * 4, b'conv1x1_mfma256'),
+            (_lib.CONV_SMALLC, t32, t_b, 32, 64, 1, 1, 0, 4 * 64 * 8 * 2, 64 * 4, b'conv_smallc_regmfma'),
+            (_lib.CONV_C64_HALO, t64, t64b, 64, 64, 1, 3, 64, 9 * 64 * 64 * 2, 64 * 4, b'conv3x3_c64_halo'),
+            (_lib.CONV_C128_HALO, t128, t128b, 128, 128, 1, 3, 128, 9 * 128 * 128 * 2, 128 * 4, b'conv3x3_c128_halo'),
+            (_lib.CONV_C64S2_HALO, t64w, t128h, 64, 128, 2, 3, 128, 9 * 64 * 128 * 2, 128 * 4, b'conv3x3s2_c64_halo'))
+        for kernel, t_i, t_o, cin, cout, stride, k, bn, wbytes, bbytes, name in accepted:
+            refused(conv(kernel, t_i, t_o, cin, cout, stride, k, bn, wbytes + 16, bbytes), b'blob')
+            refused(conv(kernel, t_i, t_o, cin, cout, stride, k, bn, wbytes, bbytes, out_coff=(ctypes.c_int * 4)(4, 0, 0, 0)), b'output channel slice')
+            if kernel != _lib.CONV_C64S2_HALO:
+                refused(conv(kernel, t_i, t_o, cin, cout, stride, k, bn, wbytes, bbytes, in_s2d=1), b'space-to-depth INPUT')
+            if kernel != _lib.CONV_MFMA256:
+                refused(conv(kernel, t_i, t_o, cin, cout, stride, k, bn, wbytes, bbytes, softmax_stat_slot=0), b'softmax_stat_slot')
+            n = n_ops()
+            assert lib.rtm3d_op_conv(ctx, ctypes.byref(conv(kernel, t_i, t_o, cin, cout, stride, k, bn, wbytes, bbytes))) == 0, lib.rtm3d_last_error()
+            got = ctypes.c_char_p()
+            _lib.check(lib.rtm3d_op_info(ctx, n, None, None, ctypes.byref(got)))
+            assert got.value == name and n_ops() == n + 1, (kernel, got.value)
+        for kernel in (1, 4, 8, -1):
+            refused(conv(kernel, t_a, t_b, 64, 64, 1, 1, 32, 64 * 64 * 2, 64 * 4), b'unknown kernel')
         # gather_peak_patches: capacity
         z = torch.zeros(4, device='cuda')
         rc = lib.rtm3d_gather_peak_patches(None, z.data_ptr(), 8, 8, 256, 1, 2, 100, z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), 150, 15, 1600)

@@ -38,7 +38,7 @@ def _softmax_partials_plan():
     ws = [(rng.standard_normal((256, 256, 4, 4)) * sc / 32).astype(np.float32) for sc in (1.0, 2.5, 6.0)]
     for x, u, w in zip(xs, us, ws):
         P.deconv(x, u, w, name='up')
-        P.ops[-1]['variant'] = 2
+        P.ops[-1]['variant'] = _lib.CONV_MFMA256
     z = P.tensor(2 * H, 2 * W, 256, 6)
     P.softmax_fuse(z0, z, us, name='fuse')
     return P
