@@ -228,8 +228,10 @@ hipError_t launch_conv_headout(const HeadOutArgs& a, hipStream_t s);
 hipError_t launch_conv_mfma(const ConvKArgs& a, int bn_tile, int groups, int epi_nchw, hipStream_t s);
 hipError_t launch_conv_mfma_deep(const ConvKArgs& a, int bn_tile, int groups, unsigned int* tile_ctr, hipStream_t s);
 hipError_t launch_conv_mfma256(const ConvKArgs& a, int groups, unsigned int* tile_ctr, float* stat_out, hipStream_t s);
-bool conv_mfma256_uses_halo(const ConvKArgs& a, int groups);
-bool conv_mfma256_uses_lattice(const ConvKArgs& a, int groups);
+// the kernel launch_conv_mfma256 runs a conv on (conv_mfma256_route; ht: the halo route's packed taps, may be null): one tile per
+// workgroup (conv_mfma256_kernel), the generic persistent kernel, the halo-tile kernel, the dilation row-sub-lattice kernel
+enum Conv256Route { C256_ONE_TILE, C256_PERSISTENT, C256_HALO, C256_LATTICE };
+Conv256Route conv_mfma256_route(const ConvKArgs& a, int groups, HaloTaps* ht);
 bool conv64_halo_supported(const ConvKArgs& a, int groups);
 hipError_t launch_conv64_halo(const ConvKArgs& a, int cu_count, unsigned int* ticket_ctr, hipStream_t s);
 hipError_t launch_conv64_root(const ConvKArgs& a, const RootKArgs& r, int cu_count, unsigned int* ticket_ctr, hipStream_t s);

@@ -727,46 +727,44 @@ static int device_cu_count() {
     return n;
 }
 
-// Whether launch_conv_mfma256 sends this conv to the halo-tile kernel (the only one that can emit the
-// spatial-softmax partials of its output, `stat_out`).
-bool conv_mfma256_uses_halo(const ConvKArgs& a, int groups) {
+// the bias floats a launch stages in LDS: up to the last group's last channel, padded to whole 256-float runs (the bias array
+// is padded to that), since channel tiles read whole runs
+static int conv256_nbias(const ConvKArgs& a, int groups) {
     int nbias = 0;
     for (int g = 0; g < groups; ++g) nbias = a.g[g].bias_off + a.cout > nbias ? a.g[g].bias_off + a.cout : nbias;
-    nbias = (nbias + 255) / 256 * 256;
-    HaloTaps ht;
-    return a.ksteps >= 4 && !a.res && (a.ntaps == 9 || a.ntaps == 4) && nbias <= 1024 && conv_mfma256_halo_supported(a, groups, &ht);
+    return (nbias + 255) / 256 * 256;
 }
 
-// Whether launch_conv_mfma256 sends this conv to the row-sub-lattice halo kernel (dilated 3x3 layers, conv_mfma256_lattice.hip).
-bool conv_mfma256_uses_lattice(const ConvKArgs& a, int groups) {
-#ifdef C256_T_NOLATTICE
-    return false;
-#endif
-    int nbias = 0;
-    for (int g = 0; g < groups; ++g) nbias = a.g[g].bias_off + a.cout > nbias ? a.g[g].bias_off + a.cout : nbias;
-    nbias = (nbias + 255) / 256 * 256;
+// The kernel launch_conv_mfma256 runs this conv on: the one place that decides it (admit_mfma256 names the op after it, and only
+// the halo route can emit spatial-softmax partials).  ht: the halo route's packed taps.
+Conv256Route conv_mfma256_route(const ConvKArgs& a, int groups, HaloTaps* ht) {
+    const int nbias = conv256_nbias(a, groups);
+    // the persistent kernels address their pixel operand as SGPR base + 32-bit byte offset per lane: inputs of 4 GB and more
+    // (bs = 32 tops out at 2.07 GB) take the one-tile kernel, which carries 64-bit addresses
     const unsigned long long in_bytes = (unsigned long long)(a.M / a.HmWm) * a.in_Hp * a.in_Wp * a.in_C * 2ull;
-    return a.ksteps >= 4 && nbias <= 1024 && in_bytes < (1ull << 32) && conv_mfma256_lattice_dilation(a, groups) != 0;
+    if (a.ksteps < 4 || nbias > CONV256_MAX_BIAS || in_bytes >= (1ull << 32)) return C256_ONE_TILE;
+    HaloTaps scratch;
+    if (!ht) ht = &scratch;
+#ifdef C256_T_NOHALO9
+    if (a.ntaps == 9) {} else          // (same-box A/B only: 3x3 layers on the generic persistent form)
+#endif
+    if (!a.res && (a.ntaps == 9 || a.ntaps == 4) && nbias <= 1024 && conv_mfma256_halo_supported(a, groups, ht)) return C256_HALO;
+#ifndef C256_T_NOLATTICE                // (same-box A/B only: the dilated head conv on the generic persistent form)
+    if (nbias <= 1024 && conv_mfma256_lattice_dilation(a, groups) != 0) return C256_LATTICE;
+#endif
+    return C256_PERSISTENT;
 }
 
 hipError_t launch_conv_mfma256(const ConvKArgs& a, int groups, unsigned int* tile_ctr, float* stat_out, hipStream_t s) {
     dim3 block(512, 1, 1);
-    int nbias = 0;
-    for (int g = 0; g < groups; ++g) nbias = a.g[g].bias_off + a.cout > nbias ? a.g[g].bias_off + a.cout : nbias;
-    nbias = (nbias + 255) / 256 * 256;      // channel tiles read whole 256-float runs (the bias array is padded to that)
-    // the persistent kernel addresses its pixel operand as SGPR base + 32-bit byte offset per lane: inputs of 4 GB and more
-    // (bs = 32 tops out at 2.07 GB) take the one-tile kernel below, which carries 64-bit addresses
-    const unsigned long long in_bytes = (unsigned long long)(a.M / a.HmWm) * a.in_Hp * a.in_Wp * a.in_C * 2ull;
-    if (a.ksteps >= 4 && nbias <= CONV256_MAX_BIAS && tile_ctr && in_bytes < (1ull << 32)) {
-        HaloTaps ht;
-#ifdef C256_T_NOHALO9
-        if (a.ntaps == 9) {} else          // (same-box A/B only: 3x3 layers on the generic persistent form)
-#endif
-        if (!a.res && (a.ntaps == 9 || a.ntaps == 4) && nbias <= 1024 && conv_mfma256_halo_supported(a, groups, &ht))
-            return launch_conv_mfma256_halo(a, ht, groups, nbias, device_cu_count(), tile_ctr, stat_out, s);
-        if (stat_out) return hipErrorInvalidValue;   // only the halo kernel writes softmax partials
-        // (-DC256_T_NOLATTICE, same-box A/B only: the dilated head conv on the generic persistent form)
-        if (conv_mfma256_uses_lattice(a, groups)) return launch_conv_mfma256_lattice(a, groups, nbias, device_cu_count(), tile_ctr, s);
+    HaloTaps ht;
+    const Conv256Route route = conv_mfma256_route(a, groups, &ht);
+    if (stat_out && route != C256_HALO) return hipErrorInvalidValue;     // only the halo kernel writes softmax partials
+    if (route != C256_ONE_TILE && !tile_ctr) return hipErrorInvalidValue;
+    const int nbias = conv256_nbias(a, groups);
+    if (route == C256_HALO) return launch_conv_mfma256_halo(a, ht, groups, nbias, device_cu_count(), tile_ctr, stat_out, s);
+    if (route == C256_LATTICE) return launch_conv_mfma256_lattice(a, groups, nbias, device_cu_count(), tile_ctr, s);
+    if (route == C256_PERSISTENT) {
         // One workgroup per CU even when there are fewer tiles (level 4: 240): with exactly as many workgroups as tiles ONE CU held
         // by another stream's workgroup costs the launch a second round; the spare workgroups find the list empty and leave.
         // Launches of at most one round take one list for the whole chip (see the kernel).  Round 6, same box, pipelined bs=32
@@ -781,7 +779,6 @@ hipError_t launch_conv_mfma256(const ConvKArgs& a, int groups, unsigned int* til
         else hipLaunchKernelGGL((conv_mfma256_persistent_kernel<0, 0>), grid, block, 0, s, a, groups, nbias, tile_ctr, one_list);
         return hipGetLastError();
     }
-    if (stat_out) return hipErrorInvalidValue;       // only the halo kernel writes softmax partials
     const int mt8 = (a.MT + 7) / 8 * 8;
     dim3 grid(mt8 * a.NT, groups, 1);
     if (a.res) hipLaunchKernelGGL((conv_mfma256_kernel<1>), grid, block, 0, s, a);

@@ -315,7 +315,10 @@ static int admit_mfma256(rtm3d_ctx* ctx, const rtm3d_conv_desc* d, size_t wbytes
     for (int g = 0; g < d->groups; ++g) { a.g[g].w_off = (uint32_t)(per_group * g); a.g[g].bias_off = d->cout * g; }
     op.kind = OP_CONV_MFMA256; op.bn_tile = 256;
     if (ensure_tile_ctr(ctx)) return 1;
-    op.name = d->ntaps == 1 ? "conv1x1_mfma256" : (d->ntaps == 4 ? "deconv4x4_phase_mfma256" : (conv_mfma256_uses_lattice(a, d->groups) ? "conv3x3_mfma256_lattice" : "conv3x3_mfma256"));
+    // the name says which kernel launch_conv_mfma256 will run it on (the generic persistent one keeps the bare name)
+    static const char* const suffix[] = {"_1tile", "", "_halo", "_lattice"};
+    op.name = d->ntaps == 1 ? "conv1x1_mfma256" : (d->ntaps == 4 ? "deconv4x4_phase_mfma256" : "conv3x3_mfma256");
+    op.name += suffix[conv_mfma256_route(a, d->groups, nullptr)];
     return 0;
 }
 
@@ -487,7 +490,7 @@ extern "C" int rtm3d_op_conv(rtm3d_ctx* ctx, const rtm3d_conv_desc* d) {
         // epilogue-emitted spatial-softmax partials: [slot][image][chunk][256][2] floats, chunk = 128-pixel run
         if (op.kind != OP_CONV_MFMA256) RT_FAIL("op_conv: softmax_stat_slot needs kernel = 2");
         if (stat_slot > 2) RT_FAIL("op_conv: softmax_stat_slot out of range");
-        if (!conv_mfma256_uses_halo(a, d->groups)) RT_FAIL("op_conv: softmax_stat_slot set on a conv that does not take the halo-tile kernel");
+        if (conv_mfma256_route(a, d->groups, nullptr) != C256_HALO) RT_FAIL("op_conv: softmax_stat_slot set on a conv that does not take the halo-tile kernel");
         if (d->cout != 256 || out->C != 256) RT_FAIL("op_conv: softmax partials need a 256-channel output tensor");
         for (int g = 0; g < d->groups; ++g) if (d->out_coff[g] != 0) RT_FAIL("op_conv: softmax partials need output channel offset 0");
         const int chunks = d->groups * (d->Hm / 8) * (d->Wm / 32) * 2;

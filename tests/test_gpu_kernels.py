@@ -14,10 +14,10 @@ pytestmark = pytest.mark.gpu
 from rtm3d_amd import plan as plan_mod, _lib     # noqa: E402
 
 
-def _run(P, feeds, fetch, x_img=None, expect_kernel=None):
+def _run(P, feeds, fetch, x_img=None, expect_kernels=None):
     R = plan_mod.RealizedPlan(P, 0)
-    if expect_kernel is not None:
-        assert expect_kernel in R.kernel_names(), R.kernel_names()
+    if expect_kernels is not None:
+        assert R.kernel_names() == expect_kernels, R.kernel_names()
     for s, arr in feeds:
         arr = np.ascontiguousarray(arr, np.float32)
         _lib.check(R.lib.rtm3d_tensor_upload(R.ctx, R.tids[s.tid], s.coff, s.C, arr.ctypes.data_as(ctypes.c_void_p)))
@@ -47,7 +47,7 @@ CONV_CASES = [
     (1, 12, 40, 512, 256, 1, 1, 1, False, False, _lib.CONV_MFMA128, 64),    # deep ring + split-K of a 1x1 (8 K-steps in 2 ranges)
     (2, 13, 21, 256, 128, 3, 1, 1, True, False, _lib.CONV_MFMA128, 0),      # deep ring + split-K, ragged M (546 px = 4.27 tiles)
     (3, 24, 40, 64, 256, 3, 1, 1, True, True, _lib.CONV_MFMA256, 0),        # mfma256, ragged M (2880 = 11.25 tiles), residual
-    (1, 16, 20, 128, 512, 3, 1, 6, False, False, _lib.CONV_MFMA256, 0),     # mfma256 persistent, NT=2, M=320: six XCDs get no tile
+    (1, 16, 20, 128, 512, 3, 1, 6, False, False, _lib.CONV_MFMA256, 0),     # mfma256 persistent, NT=2, M=320: 4 tiles from one list
     (3, 24, 40, 64, 256, 3, 1, 1, True, False, _lib.CONV_MFMA256, 0),       # mfma256 persistent, ragged M (11.25 tiles), 9 K-tiles
     (2, 12, 20, 256, 256, 1, 1, 1, False, False, _lib.CONV_MFMA256, 64),    # mfma256 persistent, 1x1: the minimum of 4 K-tiles
     (4, 96, 160, 256, 256, 1, 1, 1, True, False, _lib.CONV_MFMA256, 0),     # mfma256 persistent, 240 tiles: every workgroup draws several tickets
@@ -120,7 +120,7 @@ def test_halo_conv256_vs_torch(shape):
         P.grouped_conv([P.sub(xt, g * cin, cin) for g in range(G)], [P.sub(yt, g * 256, 256) for g in range(G)], ws, bs, relu=True, name='t')
     P.ops[-1]['variant'] = _lib.CONV_MFMA256
     x = rng.standard_normal((B, cin * G, H, W)).astype(np.float32)
-    (got,), _ = _run(P, [(xt, x)], [yt])
+    (got,), _ = _run(P, [(xt, x)], [yt], expect_kernels=['conv3x3_mfma256_halo'])
     ref = torch.cat([F.conv2d(h(torch.from_numpy(x[:, g * cin:(g + 1) * cin])), h(torch.from_numpy(ws[g])), torch.from_numpy(bs[g]), 1, 1)
                      for g in range(G)], 1).relu()
     ref = h(ref).numpy()
@@ -128,8 +128,10 @@ def test_halo_conv256_vs_torch(shape):
 
 
 # (1, 48, 32, 64, 256): one 64-channel chunk -> every K-tile stages rows of the NEXT tile; (2, 48, 64, 256, 512): four chunks, two channel
-# tiles; (40, 48, 32, 128, 256): 240 tiles, a workgroup runs several in a row and the row ring wraps across tiles; (1, 96, 320, 256, 1024):
-# one image of the head conv itself; (3, 96, 64, 192, 256): three chunks (the ring base returns to 0 only every eight chunks)
+# tiles; (40, 48, 32, 128, 256): 240 tiles in lists of 30 for 32 workgroups each - one tile per workgroup, the ring is NOT carried
+# across tiles here; (1, 96, 320, 256, 1024): one image of the head conv itself, 480 tiles in lists of 60: some workgroup runs two
+# tiles in a row, the second at ring base 8; (3, 96, 64, 192, 256): three chunks within one tile (the ring base wraps past 16).
+# The ring carried across tiles for every chunk count, and the other shapes the kernel admits: tests/test_gpu_conv256.py
 @pytest.mark.parametrize('shape', [(1, 48, 32, 64, 256), (2, 48, 64, 256, 512), (40, 48, 32, 128, 256), (1, 96, 320, 256, 1024), (3, 96, 64, 192, 256)])
 def test_lattice_conv256_vs_torch(shape):
     """3x3 DILATION-6 convs (the fused head conv, header.py:12-16) whose map is covered by tiles of 8 lattice rows x 32 columns take
@@ -146,7 +148,7 @@ def test_lattice_conv256_vs_torch(shape):
     P.conv(xs, yt, w, b, dil=6, relu=True, name='t')
     P.ops[-1]['variant'] = _lib.CONV_MFMA256
     x = rng.standard_normal((B, cin, H, W)).astype(np.float32)
-    (got,), _ = _run(P, [(xs, x)], [yt], expect_kernel='conv3x3_mfma256_lattice')
+    (got,), _ = _run(P, [(xs, x)], [yt], expect_kernels=['conv3x3_mfma256_lattice'])
     ref = h(F.conv2d(h(torch.from_numpy(x)), h(torch.from_numpy(w)), torch.from_numpy(b), 1, 6, 6).relu()).numpy()
     np.testing.assert_allclose(got, ref, rtol=2e-3, atol=2e-3 * max(1.0, np.abs(ref).max()))
 
@@ -167,7 +169,7 @@ def test_lattice_kernel_is_not_taken_for_other_shapes():
     R = plan_mod.RealizedPlan(P, 0)
     names = R.kernel_names()
     R.close()
-    assert 'conv3x3_mfma256' in names and 'conv3x3_mfma256_lattice' not in names, names
+    assert names == ['conv3x3_mfma256'], names             # the generic persistent route
     (got,), _ = _run(P, [(xt, x)], [yt])
     ref = h(F.conv2d(h(torch.from_numpy(x)), h(torch.from_numpy(w)), torch.from_numpy(b), 1, 6, 6).relu()).numpy()
     np.testing.assert_allclose(got, ref, rtol=2e-3, atol=2e-3 * max(1.0, np.abs(ref).max()))
@@ -192,7 +194,7 @@ def test_conv256_input_beyond_4gb():
     P.ops[-1]['variant'] = _lib.CONV_MFMA256
     # every image different, so that reading image (n - 7.8) instead of image n cannot go unnoticed
     x = rng.standard_normal((B, cin, H, W)).astype(np.float32)
-    (got,), _ = _run(P, [(xs, x)], [ys])
+    (got,), _ = _run(P, [(xs, x)], [ys], expect_kernels=['conv1x1_mfma256_1tile'])
     ref = h(F.conv2d(h(torch.from_numpy(x)), h(torch.from_numpy(w)), torch.from_numpy(b)).relu()).numpy()
     np.testing.assert_allclose(got, ref, rtol=2e-3, atol=2e-3 * max(1.0, np.abs(ref).max()))
 
@@ -271,7 +273,9 @@ def test_deconv_phases_vs_torch(shape):
     P.deconv(xt, yt, w, name='up')
     P.ops[-1]['variant'] = variant
     x = rng.standard_normal((B, 256, H, W)).astype(np.float32)
-    (got,), _ = _run(P, [(xt, x)], [yt])
+    halo = W % 32 == 0 and H % 8 == 0
+    expect = ['deconv4x4_phase_mfma256' + ('_halo' if halo else '')] if variant == _lib.CONV_MFMA256 else None
+    (got,), _ = _run(P, [(xt, x)], [yt], expect_kernels=expect)
     ref = h(F.conv_transpose2d(h(torch.from_numpy(x)), h(torch.from_numpy(w)), None, 2, 1)).numpy()
     np.testing.assert_allclose(got, ref, rtol=2e-3, atol=2e-3 * max(1.0, np.abs(ref).max()))
 
@@ -615,9 +619,10 @@ def test_forward_on_two_streams_is_serialised():
             assert torch.equal(a, b)
 
 
-def test_round4_entry_points_refuse_bad_arguments():
+def test_round4_entry_points_refuse_bad_arguments_and_name_routes():
     """Error behaviour of what round 4 added to the C ABI: every refusal returns non-zero with a message and records nothing
-    (the plan stays usable)."""
+    (the plan stays usable).  Every kernel id's accepted descriptor records the op name of the route it takes (the 1x1 cin=64
+    conv256 has one K-step: the one-tile route, conv1x1_mfma256_1tile)."""
     lib = _lib.load()
     ctx = ctypes.c_void_p()
     _lib.check(lib.rtm3d_ctx_create(0, ctypes.byref(ctx)))
@@ -698,12 +703,13 @@ def test_round4_entry_points_refuse_bad_arguments():
         def shaped(*args):
             tshape[tensor(*args)] = args
             return list(tshape)[-1]
-        t32, t256, t64, t64b, t128, t128b, t64w, t128h = (shaped(*a) for a in (
-            (1, 8, 16, 32, 1), (1, 8, 16, 256, 1), (1, 8, 32, 64, 1), (1, 8, 32, 64, 1), (1, 8, 32, 128, 1), (1, 8, 32, 128, 1),
-            (1, 8, 64, 64, 1), (1, 4, 32, 128, 1)))
+        t32, t256, t256b, t64, t64b, t128, t128b, t64w, t128h = (shaped(*a) for a in (
+            (1, 8, 16, 32, 1), (1, 8, 16, 256, 1), (1, 8, 16, 256, 1), (1, 8, 32, 64, 1), (1, 8, 32, 64, 1), (1, 8, 32, 128, 1),
+            (1, 8, 32, 128, 1), (1, 8, 64, 64, 1), (1, 4, 32, 128, 1)))
         accepted = (  # kernel, input, output, cin, cout, stride, k, bn_tile, weight bytes, bias bytes, op name
             (_lib.CONV_MFMA128, t_a, t_b, 64, 64, 1, 1, 32, 64 * 64 * 2, 64 * 4, b'conv1x1_mfma'),
-            (_lib.CONV_MFMA256, t_a, t256, 64, 256, 1, 1, 256, 256 * 64 * 2, 256 * 4, b'conv1x1_mfma256'),
+            (_lib.CONV_MFMA256, t_a, t256, 64, 256, 1, 1, 256, 256 * 64 * 2, 256 * 4, b'conv1x1_mfma256_1tile'),   # 1 K-step
+            (_lib.CONV_MFMA256, t256, t256b, 256, 256, 1, 1, 256, 256 * 256 * 2, 256 * 4, b'conv1x1_mfma256'),  # 4 K-steps: persistent
             (_lib.CONV_SMALLC, t32, t_b, 32, 64, 1, 1, 0, 4 * 64 * 8 * 2, 64 * 4, b'conv_smallc_regmfma'),
             (_lib.CONV_C64_HALO, t64, t64b, 64, 64, 1, 3, 64, 9 * 64 * 64 * 2, 64 * 4, b'conv3x3_c64_halo'),
             (_lib.CONV_C128_HALO, t128, t128b, 128, 128, 1, 3, 128, 9 * 128 * 128 * 2, 128 * 4, b'conv3x3_c128_halo'),
