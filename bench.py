@@ -13,8 +13,11 @@ fp32 accumulate, seeded synthetic weights ("trained"-style) and images.  Weak sc
 processes its own 32-image shard (configs[3] = 8 x 32).
 
 Prints ONE JSON line (rank 0) with the driver's keys plus `roofline` (dominant kernel, timed live
-with hipEvents on the launch stream) and `cpu_baseline` (the CPU oracle = PyTorch-CPU fp32
-restatement of the reference + SciPy L-BFGS-B, timed on this host on a bounded sample).
+with hipEvents on the launch stream during the timed steps).  A plain run does only that: set up, warm up,
+time the steps, print the line.  `--full` adds what takes runs of its own outside the timed steps:
+`cpu_baseline` (the CPU oracle = PyTorch-CPU fp32 restatement of the reference + SciPy L-BFGS-B, timed
+on this host on a bounded sample), `parity` (3D-box L-inf against that oracle), the peaks-only probe
+`detect_surface_sparse_heads` and the per-stage wall times `roofline.per_stage[*].wall_ms`.
 `--dump-outputs DIR` also writes the last timed step's detection records to DIR/records.npy, to compare two builds.
 """
 import argparse
@@ -47,10 +50,13 @@ def parse_args():
     ap.add_argument('--batch', type=int, default=32, help='images per GPU')
     ap.add_argument('--height', type=int, default=384)
     ap.add_argument('--width', type=int, default=1280)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-full', action='store_true', help='whole BASELINE.md section-4 CPU protocol (adds minutes: one-thread bs=8)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check, outside the timed steps, what the headline does not need: the CPU baseline, the parity block '
+                         'against the CPU oracle, the peaks-only probe and the per-stage wall times (without it: cpu_baseline and parity are null)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--cpu-full', action='store_true', help='with --full: whole BASELINE.md section-4 CPU protocol (adds minutes: one-thread bs=8)')
     ap.add_argument('--cpu-threads', type=int, default=0, help='threads of the all-thread CPU legs (0: min(scheduler affinity, cgroup CPU quota))')
-    ap.add_argument('--no-parity', action='store_true', help='skip the 3D-box L-inf check against the CPU oracle')
+    ap.add_argument('--no-parity', action='store_true', help='with --full: skip the 3D-box L-inf check against the CPU oracle')
     ap.add_argument('--parity-images', type=int, default=8, help='benchmark images the oracle runs for the parity block (16 planted cuboids each)')
     ap.add_argument('--side-cus', type=int, default=0, help='CUs the decode3d side stream may use (0 = unrestricted)')
     ap.add_argument('--depth', type=int, default=0, help='pipeline slots (0: automatic)')
@@ -66,7 +72,7 @@ def parse_args():
                          'preprocessed once, outside the timed region, into the fp32 NCHW batch that is then fed like the BASELINE line (the A/B partner)')
     ap.add_argument('--graph', action='store_true', help='DIAGNOSTIC (A/B): replay the plan as one hipGraph (the live roofline probe needs the eager replay, so launch_ms then comes from the per-op pass)')
     ap.add_argument('--bn-tile', action='append', default=[], metavar='OP=N', help='DIAGNOSTIC (A/B): output-channel tile (16/32/64/128) of the 128-pixel conv kernel for the op named OP (plan.BN_TILE_OVERRIDE)')
-    ap.add_argument('--no-sparse-probe', action='store_true', help='skip the informational detect_surface_sparse_heads block (a few pipelined steps of the peaks-only mode after the timed region)')
+    ap.add_argument('--no-sparse-probe', action='store_true', help='with --full: skip the informational detect_surface_sparse_heads block (a few pipelined steps of the peaks-only mode after the timed region)')
     ap.add_argument('--sparse-heads', action='store_true', help='DIAGNOSTIC (not the BASELINE line): the detect3d call surface with the regression head branches evaluated at the detected peaks only (Model.decode2d_sparse); Model.forward() and the headline keep all four dense maps')
     ap.add_argument('--zero-weights', action='store_true', help='DIAGNOSTIC: all weights and biases zero (every activation is 0): what the same kernels do when the MFMA operands carry no energy (profiles/r03_heads_clock.txt)')
     ap.add_argument('--solver-form', choices=['direct', 'published'], default=None,
@@ -734,7 +740,8 @@ def main():
         rec = rdist.pack_records(det.n, det.cls, det.score, det.mproj, det.verts, det.bbox, topk, boxes)
         return rdist.all_gather_records(rec, always=use_dist), det
 
-    # ---- warm-up (also records the plan) and choice of the dominant kernel for the live probe
+    # ---- warm-up (also records the plan) and choice of the dominant kernel for the live probe.  The per-op pass runs in every
+    # run, plain or --full: the timed steps bracket the op it picks with the probe's events
     rec, det = step()
     torch.cuda.synchronize(dev)
     plan = model._plan_for(B, H, W, dev, 'peaks' if args.sparse_heads else 'dense')
@@ -750,9 +757,9 @@ def main():
         plan.peak.forward_timed(stream, 0, pk)
         peak_info = plan.peak.forward_timed(stream, 0, pk)
     # wall time of the three stages in the REAL replay (side lanes on: the neck's up-sampling chains overlap its top-down chain,
-    # which the one-op-after-the-other pass above cannot see): events at the stage boundaries, best of five replays
+    # which the one-op-after-the-other pass above cannot see): events at the stage boundaries, best of five replays (--full)
     stage_wall = None
-    if not args.sparse_heads:
+    if args.full and not args.sparse_heads:
         nm_ = [i['name'] for i in info]
         first = lambda pred: next((k for k, n in enumerate(nm_) if pred(n)), None)
         marks = [first(lambda n: n.startswith('backbone')), first(lambda n: n.startswith(('kfpn', 'fusion'))), first(lambda n: n.startswith('heads'))]
@@ -912,15 +919,16 @@ def main():
                 print('%-28s %-22s %9.3f %9.1f %8.0f' % (i['name'][:28], i['kernel'], i['ms'], i['flops'] / i['ms'] / 1e9 if i['ms'] else 0,
                                                          i['bytes'] / i['ms'] / 1e6 if i['ms'] else 0), file=sys.stderr)
             print('forward total %.3f ms (per-op event timing)' % tot, file=sys.stderr)
-        if not args.no_cpu_baseline and world == 1:
+        # --full only, after the line's own figures: each of these takes runs of its own (tens of seconds of CPU oracle)
+        if args.full and not args.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline(bb, sd, H, W, cfg, full=args.cpu_full, threads=args.cpu_threads)
         else:
             out['cpu_baseline'] = None
-        if not args.no_parity and world == 1 and not args.from_uint8 and not args.sparse_heads:
+        if args.full and not args.no_parity and world == 1 and not args.from_uint8 and not args.sparse_heads:
             out['parity'] = parity_check(model, cfg, sd, bb, x, args.parity_images, dev, solver_form=args.solver_form)
         else:
             out['parity'] = None
-        if (not args.no_sparse_probe and world == 1 and pipe is not None and not args.sparse_heads and not args.from_uint8
+        if (args.full and not args.no_sparse_probe and world == 1 and pipe is not None and not args.sparse_heads and not args.from_uint8
                 and not args.diag_no_decode3d and model._head_variant in (None, 'rtm3d')):
             # informational, outside the timed region and never `value`: the same batch through the detect3d call surface with the
             # regression heads evaluated at the detected peaks only (what `bench.py --sparse-heads` times as a DIAGNOSTIC line)

@@ -1083,7 +1083,8 @@ def test_bench_spawn_path_nccl_world1(dev):
 
 def test_bench_dump_outputs(dev, tmp_path):
     """`bench.py --dump-outputs DIR`: the records the last timed step handed its caller, as DIR/records.npy (float32, (B, topk, 32)),
-    with a detection in every image of the seeded workload; `--steps` sets the timed steps and ms_per_step is reported."""
+    with a detection in every image of the seeded workload; `--steps` sets the timed steps and ms_per_step is reported.  A plain run
+    (no `--full`) carries none of the blocks that take runs of their own."""
     import subprocess, sys, os, json
     env = dict(os.environ)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
@@ -1091,11 +1092,13 @@ def test_bench_dump_outputs(dev, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     d = str(tmp_path / 'out')
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--batch', '4', '--height', '128',
-                        '--width', '256', '--backbone', 'RESNET-18', '--no-cpu-baseline', '--no-parity', '--no-sparse-probe', '--dump-outputs', d],
+                        '--width', '256', '--backbone', 'RESNET-18', '--dump-outputs', d],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
     assert out['steps'] == 3 and out['ms_per_step'] > 0
+    assert out['cpu_baseline'] is None and out['parity'] is None and 'detect_surface_sparse_heads' not in out
+    assert out['roofline']['launch_ms'] > 0 and all('wall_ms' not in st for st in out['roofline']['per_stage'].values())
     rec = np.load(os.path.join(d, 'records.npy'))
     assert rec.dtype == np.float32 and rec.shape == (4, 100, 32) and np.isfinite(rec).all()
     n = (rec[..., 31] > 0).sum(1)                          # flag column: valid records per image
@@ -1103,7 +1106,7 @@ def test_bench_dump_outputs(dev, tmp_path):
 
 
 def test_bench_line_parity_of_the_default_solver(dev):
-    """The default `python bench.py` line (DLA-34 bs=32 384x1280; few steps, no CPU baseline here) runs the PUBLISHED solver form in
+    """The `python bench.py --full` line (DLA-34 bs=32 384x1280; few steps, no CPU baseline here) runs the PUBLISHED solver form in
     its timed step and its stage parity - the device decode kernels on the oracle's logits with 16 cuboids planted per image -
     meets north_star on EVERY box the reference keeps: identical indices and keep decisions, box L-inf <= 1e-4."""
     import subprocess, sys, os, json
@@ -1111,7 +1114,7 @@ def test_bench_line_parity_of_the_default_solver(dev):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-sparse-probe'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-sparse-probe'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -1121,6 +1124,7 @@ def test_bench_line_parity_of_the_default_solver(dev):
     assert out['config']['solver_form'] == 'published' and st['solver_form'] == 'published'
     assert st['index_mismatches'] == 0 and st['keep_decision_mismatches'] == 0 and st['kept_ref'] >= 100, st
     assert st['box_linf'] <= 1e-4 and st['boxes']['box_linf']['frac_le_0.0001'] == 1.0, st
+    assert all(v['wall_ms'] > 0 for v in out['roofline']['per_stage'].values())          # --full: stage wall times of a real replay
 
 
 def test_bench_two_ranks_rehearsed_on_one_gpu(dev):
