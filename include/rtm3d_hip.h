@@ -450,6 +450,70 @@ typedef struct rtm3d_conv_mx8_desc {
 } rtm3d_conv_mx8_desc;
 int rtm3d_op_conv_mx8(rtm3d_ctx* ctx, const rtm3d_conv_mx8_desc* desc);
 
+/* ------------------------------------------------------------------ engine files (csrc/engine.cpp; added in ABI 9)
+ * An engine file is a realized plan written by rtm3d_amd.engine.save_engine: the state-changing calls the Python plan
+ * recorder made (tensor / blob creation and every launch, with the ids the recorder handed out), the packed weights and
+ * what a detect step needs.  Loading it replays those calls through the functions above, so a C caller gets the exact
+ * launches of the Python path without Python, torch or weight packing.  All integers little-endian.
+ *
+ *   header (256 bytes, zero-padded):
+ *     char magic[8] = "RTM3DENG"; uint32 format_version (RTM3D_ENGINE_FORMAT); uint32 abi_version (RTM3D_ABI_VERSION);
+ *     char arch[16] = "gfx950"; char state_digest[64] (hex sha256 of the state dict, rtm3d_amd.weight_cache.state_dict_digest);
+ *     uint8 body_sha256[32] (of everything after the header); uint64 body_bytes.
+ *     Nothing CU-specific is stored: the runtime picks routes from the context's CU count at replay.
+ *   body:
+ *     metadata (496 bytes): int32 B, H, W; char backbone[16]; int32 head_precision (0 fp16, 1 mxfp8), header_num_conv,
+ *       num_classes, head_channels[4], topk (TOPK_CANDIDATES); float down_sample, score_thresh; int32 n_dim_ref;
+ *       double dim_ref[16][3], ref_loc[3]; int32 solver_form (RTM3D_SOLVER_*), use_graph (default of rtm3d_ctx_set_graph);
+ *       double fun_accept (0.1)
+ *     uint32 n_records, n_blobs; uint64 records_bytes; then the records, each  uint32 opcode, uint32 payload_bytes, payload:
+ *        1 tensor_create / 2 tensor_create_mx8   int32 B, H, W, C, pad, id
+ *        3 blob_create                           uint64 bytes, offset in the blob area; int32 id, 0
+ *       16 op_input_nhwc4 (1 int32)   18 op_stem_fused (9)   19 op_conv32s2_fused (10)   20 op_conv64_root (16)
+ *       21 op_headout (in, w, bias, nheads, cout4[4])   22 op_maxpool (8)   23 op_maxpool_s2d (5)
+ *       24 op_softmax_fuse (z_in, z_out, n_u, u[3])   25 op_quant_mx8 (5)          (int32 arguments in prototype order)
+ *       17 op_conv / 26 op_conv_mx8                 uint32 sizeof(descriptor), then the descriptor bytes
+ *     uint64 blob_offset (from the body start, a multiple of 256), blob_bytes; zero padding; the blob area (each blob
+ *     at a multiple of 256).
+ * `id` is the id the recorder handed out; the loader refuses a replay that gets another one back.  Files of another
+ * format or ABI version are refused, not migrated.                                                                      */
+#define RTM3D_ENGINE_FORMAT 1
+#define RTM3D_ENGINE_MAX_CLASSES 16
+typedef struct rtm3d_engine_info {
+    int format_version, abi_version;
+    char arch[16];
+    char state_digest[72];                 /* hex, NUL-terminated */
+    int B, H, W;                           /* the input batch: fp32 NCHW (B, 3, H, W) */
+    char backbone[16];
+    int head_precision, header_num_conv, num_classes;
+    int head_channels[4];                  /* channels of the four logit maps (num_classes, 16, 2, 2) */
+    int topk;
+    float down_sample, score_thresh;
+    int n_dim_ref;
+    double dim_ref[RTM3D_ENGINE_MAX_CLASSES][3];
+    double ref_loc[3];
+    int solver_form, use_graph;
+    double fun_accept;
+    int n_records, n_tensors, n_mx8_tensors, n_blobs, n_launches, reserved;
+    uint64_t blob_bytes, file_bytes;
+} rtm3d_engine_info;
+/* Parse and check a whole engine file on the host, without touching a device: magic, versions, arch, sha256, every length
+ * against the end of the file, opcodes against the list above, descriptor sizes, every tensor / blob id against the ones
+ * created before it.  On failure rtm3d_last_error() names the record index and the reason.  info may be NULL.          */
+int rtm3d_engine_inspect(const char* path, rtm3d_engine_info* info);
+/* The same checks, then the device's arch, then a context on `device` into which the records are replayed (with the
+ * file's graph default).  On any failure the context is destroyed, *out is NULL and the call returns non-zero.
+ * Release with rtm3d_ctx_destroy.                                                                                       */
+int rtm3d_engine_load(const char* path, int device, rtm3d_ctx** out, rtm3d_engine_info* info);
+/* One detect step of a context made by rtm3d_engine_load, stream-ordered on `stream`, no host synchronisation:
+ * rtm3d_forward -> rtm3d_decode2d -> rtm3d_decode3d_slots -> rtm3d_pack_records with the file's metadata.
+ * d_in: fp32 NCHW (B, 3, H, W); d_K_per_image: B x 9 fp64; d_rec: B * topk * 32 fp32 records (layout of
+ * rtm3d_pack_records); d_workspace: rtm3d_engine_workspace_bytes(ctx) bytes of device memory (logits, decode slots,
+ * solver state), owned by the caller.  Keep d_in / d_workspace fixed across calls: a graph replay is keyed by them.    */
+size_t rtm3d_engine_workspace_bytes(rtm3d_ctx* ctx);
+int rtm3d_engine_detect(rtm3d_ctx* ctx, void* stream, const float* d_in, const double* d_K_per_image, float* d_rec,
+                        void* d_workspace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,11 @@ SIGNATURES = {
     'rtm3d_tensor_upload_mx8_raw': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     'rtm3d_op_quant_mx8': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     'rtm3d_op_conv_mx8': (c_int, [c_void_p, ctypes.POINTER(ConvMx8Desc)]),
+    # engine files (rtm3d_amd/engine.py; info: engine.EngineInfo, the mirror of struct rtm3d_engine_info)
+    'rtm3d_engine_inspect': (c_int, [ctypes.c_char_p, c_void_p]),
+    'rtm3d_engine_load': (c_int, [ctypes.c_char_p, c_int, ctypes.POINTER(c_void_p), c_void_p]),
+    'rtm3d_engine_workspace_bytes': (c_size_t, [c_void_p]),
+    'rtm3d_engine_detect': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

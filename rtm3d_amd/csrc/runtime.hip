@@ -98,7 +98,16 @@ struct rtm3d_ctx {
     int n_marks = 0;
     int mark_op[8];
     hipEvent_t mark_ev[9];
+    // state of a context made by rtm3d_engine_load (engine.cpp), released with the context
+    void* engine = nullptr;
+    void (*engine_free)(void*) = nullptr;
 };
+
+void rt_ctx_attach_engine(rtm3d_ctx* ctx, void* engine, void (*engine_free)(void*)) {
+    ctx->engine = engine;
+    ctx->engine_free = engine_free;
+}
+void* rt_ctx_engine(rtm3d_ctx* ctx) { return ctx ? ctx->engine : nullptr; }
 
 static const int PROBE_RING = 64;
 static const int TICKET_SLOTS = 56;
@@ -162,6 +171,7 @@ extern "C" void rtm3d_ctx_destroy(rtm3d_ctx* ctx) {
     for (auto& ge : ctx->graphs) { (void)hipGraphExecDestroy(ge.exec); (void)hipGraphDestroy(ge.graph); }
     if (ctx->capture_stream) (void)hipStreamDestroy(ctx->capture_stream);
     if (ctx->done_ev) (void)hipEventDestroy(ctx->done_ev);
+    if (ctx->engine_free) ctx->engine_free(ctx->engine);
     delete ctx;
 }
 

@@ -460,6 +460,12 @@ class Model(object):
                 'main_kf_logits': logits[0], 'offset_fr_main_logits': logits[1], 'main_offset_logits': logits[2],
                 'vertex_offset_logits': logits[3]}
 
+    def save_engine(self, path, B, H, W, head_precision=None, **kw):
+        """Write the engine file of this model for (B, 3, H, W) batches: rtm3d_amd.engine.save_engine (C callers load it with
+        rtm3d_engine_load and run rtm3d_engine_detect, no Python).  Needs no GPU."""
+        from .engine import save_engine
+        return save_engine(self, path, B, H, W, head_precision=head_precision, **kw)
+
     # ------------------------------------------------------------------ fused device pipeline
     def detect3d(self, x, K_per_image, dim_ref=None, ref_loc=(0.0, -0.5, 20.0), fp32_verify=False, sparse_heads=False, solver_form=None,
                  head_precision=None):
