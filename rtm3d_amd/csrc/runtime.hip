@@ -275,6 +275,7 @@ static int admit_mfma128(rtm3d_ctx* ctx, const rtm3d_conv_desc* d, size_t wbytes
     if (BN != 16 && BN != 32 && BN != 64 && BN != 128) RT_FAIL("op_conv: bn_tile must be 16/32/64/128");
     if (d->cin % 64) RT_FAIL("op_conv(mfma): cin=%d is not a multiple of 64", d->cin);
     if (!d->out_nchw_f32 && (d->cout % BN)) RT_FAIL("op_conv(mfma): cout=%d is not a multiple of the tile %d", d->cout, BN);
+    if (d->out_nchw_f32 && a.res) RT_FAIL("op_conv(mfma): the NCHW fp32 epilogue adds no residual");
     const int cout_pad = (d->cout + BN - 1) / BN * BN;
     a.cpt = d->cin / 64; a.ksteps = d->ntaps * a.cpt;
     a.MT = (a.M + 127) / 128; a.NT = cout_pad / BN;
@@ -455,7 +456,12 @@ extern "C" int rtm3d_op_conv(rtm3d_ctx* ctx, const rtm3d_conv_desc* d) {
             if (oyhi >= out->H || oxhi >= out->W || d->out_oy[g] < 0 || d->out_ox[g] < 0) RT_FAIL("op_conv: output pixel out of range");
             if (out->B != in->B) RT_FAIL("op_conv: batch mismatch");
         } else if (!s2d_only) {
-            if (oyhi >= d->out_H || oxhi >= d->out_W) RT_FAIL("op_conv: NCHW output pixel out of range");
+            if (oyhi >= d->out_H || oxhi >= d->out_W || d->out_oy[g] < 0 || d->out_ox[g] < 0) RT_FAIL("op_conv: NCHW output pixel out of range");
+            // the slot holds cout * groups channels: each group's channels lie inside it, apart from every other group's
+            const int c0 = d->out_coff[g], c1 = c0 + d->cout;
+            if (c0 < 0 || c1 > d->cout * d->groups) RT_FAIL("op_conv: NCHW output channels [%d,%d) of group %d outside the %d channels of the slot", c0, c1, g, d->cout * d->groups);
+            for (int h = 0; h < g; ++h)
+                if (d->out_coff[h] < c1 && c0 < d->out_coff[h] + d->cout) RT_FAIL("op_conv: NCHW output channels of groups %d and %d overlap", h, g);
         }
         if (res) {
             if (!slice_ok(d->res_coff[g], d->cout, res->C)) RT_FAIL("op_conv: residual channel slice out of range");

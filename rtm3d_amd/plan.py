@@ -1310,7 +1310,8 @@ class RealizedPlan(object):
         for g in range(G):
             assert op['inp'][g].tid == op['inp'][0].tid
             d.in_coff[g] = op['inp'][g].coff
-            d.out_coff[g] = op['out'][g].coff if op['out'][g] is not None else 0
+            # (an NCHW output: group g's channels follow group g - 1's in the slot)
+            d.out_coff[g] = op['out'][g].coff if op['out'][g] is not None else (g * op['cout'] if op['out_nchw'] else 0)
             d.res_coff[g] = op['res'][g].coff if op['res'][g] is not None else 0
             d.out_oy[g], d.out_ox[g] = op['out_off'][g]
             for t, (dy, dx) in enumerate(op['taps'][g]):

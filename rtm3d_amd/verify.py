@@ -100,6 +100,7 @@ class VerifyPlanF32(object):
                         d = _lib.VConvDesc()
                         d.inp = self._vt(op['inp'][g])
                         if op['out_nchw']:
+                            assert op['groups'] == 1, 'grouped NCHW output: %s' % op['name']
                             d.out.d = outs[op['out_nchw'] - 1].data_ptr()
                             d.out_nchw_f32, d.out_H, d.out_W = 1, op['out_hw'][0], op['out_hw'][1]
                         else:

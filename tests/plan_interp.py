@@ -60,7 +60,9 @@ def run_plan(plan, x_nchw, half=False, prefill=None, yx=None):
                 if op['relu']:
                     acc = acc.relu()
                 if op['out_nchw']:
-                    outs[op['out_nchw'] - 1] = acc.permute(0, 3, 1, 2).contiguous()
+                    # (group g's channels follow group g - 1's in the slot, as the recorder lays them out)
+                    prev = [outs[op['out_nchw'] - 1]] if g else []
+                    outs[op['out_nchw'] - 1] = torch.cat(prev + [acc.permute(0, 3, 1, 2)], 1).contiguous()
                 else:
                     o = op['out'][g]
                     obuf, Po, Ho, Wo = view(o)

@@ -7,8 +7,6 @@ one list or per-XCD lists, empty lists, the guaranteed run of consecutive tiles 
 reaches).  Then it checks the numbers with the output tensor poisoned: NaN in every output slice (a skipped tile cannot pass), a
 finite sentinel in the channels outside the slices (must be untouched), and a zero border (the next conv reads it as padding),
 read back raw from the device."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -17,47 +15,13 @@ pytestmark = pytest.mark.gpu
 
 from rtm3d_amd import plan as plan_mod, _lib     # noqa: E402
 from tests import conv256_tiles as tl            # noqa: E402
+from tests.conv_harness import SENTINEL, every_pair_order, f16, raw_read, raw_write   # noqa: E402
 
 CUS = 256                       # the tile mirror's CU count (MI355X, SPX: 8 XCDs x 32)
-SENTINEL = np.float16(1234.0)   # channels of an output tensor outside the conv's slices
-H2D, D2H = 1, 2                 # hipMemcpyKind
 
 
 def setup_module():
     assert torch.cuda.get_device_properties(0).multi_processor_count == CUS, 'the tile mirror assumes %d CUs' % CUS
-
-
-def _hip_memcpy(lib, dst, src, nbytes, kind):
-    # (the HIP runtime librtm3d_hip.so itself links: its handle resolves the symbols of its dependencies)
-    f = lib.hipMemcpy
-    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    assert f(dst, src, nbytes, kind) == 0, 'hipMemcpy failed'
-
-
-def _raw(R, s):
-    """(device address, padded shape (B, Hp, Wp, C), border) of the tensor Slice s lives in."""
-    base, B, H, W, C, P = R.tensor_info(s)
-    return base, (B, H + 2 * P, W + 2 * P, C), P
-
-
-def raw_read(R, s):
-    base, shape, _ = _raw(R, s)
-    out = np.empty(shape, np.float16)
-    torch.cuda.synchronize()
-    _hip_memcpy(R.lib, out.ctypes.data, base, out.nbytes, D2H)
-    return out
-
-
-def raw_write(R, s, img):
-    base, shape, _ = _raw(R, s)
-    img = np.ascontiguousarray(img, np.float16)
-    assert img.shape == shape, (img.shape, shape)
-    torch.cuda.synchronize()
-    _hip_memcpy(R.lib, base, img.ctypes.data, img.nbytes, H2D)
-
-
-def f16(a):
-    return np.asarray(a, np.float32).astype(np.float16)
 
 
 def spec(route, B, H, W, cin, cout, kind='conv', k=3, dil=1, groups=1, relu=True, res=False, in_P=None, out_P=1, in_extra=0,
@@ -293,23 +257,9 @@ CHAIN = {
 }
 
 
-def _every_pair_order(n):
-    """A sequence over 0..n-1 in which every ordered pair (a, b), a != b, appears as neighbours: an Euler circuit of the
-    complete directed graph (Hierholzer)."""
-    succ = {a: [b for b in range(n) if b != a] for a in range(n)}
-    stack, seq = [0], []
-    while stack:
-        v = stack[-1]
-        if succ[v]:
-            stack.append(succ[v].pop())
-        else:
-            seq.append(stack.pop())
-    return seq[::-1]
-
-
 def test_conv256_counter_chain():
     keys = list(CHAIN)
-    order = _every_pair_order(len(keys))
+    order = every_pair_order(len(keys))
     pairs = {(a, b) for a, b in zip(order, order[1:])}
     assert len(order) == len(keys) * (len(keys) - 1) + 1 and len(pairs) == len(keys) * (len(keys) - 1)
     for sp in CHAIN.values():

@@ -37,15 +37,15 @@ def h(t):
 
 CONV_CASES = [
     # B, H, W, cin, cout, k, stride, dil, relu, residual, variant, in_extra_ch
-    (2, 24, 40, 64, 64, 3, 1, 1, True, True, _lib.CONV_MFMA128, 0),         # v1 BN=64, residual
-    (1, 13, 21, 128, 128, 3, 1, 1, True, False, _lib.CONV_MFMA128, 64),     # ragged M (273 px), input slice of a wider tensor
-    (2, 16, 24, 64, 128, 3, 2, 1, False, False, _lib.CONV_MFMA128, 0),      # stride 2
-    (1, 12, 20, 256, 64, 1, 1, 1, True, False, _lib.CONV_MFMA128, 0),       # 1x1
-    (1, 20, 36, 64, 256, 3, 1, 6, True, False, _lib.CONV_MFMA128, 0),       # dilation 6 (head conv)
-    (4, 96, 160, 64, 128, 3, 1, 1, True, True, _lib.CONV_MFMA128, 0),       # v1 on a full-chip launch (480 tiles: the one-stage-in-flight kernel)
+    (2, 24, 40, 64, 64, 3, 1, 1, True, True, _lib.CONV_MFMA128, 0),         # BN=64, residual: deep split-K (15 tiles, 9 K-steps in 2 ranges)
+    (1, 13, 21, 128, 128, 3, 1, 1, True, False, _lib.CONV_MFMA128, 64),     # ragged M (273 px), input slice of a wider tensor: deep split-K, 4 ranges
+    (2, 16, 24, 64, 128, 3, 2, 1, False, False, _lib.CONV_MFMA128, 0),      # stride 2: deep split-K, 2 ranges
+    (1, 12, 20, 256, 64, 1, 1, 1, True, False, _lib.CONV_MFMA128, 0),       # 1x1: deep ring, 4 K-steps (too few to split)
+    (1, 20, 36, 64, 256, 3, 1, 6, True, False, _lib.CONV_MFMA128, 0),       # dilation 6 (head conv): deep split-K, 2 ranges
+    (4, 96, 160, 64, 128, 3, 1, 1, True, True, _lib.CONV_MFMA128, 0),       # BN=128 on a full-chip launch (480 tiles: the one-stage-in-flight kernel)
     (1, 12, 40, 512, 512, 3, 1, 1, True, True, _lib.CONV_MFMA128, 0),       # deep ring + split-K (32 tiles, 72 K-steps in 8 ranges), residual
     (1, 12, 40, 512, 256, 1, 1, 1, False, False, _lib.CONV_MFMA128, 64),    # deep ring + split-K of a 1x1 (8 K-steps in 2 ranges)
-    (2, 13, 21, 256, 128, 3, 1, 1, True, False, _lib.CONV_MFMA128, 0),      # deep ring + split-K, ragged M (546 px = 4.27 tiles)
+    (2, 13, 21, 256, 128, 3, 1, 1, True, False, _lib.CONV_MFMA128, 0),      # deep ring + split-K, ragged M (546 px = 4.27 tiles; 36 K-steps in 9 ranges)
     (3, 24, 40, 64, 256, 3, 1, 1, True, True, _lib.CONV_MFMA256, 0),        # mfma256, ragged M (2880 = 11.25 tiles), residual
     (1, 16, 20, 128, 512, 3, 1, 6, False, False, _lib.CONV_MFMA256, 0),     # mfma256 persistent, NT=2, M=320: 4 tiles from one list
     (3, 24, 40, 64, 256, 3, 1, 1, True, False, _lib.CONV_MFMA256, 0),       # mfma256 persistent, ragged M (11.25 tiles), 9 K-tiles
@@ -71,9 +71,18 @@ CONV_CASES = [
 ]
 
 
+# the op name (route) each 128-pixel and halo case of CONV_CASES records, in order (the conv256 and smallc cases: None)
+_D, _S = 'conv3x3_mfma_deep', 'conv3x3_mfma_deep_splitk'
+CONV_ROUTE_NAMES = [_S, _S, _S, 'conv1x1_mfma_deep', _S, 'conv3x3_mfma', _S, 'conv1x1_mfma_deep_splitk', _S] + [None] * 5 + \
+    ['conv3x3_c64_halo'] * 4 + ['conv3x3_c128_halo'] * 5 + ['conv3x3s2_c64_halo'] * 4 + [None] * 4
+assert len(CONV_ROUTE_NAMES) == len(CONV_CASES)
+
+
 @pytest.mark.parametrize('case', CONV_CASES)
 def test_conv_kernels_vs_torch(case):
     B, H, W, cin, cout, k, stride, dil, relu, use_res, variant, extra = case
+    route = CONV_ROUTE_NAMES[CONV_CASES.index(case)]
+    assert (route is None) == (variant in (_lib.CONV_MFMA256, _lib.CONV_SMALLC)), case
     rng = np.random.default_rng(hash(case) % (2 ** 32))
     pad = dil * (k - 1) // 2
     P = plan_mod.Plan(B, H * 4, W * 4)
@@ -92,7 +101,7 @@ def test_conv_kernels_vs_torch(case):
     if use_res:
         r = rng.standard_normal((B, cout, Ho, Wo)).astype(np.float32)
         feeds.append((rs, r))
-    (got,), _ = _run(P, feeds, [ys])
+    (got,), _ = _run(P, feeds, [ys], expect_kernels=[route] if route else None)
     ref = F.conv2d(h(torch.from_numpy(x)), h(torch.from_numpy(w)), torch.from_numpy(b), stride, pad, dil)
     if use_res:
         ref = ref + h(torch.from_numpy(r))
