@@ -741,6 +741,9 @@ extern "C" int rtm3d_op_conv32s2_fused(rtm3d_ctx* ctx, int in_tensor, int in_cof
     for (Tensor* o : {oc, op_})
         if (o->H * 2 != x->H || o->W * 2 != x->W || o->B != x->B) RT_FAIL("op_conv32s2_fused: outputs must have half the input resolution");
     if (!slice_ok(conv_coff, 64, oc->C) || !slice_ok(proj_coff, 64, op_->C)) RT_FAIL("op_conv32s2_fused: output slice mismatch");
+    // the two outputs may be slices of ONE tensor: different lanes of one launch write them, so their channel ranges must not meet
+    if (oc == op_ && conv_coff < proj_coff + 64 && proj_coff < conv_coff + 64)
+        RT_FAIL("op_conv32s2_fused: the conv slice [%d,%d) overlaps the project slice [%d,%d) of the same tensor", conv_coff, conv_coff + 64, proj_coff, proj_coff + 64);
     size_t wc = 0, bc = 0, wp = 0, bp = 0;
     const f16* w0 = (const f16*)get_blob(ctx, w_conv_blob, &wc);
     const float* b0 = (const float*)get_blob(ctx, b_conv_blob, &bc);

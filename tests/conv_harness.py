@@ -1,5 +1,6 @@
-"""Helpers shared by the route-level conv suites (tests/test_gpu_conv256.py, tests/test_gpu_conv128.py): raw reads and writes of
-a plan tensor's whole padded device image, and the launch order that puts every ordered pair of regimes next to each other."""
+"""Helpers shared by the route-level suites (tests/test_gpu_conv256.py, tests/test_gpu_conv128.py, tests/test_gpu_fused.py): raw
+reads and writes of a plan tensor's whole padded device image, and the launch order that puts every ordered pair of regimes next
+to each other."""
 import ctypes
 
 import numpy as np
