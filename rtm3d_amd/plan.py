@@ -131,6 +131,9 @@ class Plan(object):
                          'bias': np.zeros((4, cout), np.float32), 'out_nchw': 0, 'out_hw': (2 * Hi, 2 * Wi)})
 
     def maxpool(self, inp, out, k, stride, pad, name=''):
+        """k x k max-pool.  A window that reaches over the map's edge reads the input tensor's zero border: the result is the
+        max over the window of the ZERO-padded input, which equals PyTorch's max_pool2d (-inf padding) only on non-negative
+        input, such as the post-ReLU maps the networks pool."""
         assert inp.C == out.C
         self.ops.append({'op': 'maxpool', 'name': name, 'inp': inp, 'out': out, 'k': k, 'stride': stride, 'pad': pad})
 
