@@ -1,10 +1,9 @@
-// 3D box decode on device: the fp64 L-BFGS-B of lbfgsb.h, one wavefront per object - lbfgsb_wave_pub.h, the published subspace
-// step SciPy runs (the default since round 6), or lbfgsb_wave.h, the direct two-loop search direction (opt-in) - or one lane per
-// object (the cross-check kernels of the two forms, bit-identical to the wave kernels).
+// 3D box decode on device: the fp64 L-BFGS-B of lbfgsb.h, one wavefront per object - the driver of lbfgsb_wave.h with the published
+// subspace step SciPy runs (lbfgsb_wave_pub.h, the default since round 6) or with the direct two-loop search direction (opt-in) -
+// or one lane per object (the cross-check kernels of the two forms, bit-identical to the wave kernels).
 // Replaces optim_decode_bbox3d (utils/model_utils.py:264-312) + scipy L-BFGS-B.
 // The work is latency-bound fp64 (a few hundred kFLOP per object, <= topk objects per image), so the
 // kernel only needs enough lanes in flight: 64-lane workgroups, objects spread over the CUs.
-#include <type_traits>
 #include "common.h"
 #include "lbfgsb.h"
 #include "lbfgsb_wave.h"
@@ -76,8 +75,8 @@ __global__ __launch_bounds__(64) void decode3d_kernel(int N, const int64_t* __re
 #ifndef D3_WPB_PUB
 #define D3_WPB_PUB 8
 #endif
-// FORM 0: the direct form (two-loop search direction, lbfgsb_wave.h), opt-in;
-// FORM 1: the published subspace step (lbfgsb_wave_pub.h: what SciPy runs), the default of every entry since round 6:
+// FORM (= RTM3D_SOLVER_*).  0: the direct form (two-loop search direction, lbfgsb_wave.h), opt-in;
+// 1: the published subspace step (lbfgsb_wave_pub.h: what SciPy runs), the default of every entry since round 6:
 // 8.4 KB of LDS per object, i.e. 67 KB per workgroup of eight.
 template <int D3_WPB, int FORM>
 __global__ __launch_bounds__(64 * D3_WPB) void decode3d_wave_kernel(int N, const int64_t* __restrict__ cls,
@@ -87,16 +86,14 @@ __global__ __launch_bounds__(64 * D3_WPB) void decode3d_wave_kernel(int N, const
                                                            double* __restrict__ f_out, int32_t* __restrict__ nit,
                                                            int32_t* __restrict__ status,
                                                            const int32_t* __restrict__ n_per_image, int topk) {
-    using Mem = typename std::conditional<FORM == 1, lbw_pub::LbWaveMem, LbWaveMem>::type;
-    using KK = typename std::conditional<FORM == 1, lbw_pub::LbWaveK, LbWaveK>::type;
-    __shared__ Mem mems[D3_WPB];
+    __shared__ LbwMem<FORM> mems[D3_WPB];
     // These waves are latency chains that issue an instruction every few hundred cycles; beside the MFMA / DMA
     // waves of the next batch's convolutions they lose every arbitration at equal priority and the kernel stretches
     // from 1.3 ms to ~5 ms, into the persistent conv kernels that need whole CUs.  Highest wave priority: the
     // chains run at their own pace, the co-resident conv waves give up a few issue slots.
     __builtin_amdgcn_s_setprio(3);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    Mem& mem = mems[wave];
+    LbwMem<FORM>& mem = mems[wave];
     const int i = blockIdx.x * D3_WPB + wave;
     if (i >= N) return;
     int ki = i;
@@ -104,7 +101,7 @@ __global__ __launch_bounds__(64 * D3_WPB) void decode3d_wave_kernel(int N, const
         ki = i / topk;
         if (i - ki * topk >= n_per_image[ki]) { if (lane == 0) status[i] = -1; return; }
     }
-    KK Kk;
+    LbWaveK Kk;
     Kk.k00 = K[ki * 9 + 0]; Kk.k02 = K[ki * 9 + 2]; Kk.k11 = K[ki * 9 + 4]; Kk.k12 = K[ki * 9 + 5];
     int c = (int)cls[i];
     c = c < 0 ? 0 : (c >= ncls ? ncls - 1 : c);
@@ -117,9 +114,7 @@ __global__ __launch_bounds__(64 * D3_WPB) void decode3d_wave_kernel(int N, const
     WSYNC();
     double f;
     int it;
-    int st;
-    if constexpr (FORM == 1) st = lbw_pub::lbw_minimize(&mem, Kk, &f, &it, lane, 15000, 15000);
-    else st = lbw_minimize(&mem, Kk, &f, &it, lane, 15000, 15000);
+    const int st = lbw_minimize(&mem, Kk, &f, &it, lane, 15000, 15000);
     WSYNC();
     if (lane < 8) x_out[(size_t)i * 8 + lane] = mem.x[lane];
     if (lane == 0) { f_out[i] = f; nit[i] = it; status[i] = st; }
@@ -127,25 +122,32 @@ __global__ __launch_bounds__(64 * D3_WPB) void decode3d_wave_kernel(int N, const
 
 extern void rt_set_error(const char* fmt, ...);
 
-#define D3_LAUNCH(...) hipLaunchKernelGGL((decode3d_wave_kernel<D3_WPB_DEFAULT, 0>), dim3((N + D3_WPB_DEFAULT - 1) / D3_WPB_DEFAULT), \
-                                          dim3(64 * D3_WPB_DEFAULT), 0, (hipStream_t)stream, __VA_ARGS__)
-#define D3_LAUNCH_PUB(...) hipLaunchKernelGGL((decode3d_wave_kernel<D3_WPB_PUB, 1>), dim3((N + D3_WPB_PUB - 1) / D3_WPB_PUB), \
-                                              dim3(64 * D3_WPB_PUB), 0, (hipStream_t)stream, __VA_ARGS__)
+// Both wave entries: checks and launch of the wave kernel of `form` on N objects.  topk > 0 is slot mode (N = images * topk, d_n the
+// objects per image); `what` is the entry's name in the error texts.
+static int launch_wave(const char* what, int form, void* stream, int N, const int32_t* d_n, int topk, const int64_t* d_cls,
+                       const float* d_verts, const double* d_K, const double* d_dim_ref, int ncls, const double* d_ref_loc,
+                       double* d_x, double* d_fun, int32_t* d_nit, int32_t* d_status) {
+    if (form != RTM3D_SOLVER_DIRECT && form != RTM3D_SOLVER_PUBLISHED) { rt_set_error("%s: unknown solver form %d (0 = direct two-loop direction, 1 = published subspace step)", what, form); return 1; }
+    if (N == 0) return 0;
+    if ((topk > 0 && !d_n) || !d_cls || !d_verts || !d_K || !d_dim_ref || !d_ref_loc || !d_x || !d_fun || !d_nit || !d_status) {
+        rt_set_error("%s: null pointer", what); return 1;
+    }
+    if (form == RTM3D_SOLVER_PUBLISHED)
+        hipLaunchKernelGGL((decode3d_wave_kernel<D3_WPB_PUB, RTM3D_SOLVER_PUBLISHED>), dim3((N + D3_WPB_PUB - 1) / D3_WPB_PUB), dim3(64 * D3_WPB_PUB), 0, (hipStream_t)stream,
+                           N, d_cls, d_verts, d_K, d_dim_ref, ncls, d_ref_loc, d_x, d_fun, d_nit, d_status, d_n, topk);
+    else
+        hipLaunchKernelGGL((decode3d_wave_kernel<D3_WPB_DEFAULT, RTM3D_SOLVER_DIRECT>), dim3((N + D3_WPB_DEFAULT - 1) / D3_WPB_DEFAULT), dim3(64 * D3_WPB_DEFAULT), 0, (hipStream_t)stream,
+                           N, d_cls, d_verts, d_K, d_dim_ref, ncls, d_ref_loc, d_x, d_fun, d_nit, d_status, d_n, topk);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { rt_set_error("%s launch: %s", what, hipGetErrorString(e)); return 1; }
+    return 0;
+}
 
 extern "C" int rtm3d_decode3d(void* stream, int N, const int64_t* d_cls, const float* d_verts, const double* d_K,
                               const double* d_dim_ref, int ncls, const double* d_ref_loc, double* d_x,
                               double* d_fun, int32_t* d_nit, int32_t* d_status, int form) {
     if (N < 0 || ncls <= 0) { rt_set_error("decode3d: bad sizes"); return 1; }
-    if (form != RTM3D_SOLVER_DIRECT && form != RTM3D_SOLVER_PUBLISHED) { rt_set_error("decode3d: unknown solver form %d (0 = direct two-loop direction, 1 = published subspace step)", form); return 1; }
-    if (N == 0) return 0;
-    if (!d_cls || !d_verts || !d_K || !d_dim_ref || !d_ref_loc || !d_x || !d_fun || !d_nit || !d_status) {
-        rt_set_error("decode3d: null pointer"); return 1;
-    }
-    if (form == RTM3D_SOLVER_PUBLISHED) D3_LAUNCH_PUB(N, d_cls, d_verts, d_K, d_dim_ref, ncls, d_ref_loc, d_x, d_fun, d_nit, d_status, (const int32_t*)nullptr, 0);
-    else D3_LAUNCH(N, d_cls, d_verts, d_K, d_dim_ref, ncls, d_ref_loc, d_x, d_fun, d_nit, d_status, (const int32_t*)nullptr, 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("decode3d launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return launch_wave("decode3d", form, stream, N, nullptr, 0, d_cls, d_verts, d_K, d_dim_ref, ncls, d_ref_loc, d_x, d_fun, d_nit, d_status);
 }
 
 extern "C" int rtm3d_decode3d_slots(void* stream, int B, int topk, const int32_t* d_n, const int64_t* d_cls,
@@ -153,16 +155,7 @@ extern "C" int rtm3d_decode3d_slots(void* stream, int B, int topk, const int32_t
                                     const double* d_ref_loc, double* d_x, double* d_fun, int32_t* d_nit,
                                     int32_t* d_status, int form) {
     if (B <= 0 || topk <= 0 || ncls <= 0) { rt_set_error("decode3d_slots: bad sizes"); return 1; }
-    if (form != RTM3D_SOLVER_DIRECT && form != RTM3D_SOLVER_PUBLISHED) { rt_set_error("decode3d_slots: unknown solver form %d (0 = direct two-loop direction, 1 = published subspace step)", form); return 1; }
-    if (!d_n || !d_cls || !d_verts || !d_K_per_image || !d_dim_ref || !d_ref_loc || !d_x || !d_fun || !d_nit || !d_status) {
-        rt_set_error("decode3d_slots: null pointer"); return 1;
-    }
-    const int N = B * topk;
-    if (form == RTM3D_SOLVER_PUBLISHED) D3_LAUNCH_PUB(N, d_cls, d_verts, d_K_per_image, d_dim_ref, ncls, d_ref_loc, d_x, d_fun, d_nit, d_status, d_n, topk);
-    else D3_LAUNCH(N, d_cls, d_verts, d_K_per_image, d_dim_ref, ncls, d_ref_loc, d_x, d_fun, d_nit, d_status, d_n, topk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("decode3d_slots launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return launch_wave("decode3d_slots", form, stream, B * topk, d_n, topk, d_cls, d_verts, d_K_per_image, d_dim_ref, ncls, d_ref_loc, d_x, d_fun, d_nit, d_status);
 }
 
 // Same problem on the one-lane-per-object kernels (scalar lbfgsb.h): cross-checks of the wave kernel.

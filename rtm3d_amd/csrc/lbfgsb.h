@@ -16,7 +16,7 @@
 //
 // Two forms of the search direction (argument `direct` of lb_minimize):
 //   direct = 0  the published subspace step (formk / subsm, and formt as the positive-definiteness check): the form
-//               SciPy runs and, since round 6, the product's DEFAULT (wave kernel: lbfgsb_wave_pub.h; this scalar form is its
+//               SciPy runs and, since round 6, the product's DEFAULT (wave kernel: lbfgsb_wave.h + lbfgsb_wave_pub.h; this scalar form is its
 //               cross-check, rtm3d_decode3d_reference_form, tests/host_lbfgsb.cpp);
 //   direct = 1  the opt-in form: the same vector  -B^-1 g  from the two-loop recursion over the same stored pairs
 //               (lb_two_loop).  Without bounds the two are equal in exact arithmetic; in fp64 the iterates differ in the

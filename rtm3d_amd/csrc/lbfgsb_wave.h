@@ -1,19 +1,21 @@
-// Wave-cooperative form of lbfgsb.h in its DIRECT form (lb_minimize with direct = 1; the product's default in rounds 3-5, opt-in
-// since round 6: lbfgsb_wave_pub.h is the default): ONE 64-lane wavefront solves ONE object.
+// Wave-cooperative form of lbfgsb.h: ONE 64-lane wavefront solves ONE object.  This file holds what the two forms of the search
+// direction share - the objective, the ring of stored pairs, and the ONE iteration driver lbw_minimize<FORM> (lb_minimize of
+// lbfgsb.h; the form is a template argument here where it is the argument `direct` there) - and the parts of the DIRECT form
+// (FORM = LBW_DIRECT: lb_minimize with direct = 1; the product's default in rounds 3-5, opt-in since round 6).  The parts of the
+// published form, the default, are in lbfgsb_wave_pub.h; what a form changes in an iteration are the `if constexpr` arms of the driver.
 //
 // Same algorithm and the same fp64 arithmetic in the same order as the scalar version - every individual sum runs
 // sequentially in index order - so the two are bit-identical (tests: rtm3d_decode3d vs rtm3d_decode3d_scalar):
 //   - the 64 (corner, unknown) terms of the gradient and the 16 terms of the objective are spread over the lanes;
-//   - the search direction comes from the two-loop recursion over the stored pairs (lb_two_loop): every lane runs the whole
-//     recursion redundantly on the same LDS operands (broadcast reads), so its 2 * col dependent steps need no cross-lane
-//     traffic at all; only lanes 0..7 store the result;
+//   - the search direction of the direct form comes from the two-loop recursion over the stored pairs (lb_two_loop): every lane
+//     runs the whole recursion redundantly on the same LDS operands (broadcast reads), so its 2 * col dependent steps need no
+//     cross-lane traffic at all; only lanes 0..7 store the result;
 //   - scalar control (line search state, convergence tests) is computed redundantly by every lane, so control flow stays
 //     wave-uniform.
 // History: up to round 2 this file carried the published subspace step (formk / subsm / formt: 20 x 20 LEL' factorisation
 // spread over the lanes, 8.4 KB of LDS and 178 VGPRs per object, 35.7k cycles per iteration of which 24k in those three).
 // Without bounds that step is  -B^-1 g, which the two-loop recursion delivers from the same pairs in ~3k cycles; measured
-// against the reference's SciPy results the direct form is as close as the published one (lbfgsb.h, header).  The
-// published form lives on in lbfgsb.h (direct = 0) as the cross-check.
+// against the reference's SciPy results the direct form is as close as the published one (lbfgsb.h, header).
 // A wave's LDS instructions execute in order, so WSYNC() is only a compiler/LDS ordering fence at
 // wavefront scope (no s_barrier): a workgroup may hold several independent objects, one per wave.
 #pragma once
@@ -24,8 +26,10 @@
 
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
-// -DLBW_PROF=1 (diagnostic build only, tools/prof_lbw.sh): per-phase cycle sums (s_memtime) in LDS; at the end the first
-// eight replace the solution in w->x, where tools/prof_lbw.py reads them
+// -DLBW_PROF=1|2|3 (diagnostic build only, tools/prof_lbw.sh): per-phase cycle sums (s_memtime) in LDS, 24 slots; at the end
+// eight of them (LBW_PROF = 1, 2, 3: slots 0-7, 8-15, 16-23) replace the solution in w->x, where tools/prof_lbw.py reads them.
+// Slots 0-7 are the driver's and mean the same in both forms: 0 direction, 2 line search, of which 4 f + g and 5 dcsrch, 3 matupd,
+// 7 total; the published form's own: 1 subsm, 6 formt, 15 formk, 8-14 inside formk, 16-17 inside subsm.
 #ifdef LBW_PROF
 #define PTB(name) const long long name = __builtin_readcyclecounter()
 #define PTE(name, k) do { if (lane == 0) w->prof[k] += __builtin_readcyclecounter() - name; } while (0)
@@ -34,14 +38,18 @@
 #define PTE(name, k)
 #endif
 
-struct LbWaveMem {
+enum { LBW_DIRECT = 0, LBW_PUBLISHED = 1 };      // FORM (the values of RTM3D_SOLVER_*)
+
+// LDS of one object.  Both forms have ws, wy, the vectors x z r d t g, terms, fterms and uv: the shared code touches only those.
+template <int FORM> struct LbwMem;
+template <> struct LbwMem<LBW_DIRECT> {
     double ws[LB_N * LB_M], wy[LB_N * LB_M];      // S and Y, one pair per ring slot (column)
     double rho[LB_M];                             // 1 / (s'y) per ring slot
     double x[LB_N], z[LB_N], r[LB_N], d[LB_N], t[LB_N], g[LB_N];
     double terms[64], fterms[16];
     double uv[16];
 #ifdef LBW_PROF
-    long long prof[8];
+    long long prof[24];
 #endif
 };
 #define VWS_(i, j) w->ws[((j)-1) * LB_N + (i)-1]
@@ -50,7 +58,8 @@ struct LbWaveMem {
 struct LbWaveK { double k00, k02, k11, k12; };
 
 // f (returned, identical in every lane) and g (-> w->g) at w->x.
-__device__ static inline double lbw_fg(LbWaveMem* w, const LbWaveK& K, int lane) {
+template <int FORM>
+__device__ static inline double lbw_fg(LbwMem<FORM>* w, const LbWaveK& K, int lane) {
     const int c = lane >> 3, i = lane & 7;
     double c0, c1, c2;
     lb_corner(c, &c0, &c1, &c2);
@@ -100,12 +109,41 @@ __device__ static inline double lbw_dot8(const double* a, const double* b) {
     return s;
 }
 
+// A wave-uniform double (every lane computed the same bits from LDS broadcasts) handed to the compiler AS uniform: it may then live
+// in an SGPR pair - or, under pressure, in two lanes of a spill VGPR (v_writelane / v_readlane: a few cycles) - instead of two
+// VGPRs of every lane.  The loop-carried scalars of lbw_minimize (f, theta, the camera constants) are live across formk / subsm, whose
+// unrolled factorisations want every vector register: at the 168-register budget of twelve waves per workgroup they were the values
+// the allocator sent to scratch memory (a global-memory round trip inside a latency chain).  Same bits in, same bits out.
+// The direct form has no such pressure and passes the value through.
+template <int FORM>
+__device__ static inline double lbw_uni(double v) {
+    if constexpr (FORM == LBW_DIRECT) return v;
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    return __hiloint2double(hi, lo);
+}
+
+// Head of lb_matupd in both forms: the ring pointers, and the new pair (d, r) into its slot
+template <int FORM>
+__device__ static inline void lbw_push_pair(LbwMem<FORM>* w, int* itail, int iupdat, int* col, int* head, int lane) {
+    const int m = LB_M, n = LB_N;
+    {   // (value selection, not stores through col / head per branch: see lb_dcstep)
+        const bool grow = iupdat <= m;
+        const int col0 = *col, head0 = *head, itail0 = *itail;
+        *col = grow ? iupdat : col0;
+        *itail = grow ? (head0 + iupdat - 2) % m + 1 : itail0 % m + 1;
+        *head = grow ? head0 : head0 % m + 1;
+    }
+    if (lane < n) { VWS_(lane + 1, *itail) = w->d[lane]; VWY_(lane + 1, *itail) = w->r[lane]; }
+}
+
 // z = x - H g by the two-loop recursion (lb_two_loop, same operations in the same order), run redundantly by every lane:
 // q and alpha live in registers, the pairs are read from LDS at wave-uniform addresses.  The recursion is ONE dependent
 // chain of 2 * col steps (eight products, three tree additions, scale, multiply, subtract), ~360 cycles each: 7.2k cycles
 // per iteration.  (Measured and not kept: fetching the operands of step k + 1 during step k from two alternating register
 // buffers - 7.5k cycles: the chain waits for arithmetic, not for LDS; with the next operands copied into place 9.0k.)
-__device__ static inline void lbw_two_loop(LbWaveMem* w, double theta, int col, int head, int lane) {
+__device__ static inline void lbw_two_loop(LbwMem<LBW_DIRECT>* w, double theta, int col, int head, int lane) {
     const int m = LB_M, n = LB_N;
     double q[LB_N], alpha[LB_M];
 #pragma unroll
@@ -152,40 +190,41 @@ __device__ static inline void lbw_two_loop(LbWaveMem* w, double theta, int col, 
     WSYNC();
 }
 
-// lb_matupd for the direct form: ring pointers, the new pair, rho of its slot, theta (S'S, S'Y are not needed)
-__device__ static inline void lbw_matupd(LbWaveMem* w, int* itail, int iupdat, int* col, int* head, double* theta,
-                                         double rr, double dr, int lane) {
-    const int m = LB_M, n = LB_N;
-    {   // (value selection, not stores through col / head per branch: see lb_dcstep)
-        const bool grow = iupdat <= m;
-        const int col0 = *col, head0 = *head, itail0 = *itail;
-        *col = grow ? iupdat : col0;
-        *itail = grow ? (head0 + iupdat - 2) % m + 1 : itail0 % m + 1;
-        *head = grow ? head0 : head0 % m + 1;
-    }
-    if (lane < n) { VWS_(lane + 1, *itail) = w->d[lane]; VWY_(lane + 1, *itail) = w->r[lane]; }
+// lb_matupd for the direct form: ring pointers, the new pair, rho of its slot, theta (S'S, S'Y, i.e. stp and dtd, are not needed)
+__device__ static inline void lbw_matupd(LbwMem<LBW_DIRECT>* w, int* itail, int iupdat, int* col, int* head, double* theta,
+                                         double rr, double dr, double stp, double dtd, int lane) {
+    (void)stp; (void)dtd;
+    lbw_push_pair(w, itail, iupdat, col, head, lane);
     if (lane == 0) w->rho[*itail - 1] = 1.0 / dr;
     *theta = rr / dr;
     WSYNC();
 }
 
-// Driver: identical control flow to lb_minimize(direct = 1) (lbfgsb.h).  w->x holds x0 on entry, the result on exit.
-__device__ static inline int lbw_minimize(LbWaveMem* w, const LbWaveK& K, double* f_out, int* nit_out, int lane,
+// Driver: identical control flow to lb_minimize (lbfgsb.h).  w->x holds x0 on entry, the result on exit.
+// The published form's lbw_formk / lbw_subsm / lbw_matupd / lbw_formt (lbfgsb_wave_pub.h) are looked up when FORM = LBW_PUBLISHED
+// is instantiated: a translation unit that does so includes that header.
+// (Measured and not kept, both against the listing of the two hand-kept drivers this one replaced, which it reproduces instruction
+// for instruction: formk + subsm behind one per-form function - the inliner then simplifies the two together before the driver sees
+// them and the published kernel comes out 15 instructions longer with other register assignments; the three places that drop the
+// pairs as a lambda capturing the loop's scalars - both kernels change.  Hence `if constexpr` arms and a macro.)
+#define LBW_DROP_PAIRS() do { col = 0; head = 1; theta = 1.0; iupdat = 0; updatd = 0; } while (0)
+template <int FORM>
+__device__ static inline int lbw_minimize(LbwMem<FORM>* w, const LbWaveK& K, double* f_out, int* nit_out, int lane,
                                           int maxiter, int maxfun) {
     const int n = LB_N, maxls = 20;
     const double epsmch = 2.220446049250313e-16, factr = 1e7, pgtol = 1e-5;
     const double ftol = 1e-3, gtol = 0.9, xtol = 0.1, big = 1e10;
     const double tol = factr * epsmch;
-    int col = 0, head = 1, itail = 0, iupdat = 0, iter = 0, nfgv = 0, info;
+    int col = 0, head = 1, itail = 0, iupdat = 0, updatd = 0, iter = 0, nfgv = 0, info;       // (updatd: formk is due; published form)
     double theta = 1.0, f, fold = 0.0, gd = 0.0, gdold = 0.0, stp = 0.0, dnorm = 0.0, dtd = 0.0, sbgnrm;
     LbSearch S;
 
 #ifdef LBW_PROF
-    if (lane < 8) w->prof[lane] = 0;
+    if (lane < 24) w->prof[lane] = 0;
     WSYNC();
     const long long tstart_ = __builtin_readcyclecounter();
 #endif
-    f = lbw_fg(w, K, lane); nfgv = 1;
+    f = lbw_uni<FORM>(lbw_fg(w, K, lane)); nfgv = 1;
     {   // non-finite key points: x0, fun = NaN / Inf, 0 iterations, own status (see lb_minimize)
         bool finite = lb_isfinite(f);
         for (int i = 0; i < n; ++i) finite = finite && lb_isfinite(w->g[i]);
@@ -200,8 +239,22 @@ __device__ static inline int lbw_minimize(LbWaveMem* w, const LbWaveK& K, double
         if (col == 0) {
             if (lane < n) w->z[lane] = w->x[lane] + 1.0 * (-w->g[lane]);
             WSYNC();
-        } else {
+        } else if constexpr (FORM == LBW_DIRECT) {
             lbw_two_loop(w, theta, col, head, lane);
+        } else {
+            if (lane < n) { w->z[lane] = w->x[lane]; w->r[lane] = -w->g[lane]; }
+            WSYNC();
+            info = 0;
+            PTB(tk_);
+            if (updatd) info = lbw_formk(w, iupdat, theta, col, head, lane);
+            PTE(tk_, 15); PTB(ts_);
+            if (info == 0) info = lbw_subsm(w, theta, col, head, lane);
+            PTE(ts_, 1);
+            if (info != 0) {
+                LBW_DROP_PAIRS();
+                WSYNC();
+                continue;
+            }
         }
         PTE(td_, 0);
         if (lane < n) { w->d[lane] = w->z[lane] - w->x[lane]; w->t[lane] = w->x[lane]; w->r[lane] = w->g[lane]; }
@@ -232,7 +285,7 @@ __device__ static inline int lbw_minimize(LbWaveMem* w, const LbWaveK& K, double
             WSYNC();
             if (iback >= maxls) { ls_fail = 1; break; }
             PTB(tf_);
-            f = lbw_fg(w, K, lane);
+            f = lbw_uni<FORM>(lbw_fg(w, K, lane));
             PTE(tf_, 4);
         }
         PTE(tl_, 2);
@@ -242,7 +295,7 @@ __device__ static inline int lbw_minimize(LbWaveMem* w, const LbWaveK& K, double
             WSYNC();
             f = fold;
             if (col == 0) { *f_out = f; *nit_out = iter; return 2; }
-            col = 0; head = 1; theta = 1.0; iupdat = 0;
+            LBW_DROP_PAIRS();
             continue;
         }
         iter += 1;
@@ -265,20 +318,27 @@ __device__ static inline int lbw_minimize(LbWaveMem* w, const LbWaveK& K, double
             WSYNC();
             ddum = -gdold * stp;
         }
-        if (dr <= epsmch * ddum) continue;
-        iupdat += 1;
+        if (dr <= epsmch * ddum) { updatd = 0; continue; }
+        updatd = 1; iupdat += 1;
         PTB(tm_);
-        lbw_matupd(w, &itail, iupdat, &col, &head, &theta, rr, dr, lane);
+        lbw_matupd(w, &itail, iupdat, &col, &head, &theta, rr, dr, stp, dtd, lane);
         PTE(tm_, 3);
+        if constexpr (FORM == LBW_PUBLISHED) {
+            theta = lbw_uni<FORM>(theta);
+            PTB(tt_);
+            if (lbw_formt(w, col, theta, lane) != 0) LBW_DROP_PAIRS();
+            PTE(tt_, 6);
+        }
     }
     *f_out = f; *nit_out = iter;
 #ifdef LBW_PROF
     WSYNC();
     if (lane == 0) w->prof[7] = __builtin_readcyclecounter() - tstart_;
     WSYNC();
-    if (lane < 8) w->x[lane] = (double)w->prof[lane];
+    if (lane < 8) w->x[lane] = (double)w->prof[(LBW_PROF - 1) * 8 + lane];
     WSYNC();
 #endif
     return 0;
 }
+#undef LBW_DROP_PAIRS
 #endif  // __HIPCC__

@@ -1,5 +1,6 @@
-// Wave-cooperative L-BFGS-B with the PUBLISHED subspace step (formk / subsm / formt: the form SciPy's L-BFGS-B 3.0 runs, and the
-// form utils/model_utils.py:295-296 therefore runs in the reference): ONE 64-lane wavefront solves ONE object.
+// The PUBLISHED subspace step (formk / subsm / formt: the form SciPy's L-BFGS-B 3.0 runs, and the form utils/model_utils.py:295-296
+// therefore runs in the reference) for the wave-cooperative driver of lbfgsb_wave.h (lbw_minimize<LBW_PUBLISHED>): its LDS struct,
+// lbw_formk, lbw_subsm, lbw_matupd and lbw_formt, and the factorisations and triangular solves under them.
 //
 // History: the round-2 product solver (git fdc3025), replaced as the default by the two-loop direction of lbfgsb_wave.h at the end of
 // round 2, back on the product path in round 5 (rtm3d_decode3d_slots form = 1) and THE DEFAULT of every entry since round 6
@@ -19,17 +20,14 @@
 // against 14.7k for the direct form; 135 VGPRs (239 with the unrolled through-LDS factorisations), 67 KB of LDS per 8-object
 // workgroup; the bench batch's decode kernel alone 2.62 ms (2.93 before, 1.64 for the direct form); per pipelined bs=32 step at
 // ~470 objects + 0.33 ms over the direct form before this round's changes.
-// Everything sits in namespace lbw_pub: the type and function names are those of lbfgsb_wave.h.
 #pragma once
 #include "lbfgsb.h"
-#include "lbfgsb_wave.h"       // WSYNC / PTB / PTE / VWS_ / VWY_
+#include "lbfgsb_wave.h"       // WSYNC / PTB / PTE / VWS_ / VWY_, lbw_dot8, lbw_push_pair; the driver
 
 #if defined(__HIPCC__)
 #pragma clang fp contract(off)
 
-namespace lbw_pub {
-
-struct LbWaveMem {
+template <> struct LbwMem<LBW_PUBLISHED> {
     double ws[LB_N * LB_M], wy[LB_N * LB_M];
     double sy[LB_M * LB_M], ss[LB_M * LB_M], wt[LB_M * LB_M];
     // WN (upper triangle incl. diagonal: the matrix formk factorises in place) and WN1 (lower triangles of its (1,1) and
@@ -49,7 +47,7 @@ struct LbWaveMem {
 #define VWN_(i, j) w->wn[((j)-1) * LB_M2 + (i)-1]
 #define VWN1_(i, j) (*((i) == (j) ? &w->wn1d[(i)-1] : &w->wn[((j)-1) * LB_M2 + (i)-1]))      /* i >= j */
 
-struct LbWaveK { double k00, k02, k11, k12; };
+using LbwMemPub = LbwMem<LBW_PUBLISHED>;
 
 // The lane index as a value the optimiser cannot see through: index arithmetic derived from it is then redone where it is
 // used (a few VALU instructions) instead of being hoisted out of the iteration loop and kept live across it.  The loop
@@ -75,69 +73,6 @@ __device__ static inline double lbw_bcast(double v, int src) {
     lo = __builtin_amdgcn_readlane(lo, src);
     hi = __builtin_amdgcn_readlane(hi, src);
     return __hiloint2double(hi, lo);
-}
-
-// A wave-uniform double (every lane computed the same bits from LDS broadcasts) handed to the compiler AS uniform: it may then live
-// in an SGPR pair - or, under pressure, in two lanes of a spill VGPR (v_writelane / v_readlane: a few cycles) - instead of two
-// VGPRs of every lane.  The loop-carried scalars of lbw_minimize (f, theta, the camera constants) are live across formk / subsm, whose
-// unrolled factorisations want every vector register: at the 168-register budget of twelve waves per workgroup they were the values
-// the allocator sent to scratch memory (a global-memory round trip inside a latency chain).  Same bits in, same bits out.
-__device__ static inline double lbw_uni(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    hi = __builtin_amdgcn_readfirstlane(hi);
-    return __hiloint2double(hi, lo);
-}
-
-// f (returned, identical in every lane) and g (-> w->g) at w->x.
-__device__ static inline double lbw_fg(LbWaveMem* w, const LbWaveK& K, int lane) {
-    const int c = lane >> 3, i = lane & 7;
-    double c0, c1, c2;
-    lb_corner(c, &c0, &c1, &c2);
-    const double x0 = w->x[0], x1 = w->x[1], x2 = w->x[2], x3 = w->x[3], x4 = w->x[4], x5 = w->x[5], x6 = w->x[6], x7 = w->x[7];
-    const double xc = c0 * x2 * x1 + c2 * x4 * x0 + x5;
-    const double yc = c1 * x3 + x6;
-    const double zc = (-c0) * x2 * x0 + c2 * x4 * x1 + x7;
-    const double u = w->uv[2 * c], v = w->uv[2 * c + 1];
-    if (i == 0) {
-        const double ex = xc * K.k00 / (zc + 1e-4) + K.k02 - u;
-        const double ey = yc * K.k11 / (zc + 1e-4) + K.k12 - v;
-        w->fterms[2 * c] = ex * ex;
-        w->fterms[2 * c + 1] = ey * ey;
-    }
-    const double dex = (xc * K.k00 / (zc + 1e-6) + K.k02 - u) * 2;
-    const double dey = (yc * K.k11 / (zc + 1e-6) + K.k12 - v) * 2;
-    double dx, dy, dz;
-    switch (i) {
-        case 0: dx = c2 * x4; dy = 0; dz = (-c0) * x2; break;
-        case 1: dx = c0 * x2; dy = 0; dz = c2 * x4; break;
-        case 2: dx = c0 * x1; dy = 0; dz = (-c0) * x0; break;
-        case 3: dx = 0; dy = c1; dz = 0; break;
-        case 4: dx = c2 * x0; dy = 0; dz = c2 * x1; break;
-        case 5: dx = 1; dy = 0; dz = 0; break;
-        case 6: dx = 0; dy = 1; dz = 0; break;
-        default: dx = 0; dy = 0; dz = 1; break;
-    }
-    const double den = zc * zc + 1e-6;
-    const double gx = K.k00 * (dx * zc - dz * xc) / den;
-    const double gy = K.k11 * (dy * zc - dz * yc) / den;
-    w->terms[lane] = dex * gx + dey * gy;
-    WSYNC();
-    if (lane < 8) {
-        double s = 0.0;
-        for (int k = 0; k < 8; ++k) s += w->terms[k * 8 + lane];
-        w->g[lane] = s;
-    }
-    double f = 0.0;
-    for (int k = 0; k < 16; ++k) f += w->fterms[k];
-    WSYNC();
-    return f;
-}
-
-__device__ static inline double lbw_dot8(const double* a, const double* b) {
-    double s = 0.0;
-    for (int i = 0; i < LB_N; ++i) s += a[i] * b[i];
-    return s;
 }
 
 // Cholesky A = U'U (upper, column-major, leading dimension lda) of an n x n block (n <= LB_M), in place; the diagonal of the result
@@ -306,7 +241,7 @@ __device__ static inline int lbw_rhs_solve(const double* u, double* b, int n) {
     return n == LB_M ? lbw_rhs_solve_t<true>(u, b, n) : lbw_rhs_solve_t<false>(u, b, n);
 }
 
-__device__ static inline int lbw_formk(LbWaveMem* w, int iupdat, double theta, int col, int head, int lane) {
+__device__ static inline int lbw_formk(LbwMemPub* w, int iupdat, double theta, int col, int head, int lane) {
     lane = lbw_opaque(lane);
     const int m = LB_M, n = LB_N;
     PTB(f0_);
@@ -407,7 +342,7 @@ __device__ static inline int lbw_formk(LbWaveMem* w, int iupdat, double theta, i
     return 0;
 }
 
-__device__ static inline int lbw_subsm(LbWaveMem* w, double theta, int col, int head, int lane) {
+__device__ static inline int lbw_subsm(LbwMemPub* w, double theta, int col, int head, int lane) {
     lane = lbw_opaque(lane);
     const int m = LB_M, n = LB_N;
     const int col2 = 2 * col;
@@ -456,18 +391,11 @@ __device__ static inline int lbw_subsm(LbWaveMem* w, double theta, int col, int 
     return 0;
 }
 
-__device__ static inline void lbw_matupd(LbWaveMem* w, int* itail, int iupdat, int* col, int* head, double* theta,
+__device__ static inline void lbw_matupd(LbwMemPub* w, int* itail, int iupdat, int* col, int* head, double* theta,
                                          double rr, double dr, double stp, double dtd, int lane) {
     lane = lbw_opaque(lane);
-    const int m = LB_M, n = LB_N;
-    {   // (value selection, not stores through col / head per branch: see lb_dcstep)
-        const bool grow = iupdat <= m;
-        const int col0 = *col, head0 = *head, itail0 = *itail;
-        *col = grow ? iupdat : col0;
-        *itail = grow ? (head0 + iupdat - 2) % m + 1 : itail0 % m + 1;
-        *head = grow ? head0 : head0 % m + 1;
-    }
-    if (lane < n) { VWS_(lane + 1, *itail) = w->d[lane]; VWY_(lane + 1, *itail) = w->r[lane]; }
+    const int m = LB_M;
+    lbw_push_pair(w, itail, iupdat, col, head, lane);
     *theta = rr / dr;
     if (iupdat > m) {
         // move the old information: SS upper triangle and SY lower triangle one step up-left (9x9 grids)
@@ -502,7 +430,7 @@ __device__ static inline void lbw_matupd(LbWaveMem* w, int* itail, int iupdat, i
     WSYNC();
 }
 
-__device__ static inline int lbw_formt(LbWaveMem* w, int col, double theta, int lane) {
+__device__ static inline int lbw_formt(LbwMemPub* w, int col, double theta, int lane) {
     lane = lbw_opaque(lane);
     if (lane < col) w->wv[lane] = 1.0 / VSY_(lane + 1, lane + 1);      // 1 / SY(k, k) (wv is free between subsm calls)
     WSYNC();
@@ -530,128 +458,4 @@ __device__ static inline int lbw_formt(LbWaveMem* w, int col, double theta, int 
     WSYNC();
     return 0;            // T's factorisation (a pass / fail verdict only) runs inside the next lbw_formk: lbw_potrf_lanes<true>
 }
-
-// Driver: identical control flow to lb_minimize (lbfgsb.h).  w->x holds x0 on entry, the result on exit.
-__device__ static inline int lbw_minimize(LbWaveMem* w, const LbWaveK& K, double* f_out, int* nit_out, int lane,
-                                          int maxiter, int maxfun) {
-    const int n = LB_N, maxls = 20;
-    const double epsmch = 2.220446049250313e-16, factr = 1e7, pgtol = 1e-5;
-    const double ftol = 1e-3, gtol = 0.9, xtol = 0.1, big = 1e10;
-    const double tol = factr * epsmch;
-    int col = 0, head = 1, itail = 0, iupdat = 0, updatd = 0, iter = 0, nfgv = 0, info;
-    double theta = 1.0, f, fold = 0.0, gd = 0.0, gdold = 0.0, stp = 0.0, dnorm = 0.0, dtd = 0.0, sbgnrm;
-    LbSearch S;
-
-#ifdef LBW_PROF
-    if (lane < 24) w->prof[lane] = 0;
-    WSYNC();
-    const long long tstart_ = __builtin_readcyclecounter();
-#endif
-    f = lbw_uni(lbw_fg(w, K, lane)); nfgv = 1;
-    {   // non-finite key points: x0, fun = NaN / Inf, 0 iterations, own status (see lb_minimize)
-        bool finite = lb_isfinite(f);
-        for (int i = 0; i < n; ++i) finite = finite && lb_isfinite(w->g[i]);
-        if (!finite) { *f_out = f; *nit_out = 0; return LB_STATUS_NONFINITE; }
-    }
-    sbgnrm = 0.0;
-    for (int i = 0; i < n; ++i) sbgnrm = fmax(sbgnrm, fabs(w->g[i]));
-    if (sbgnrm <= pgtol) { *f_out = f; *nit_out = 0; return 0; }
-
-    for (;;) {
-        if (col == 0) {
-            if (lane < n) w->z[lane] = w->x[lane] + 1.0 * (-w->g[lane]);
-            WSYNC();
-        } else {
-            if (lane < n) { w->z[lane] = w->x[lane]; w->r[lane] = -w->g[lane]; }
-            WSYNC();
-            info = 0;
-            PTB(tk_);
-            if (updatd) info = lbw_formk(w, iupdat, theta, col, head, lane);
-            PTE(tk_, 0); PTB(ts_);
-            if (info == 0) info = lbw_subsm(w, theta, col, head, lane);
-            PTE(ts_, 1);
-            if (info != 0) {
-                col = 0; head = 1; theta = 1.0; iupdat = 0; updatd = 0;
-                WSYNC();
-                continue;
-            }
-        }
-        if (lane < n) { w->d[lane] = w->z[lane] - w->x[lane]; w->t[lane] = w->x[lane]; w->r[lane] = w->g[lane]; }
-        WSYNC();
-        dtd = lbw_dot8(w->d, w->d);
-        dnorm = sqrt(dtd);
-        const double stpmx = big;
-        stp = (iter == 0) ? fmin(1.0 / dnorm, stpmx) : 1.0;
-        fold = f;
-        int ifun = 0, iback = 0, ls_fail = 0, start = 1;
-        info = 0;
-        PTB(tl_);
-        for (;;) {
-            gd = lbw_dot8(w->g, w->d);
-            if (ifun == 0) {
-                gdold = gd;
-                if (gd >= 0.0) { info = -4; break; }
-            }
-            const int task = lb_dcsrch(f, gd, &stp, ftol, gtol, xtol, 0.0, stpmx, start, &S);
-            start = 0;
-            if (task == LS_ERROR) { info = -4; break; }
-            if (task == LS_CONV || task == LS_WARN) break;
-            ifun += 1; nfgv += 1; iback = ifun - 1;
-            WSYNC();
-            if (lane < n) w->x[lane] = (stp == 1.0) ? w->z[lane] : stp * w->d[lane] + w->t[lane];
-            WSYNC();
-            if (iback >= maxls) { ls_fail = 1; break; }
-            f = lbw_uni(lbw_fg(w, K, lane));
-        }
-        PTE(tl_, 2);
-        if (info != 0 || ls_fail) {
-            WSYNC();
-            if (lane < n) { w->x[lane] = w->t[lane]; w->g[lane] = w->r[lane]; }
-            WSYNC();
-            f = fold;
-            if (col == 0) { *f_out = f; *nit_out = iter; return 2; }
-            col = 0; head = 1; theta = 1.0; iupdat = 0; updatd = 0;
-            continue;
-        }
-        iter += 1;
-        sbgnrm = 0.0;
-        for (int i = 0; i < n; ++i) sbgnrm = fmax(sbgnrm, fabs(w->g[i]));
-        if (iter >= maxiter || nfgv > maxfun) { *f_out = f; *nit_out = iter; return 1; }
-        if (sbgnrm <= pgtol) break;
-        const double ddum0 = lb_max3(fabs(fold), fabs(f), 1.0);
-        if ((fold - f) <= tol * ddum0) break;
-        WSYNC();
-        if (lane < n) w->r[lane] = w->g[lane] - w->r[lane];
-        WSYNC();
-        const double rr = lbw_dot8(w->r, w->r);
-        double dr, ddum;
-        if (stp == 1.0) { dr = gd - gdold; ddum = -gdold; }
-        else {
-            dr = (gd - gdold) * stp;
-            WSYNC();
-            if (lane < n) w->d[lane] = stp * w->d[lane];
-            WSYNC();
-            ddum = -gdold * stp;
-        }
-        if (dr <= epsmch * ddum) { updatd = 0; continue; }
-        updatd = 1; iupdat += 1;
-        PTB(tm_);
-        lbw_matupd(w, &itail, iupdat, &col, &head, &theta, rr, dr, stp, dtd, lane);
-        theta = lbw_uni(theta);
-        PTE(tm_, 3); PTB(tt_);
-        if (lbw_formt(w, col, theta, lane) != 0) { col = 0; head = 1; theta = 1.0; iupdat = 0; updatd = 0; }
-        PTE(tt_, 4);
-    }
-    *f_out = f; *nit_out = iter;
-#ifdef LBW_PROF
-    WSYNC();
-    if (lane == 0) w->prof[7] = __builtin_readcyclecounter() - tstart_;
-    WSYNC();
-    if (lane < 8) w->x[lane] = (double)w->prof[(LBW_PROF - 1) * 8 + lane];      // LBW_PROF = 1, 2, 3: which eight counters
-    WSYNC();
-#endif
-    return 0;
-}
-
-}  // namespace lbw_pub
 #endif  // __HIPCC__
