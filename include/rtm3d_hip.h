@@ -68,7 +68,11 @@ int rtm3d_blob_address(rtm3d_ctx* ctx, int id, void** d_ptr, size_t* bytes);
 int rtm3d_op_input_nhwc4(rtm3d_ctx* ctx, int out_tensor);
 
 /* Generic convolution descriptor (one launch; `groups` independent sub-problems on grid.z).
- * Covers conv KxK (any stride / dilation), 1x1 over channel slices of wider tensors (the DLA root
+ * Covers conv KxK (any stride / dilation on kernels 0 and 2, and on the per-tile cin = 16 / 32 instances of kernel 3, which
+ * index every tap; the rest of kernel 3 is narrower and refuses other taps by name: its vertical-walk instances - stride 1,
+ * out_scale 1, cout 16 with cin = 4 or the 6-k-step cin = 16 packing - take only the dense 7x7 / 3x3 taps in row-major
+ * order at dilation 1, its cin = 4 instances need the 7 taps of a filter row on adjacent pixels of a 4-channel tensor, and
+ * its 16-byte accesses need tensors whose channel count is a multiple of 8), 1x1 over channel slices of wider tensors (the DLA root
  * "concat" never materialises: producers write slices), grouped head convs, and the four
  * sub-pixel phases of ConvTranspose2d(k4,s2,p1) (models/nets/module.py:7-15).
  * Iteration domain: m in [0, B*Hm*Wm) -> (n, y, x).

@@ -335,7 +335,9 @@ static int admit_mfma256(rtm3d_ctx* ctx, const rtm3d_conv_desc* d, size_t wbytes
 
 static int admit_smallc(rtm3d_ctx*, const rtm3d_conv_desc* d, size_t wbytes, size_t bbytes, Op& op) {
     ConvKArgs& a = op.conv;
-    if (d->groups != 1 || d->out_nchw_f32 || a.res) RT_FAIL("op_conv(smallc): groups/NCHW output/residual unsupported");
+    if (d->groups != 1) RT_FAIL("op_conv(smallc): groups=%d unsupported (one group)", d->groups);
+    if (d->out_nchw_f32) RT_FAIL("op_conv(smallc): NCHW output unsupported");
+    if (a.res) RT_FAIL("op_conv(smallc): residual unsupported");
     if (!conv_smallc_supported(d->cin, d->cout, d->ntaps)) RT_FAIL("op_conv(smallc): no kernel for cin=%d cout=%d ntaps=%d", d->cin, d->cout, d->ntaps);
     int S = d->cin == 16 ? 5 : (d->cin == 32 ? d->ntaps : 7);
     // cin=16 also comes packed by filter rows (6 k-steps: taps (ky,0),(ky,1) | (ky,2),zero) for the
@@ -345,6 +347,33 @@ static int admit_smallc(rtm3d_ctx*, const rtm3d_conv_desc* d, size_t wbytes, siz
     a.ksteps = S;
     if (bbytes != (size_t)d->cout * sizeof(float)) RT_FAIL("op_conv(smallc): bias blob size mismatch");
     if (d->cin == 4 && a.in_P < 4) RT_FAIL("op_conv(smallc): the NHWC4 stem input needs a border of 4");
+    // operand alignment: a cin = 4 lane loads two adjacent PIXELS in one 16-byte piece (a 4-channel tensor); cin = 16 / 32 lanes load
+    // 16-byte pieces of one pixel, and the instances with an even number of 16-channel tiles (cout 32 / 64) store 16 bytes
+    if (d->cin == 4 && (a.in_C != 4 || d->in_coff[0] != 0)) RT_FAIL("op_conv(smallc): cin=4 reads a 4-channel NHWC4 tensor (input tensor has %d channels, in_coff=%d)", a.in_C, d->in_coff[0]);
+    if (d->cin != 4 && a.in_C % 8) RT_FAIL("op_conv(smallc): 16-byte operand loads are misaligned in an input tensor of %d channels (needs a multiple of 8)", a.in_C);
+    if (d->cout != 16 && a.out_C % 8) RT_FAIL("op_conv(smallc): 16-byte stores are misaligned in an output tensor of %d channels (needs a multiple of 8)", a.out_C);
+    // tap geometry of the instance launch_conv_smallc will run (conv_smallc.hip).  The vertical-walk kernel keeps operand rows in
+    // registers from one output row to the next: filter row ky + 1 must lie exactly one input row below filter row ky.  Both
+    // cin = 4 instances load taps (ky, kx), (ky, kx + 1) as one piece.  The per-tile cin = 16 / 32 instances index every tap.
+    const int* dy = d->tap_dy[0];
+    const int* dx = d->tap_dx[0];
+    const bool rows = d->in_stride == 1 && d->out_scale == 1 && d->cout == 16 && (d->cin == 4 || (d->cin == 16 && S == 6));
+    if (rows) {
+        const int K = d->cin == 4 ? 7 : 3;
+        for (int t = 0; t < d->ntaps; ++t)
+            if (dy[t] != dy[0] + t / K || dx[t] != dx[0] + t % K)
+                RT_FAIL("op_conv(smallc): tap geometry: the vertical-walk kernel needs the dense %dx%d taps in row-major order, dilation 1 (tap %d is (%d,%d), expected (%d,%d))",
+                        K, K, t, dy[t], dx[t], dy[0] + t / K, dx[0] + t % K);
+    } else if (d->cin == 4) {
+        for (int t = 0; t < d->ntaps; ++t)
+            if (t % 7 && (dy[t] != dy[t - 1] || dx[t] != dx[t - 1] + 1))
+                RT_FAIL("op_conv(smallc): tap geometry: cin=4 needs the 7 taps of a filter row on adjacent pixels (tap %d is (%d,%d) after (%d,%d))",
+                        t, dy[t], dx[t], dy[t - 1], dx[t - 1]);
+    }
+    if (d->cin == 4)
+        for (int ky = 0; ky < 7; ++ky)      // the zero-weighted eighth pixel of a filter row is read too
+            if ((d->Wm - 1) * d->in_stride + dx[ky * 7 + 6] + 1 >= a.in_Wp - a.in_P)
+                RT_FAIL("op_conv(smallc): the pixel right of tap (%d,%d), read with zero weight, leaves the padded input", dy[ky * 7 + 6], dx[ky * 7 + 6]);
     a.g[0].w_off = 0; a.g[0].bias_off = 0;
     op.kind = OP_CONV_SMALLC;
     op.name = d->cin == 4 ? "stem7x7_regmfma" : "conv_smallc_regmfma";

@@ -1189,8 +1189,10 @@ def lower(P):
 
 
 def _smallc_rows(op):
-    """16 -> 16 channel stride-1 3x3 layers are packed by filter rows for conv_smallc.hip's vertical-walk kernel."""
-    return op['cin'] == 16 and op['cout'] == 16 and op['in_stride'] == 1 and op['out_scale'] == 1 and len(op['taps'][0]) == 9
+    """16 -> 16 channel stride-1 3x3 layers are packed by filter rows for conv_smallc.hip's vertical-walk kernel.  That kernel
+    keeps operand rows in registers from one output row to the next, so only the plain dilation-1 taps take it: any other nine
+    taps (a dilated conv) keep the per-tap packing of the per-tile kernel."""
+    return op['cin'] == 16 and op['cout'] == 16 and op['in_stride'] == 1 and op['out_scale'] == 1 and list(op['taps'][0]) == _TAPS3
 
 
 def _mfma_packing(op, bn):

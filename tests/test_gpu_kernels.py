@@ -1,7 +1,8 @@
 """GPU (-m gpu): every HIP kernel variant on its own, through the C ABI, against a plain PyTorch fp32
 reference of the same op (fp16-rounded operands, fp32 math), including ragged shapes: pixel counts
 that are not multiples of the 128/256-pixel tiles, channel slices of wider tensors, strides, dilation,
-the four transposed-convolution phases, residual + ReLU epilogues."""
+the four transposed-convolution phases, residual + ReLU epilogues.  The register-direct small-channel kernels (kernel 3,
+conv_smallc.hip) have a suite of their own over every launch instance and regime, with bit-exact cases: tests/test_gpu_smallc.py."""
 import ctypes
 
 import numpy as np
