@@ -1,8 +1,9 @@
 """Engine files: a realized plan written to disk, so that a C or C++ process runs the model without Python.
 
-``save_engine`` drives the unchanged ``plan.build_plan`` and ``plan.RealizedPlan`` against a recording stand-in for
-librtm3d_hip.so (no GPU, no library needed) and writes the state-changing C ABI calls it made - tensor and blob creation,
-every ``rtm3d_op_*`` launch with its descriptor - plus the packed weight blobs and the metadata of a detect step.
+``save_engine`` has ``plan.PlanRecorder`` - the recording half of ``plan.RealizedPlan`` - issue the plan of ``plan.build_plan``
+on a recorder of its own instead of librtm3d_hip.so (no GPU, no library, no context needed) and writes the state-changing C ABI
+calls it made - tensor and blob creation, every ``rtm3d_op_*`` launch with its descriptor - plus the packed weight blobs and the
+metadata of a detect step.
 ``rtm3d_engine_load`` (csrc/engine.cpp) replays those calls inside the library; ``rtm3d_engine_detect`` then runs
 forward -> decode2d -> decode3d_slots -> pack_records on one stream.  The format is documented in DESIGN.md section 10 and
 above the prototypes in include/rtm3d_hip.h; ``read_engine`` is a pure-Python parser of it (inspection and tests).
@@ -14,7 +15,6 @@ above the prototypes in include/rtm3d_hip.h; ``read_engine`` is a pure-Python pa
 import ctypes
 import hashlib
 import struct
-import threading
 
 import numpy as np
 
@@ -94,20 +94,13 @@ def info_dict(info):
 
 # ---------------------------------------------------------------------------------------------------------- export
 class _Recorder(object):
-    """Stand-in for the ctypes library while RealizedPlan records a plan: keeps the allowlisted calls with their arguments
-    and the blob bytes, hands out ids per namespace the way the runtime does (0, 1, 2 ... in creation order), returns 0."""
+    """The `lib` plan.PlanRecorder issues an exported plan on: keeps the allowlisted calls with their arguments and the blob
+    bytes, hands out ids per namespace the way the runtime does (0, 1, 2 ... in creation order), returns 0."""
 
     def __init__(self):
         self.records = []          # (name, tuple of ints | descriptor bytes | (nbytes, blob index))
         self.blobs = []
         self._next = {}
-
-    def rtm3d_ctx_create(self, device, out):
-        out._obj.value = 0x1000
-        return 0
-
-    def rtm3d_ctx_destroy(self, ctx):
-        return None
 
     def __getattr__(self, name):
         if not name.startswith('rtm3d_'):
@@ -149,22 +142,12 @@ class _Recorder(object):
         return 0
 
 
-_RECORD_LOCK = threading.Lock()
-
-
 def record_plan(ir):
-    """(records, blobs) of RealizedPlan(ir) recorded against the stand-in (the plan module is not changed: _lib.load is
-    pointed at the recorder for the duration of the call)."""
+    """(records, blobs) of the plan IR as plan.PlanRecorder issues it: on a _Recorder, with no context (nothing shared is
+    touched: neither the library nor its loader)."""
     from . import plan as plan_mod
     rec = _Recorder()
-    with _RECORD_LOCK:
-        load = _lib.load
-        _lib.load = lambda: rec
-        try:
-            R = plan_mod.RealizedPlan(ir, 0)
-            R.ctx = None                      # nothing to destroy
-        finally:
-            _lib.load = load
+    plan_mod.PlanRecorder(ir, rec, None)
     return rec.records, rec.blobs
 
 

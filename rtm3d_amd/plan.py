@@ -7,8 +7,8 @@ orchestration").  ``build_plan`` walks the architecture once and emits a small I
   ops     : input4 | conv | headout | maxpool | softmax   with BatchNorm already folded into weights/bias
 
 ``lower`` turns the IR into launches - fusions, level rewrites and the kernel of every conv decided, no
-device needed - and ``RealizedPlan`` packs their weights and records them into a runtime context through
-the C ABI.  The IR is plain numpy so the wiring (channel slices instead of torch.cat, sub-pixel phases
+device needed - ``PlanRecorder`` packs their weights and issues them as C ABI calls, and ``RealizedPlan``
+is a runtime context those calls were recorded into.  The IR is plain numpy so the wiring (channel slices instead of torch.cat, sub-pixel phases
 of the transposed convolutions, BN folding) and the lowering's rewrites can be checked on a CPU-only
 machine by tests/plan_interp.py.
 
@@ -1210,17 +1210,14 @@ _CONV_PACKING = {
 }
 
 
-class RealizedPlan(object):
-    """A Plan recorded into a librtm3d_hip context: the launches of lower(plan), one rtm3d_* call sequence per launch kind."""
-    def __init__(self, plan, device_index):
-        lib = _lib.load()
-        self.lib, self.plan, self.cache = lib, plan, plan.cache
-        self.peak, self.yx_blob = None, None
-        ctx = ctypes.c_void_p()
-        _lib.check(lib.rtm3d_ctx_create(int(device_index), ctypes.byref(ctx)), 'ctx_create')
-        self.ctx = ctx
+class PlanRecorder(object):
+    """The launches of lower(plan) issued on `lib`, one rtm3d_* call sequence per launch kind: tensor and blob creation and the
+    rtm3d_op_* entries, nothing else.  `lib` is the ctypes library or anything with those entries (an engine export, a test's
+    call log); `ctx` is handed through as their first argument and never looked at (None where `lib` has no context)."""
+    def __init__(self, plan, lib, ctx):
+        self.lib, self.plan, self.cache, self.ctx = lib, plan, plan.cache, ctx
+        self.yx_blob = None                     # blob of the peak coordinates: created by a patch plan's first patch_mask launch
         self.lowering = lower(plan)
-        self.unwritten = self.lowering['unwritten']
         self.tids = []
         for i, t in enumerate(plan.tensors):
             tid = ctypes.c_int()
@@ -1391,6 +1388,22 @@ class RealizedPlan(object):
         us = (ctypes.c_int * len(op['us']))(*[self.tids[u.tid] for u in op['us']])
         _lib.check(self.lib.rtm3d_op_softmax_fuse(self.ctx, self.tids[op['z_in'].tid], self.tids[op['z_out'].tid], len(op['us']), us),
                    'op_softmax_fuse')
+
+class RealizedPlan(object):
+    """A Plan recorded into a librtm3d_hip context of its own (PlanRecorder on the library), and the handle of that context."""
+    def __init__(self, plan, device_index):
+        lib = _lib.load()
+        self.lib, self.plan, self.cache, self.peak, self.ctx = lib, plan, plan.cache, None, None
+        ctx = ctypes.c_void_p()
+        _lib.check(lib.rtm3d_ctx_create(int(device_index), ctypes.byref(ctx)), 'ctx_create')
+        try:
+            rec = PlanRecorder(plan, lib, ctx)
+        except BaseException:
+            lib.rtm3d_ctx_destroy(ctx)
+            raise
+        self.ctx = ctx
+        self.lowering, self.unwritten = rec.lowering, rec.lowering['unwritten']
+        self.tids, self.op_names, self.weight_ranges, self.yx_blob = rec.tids, rec.op_names, rec.weight_ranges, rec.yx_blob
 
     def tensor_info(self, s):
         """(device address of padded element [0][0][0][0], B, H, W, C, border) of the tensor a Slice lives in."""

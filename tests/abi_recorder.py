@@ -1,13 +1,19 @@
-"""Stand-in for the ctypes binding of librtm3d_hip.so - TEST INFRASTRUCTURE, not a product path.
+"""A stand-in for the ctypes binding of librtm3d_hip.so - TEST INFRASTRUCTURE, not a product path.
 
-``rtm3d_amd._lib.load`` monkeypatched to return an ``AbiRecorder`` lets ``plan.RealizedPlan`` record a plan on a machine
-without the library or a GPU: every C ABI call is logged by name with its arguments (the context pointer left out), the
-id out-parameters of tensor and blob creation are answered with counters, and every call returns 0.  The log is what the
-runtime would have been told, so its digest pins the realized launch list of a plan.
+``record(ir)`` has ``plan.PlanRecorder`` issue a plan on an ``AbiRecorder``, on a machine without the library or a GPU: every
+C ABI call is logged by name with its arguments (the context pointer left out), the id out-parameters of tensor and blob
+creation are answered with counters, and every call returns 0.  The log is what the runtime would have been told, so its
+digest pins the realized launch list of a plan.
 """
 import ctypes
 import hashlib
 import json
+
+from rtm3d_amd import plan as plan_mod
+
+# the plan module's switches as the product sets them (pinned so that RTM3D_* environment variables change nothing)
+DEFAULTS = {'V2_MIN_TILES': 200, 'FUSE_LEVEL_ENTRY': True, 'FUSE_LEVEL_TAIL': True, 'FOLD_PROJECT': True, 'FOLD_PROJECT_C128': True,
+            'FOLD_NECK_UP': True, 'FUSE_STEM': True, 'USE_CONV128': True, 'USE_CONV64S2': True, 'S2D_ONLY': True, 'BN_TILE_OVERRIDE': {}}
 
 
 def _value(a):
@@ -40,9 +46,6 @@ class AbiRecorder(object):
         return call
 
     def _record(self, name, args):
-        if name == 'rtm3d_ctx_create':
-            args[1]._obj.value = 0x1000                 # any non-null context handle (not logged)
-            return 0
         args = args[1:]                                 # (the context pointer)
         if name == 'rtm3d_blob_create':
             data = ctypes.string_at(args[0].value, args[1]) if args[1] else b''
@@ -64,3 +67,16 @@ class AbiRecorder(object):
 
     def digest(self):
         return hashlib.sha256(json.dumps(self.calls, sort_keys=True).encode()).hexdigest()
+
+
+def pin_switches(monkeypatch, **switches):
+    """Set the plan module's switches to DEFAULTS, but for `switches`."""
+    for k, v in dict(DEFAULTS, **switches).items():
+        monkeypatch.setattr(plan_mod, k, v)
+
+
+def record(ir):
+    """The AbiRecorder a plan IR was issued on; .recorded is the plan.PlanRecorder that did (op_names, tids ...)."""
+    rec = AbiRecorder()
+    rec.recorded = plan_mod.PlanRecorder(ir, rec, None)
+    return rec

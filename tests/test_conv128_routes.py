@@ -7,8 +7,7 @@ import pytest
 from rtm3d_amd import _lib, plan as plan_mod, weights
 from tests import conv128_routes as cr
 from tests import test_gpu_conv128 as gpu_cases
-from tests.abi_recorder import AbiRecorder
-from tests.test_realize_abi import DEFAULTS
+from tests.abi_recorder import pin_switches, record
 
 
 def test_route_of_names():
@@ -98,8 +97,7 @@ def product_regimes(calls):
 
 
 def test_every_product_regime_has_a_gpu_case(monkeypatch):
-    for k, v in DEFAULTS.items():
-        monkeypatch.setattr(plan_mod, k, v)
+    pin_switches(monkeypatch)
     sds = {bb: weights.synth_state_dict(bb, 3, 'trained') for bb in ('DLA-34', 'RESNET-18', 'RESNET-34')}
     plans = [('DLA-34', B, H) for B in (1, 2, 32) for H in (384, 416)] + [('RESNET-18', 8, 384), ('RESNET-34', 8, 384)]
     builds = [lambda bb=bb, B=B, H=H: plan_mod.build_plan(sds[bb], bb, B, H, 1280) for bb, B, H in plans]
@@ -107,25 +105,18 @@ def test_every_product_regime_has_a_gpu_case(monkeypatch):
     covered = {gpu_cases.regime(sp) for sp in gpu_cases.CASES.values()}
     missing = {}
     for build in builds:
-        rec = AbiRecorder()
-        monkeypatch.setattr(_lib, 'load', lambda: rec)
-        R = plan_mod.RealizedPlan(build(), 0)
-        R.close()
-        for key, d in product_regimes(rec.calls).items():
+        for key, d in product_regimes(record(build()).calls).items():
             if key not in covered:
                 missing[key] = (d['Hm'], d['Wm'], d['cin'], d['cout'], d['ntaps'])
     assert not missing, missing
 
 
-def test_grouped_nchw_output_records_group_channel_offsets(monkeypatch):
+def test_grouped_nchw_output_records_group_channel_offsets():
     """A grouped conv with an fp32 NCHW output: group g's channels follow group g - 1's in the slot (out_coff = g * cout)."""
     P = plan_mod.Plan(1, 48, 80)
     x = P.tensor(12, 20, 128, 1)
     ws = [np.zeros((3, 64, 9), np.float32)] * 2
     P.conv_taps([P.sub(x, 0, 64), P.sub(x, 64, 64)], [None, None], ws, [np.zeros(3, np.float32)] * 2,
                 [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)], 12, 20, name='g', out_nchw=2)
-    rec = AbiRecorder()
-    monkeypatch.setattr(_lib, 'load', lambda: rec)
-    plan_mod.RealizedPlan(P, 0).close()
-    (d,) = [a[0] for fn, a in rec.calls if fn == 'rtm3d_op_conv']
+    (d,) = [a[0] for fn, a in record(P).calls if fn == 'rtm3d_op_conv']
     assert (d['out_tensor'], d['out_nchw_f32'], d['groups'], d['out_coff'][:2]) == (-1, 2, 2, [0, 3])

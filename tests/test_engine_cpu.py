@@ -1,5 +1,5 @@
 """CPU: engine files (rtm3d_amd/engine.py, csrc/engine.cpp).  An exported engine holds exactly the C ABI call stream that
-plan.RealizedPlan records (same digest as tests/abi_recorder.py gives for the direct recording), export is deterministic,
+plan.PlanRecorder issues (same digest as tests/abi_recorder.py gives for the direct recording), export is deterministic,
 the C loader's host-side checks refuse every kind of damaged file before any device work, struct rtm3d_engine_info has
 the same layout in C and in ctypes, and the plain C example compiles and links against the header and the library."""
 import ctypes
@@ -14,7 +14,7 @@ import pytest
 
 import rtm3d_amd
 from rtm3d_amd import _lib, engine, plan as plan_mod, weights
-from tests.abi_recorder import AbiRecorder
+from tests.abi_recorder import AbiRecorder, record
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(REPO, 'tests', '_build')
@@ -53,20 +53,14 @@ CASES = {
 }
 
 
-def _direct_recording(m, B, H, W, prec, monkeypatch):
-    rec = AbiRecorder()
-    with monkeypatch.context() as mp:
-        mp.setattr(_lib, 'load', lambda: rec)
-        ir = plan_mod.build_plan(m._sd, m._backbone_name, B, H, W, m._head_variant, num_classes=m._num_classes,
-                                 header_num_conv=m._num_conv, head_precision=prec)
-        R = plan_mod.RealizedPlan(ir, 0)
-        digest, n = rec.digest(), len(rec.calls)
-        R.close()
-    return digest, n, len(rec.launches())
+def _direct_recording(m, B, H, W, prec):
+    rec = record(plan_mod.build_plan(m._sd, m._backbone_name, B, H, W, m._head_variant, num_classes=m._num_classes,
+                                     header_num_conv=m._num_conv, head_precision=prec))
+    return rec.digest(), len(rec.calls), len(rec.launches())
 
 
 @pytest.mark.parametrize('case', sorted(CASES))
-def test_engine_holds_the_realized_call_stream(case, tmp_path, monkeypatch):
+def test_engine_holds_the_realized_call_stream(case, tmp_path):
     bb, B, H, W, mk, sk = CASES[case]
     m = make_model(bb, **mk)
     path = str(tmp_path / 'e.rtm3d')
@@ -79,7 +73,7 @@ def test_engine_holds_the_realized_call_stream(case, tmp_path, monkeypatch):
     parsed = engine.read_engine(path)
     rec = AbiRecorder()
     engine.replay(parsed, rec)
-    want, n_calls, n_launches = _direct_recording(m, B, H, W, prec, monkeypatch)
+    want, n_calls, n_launches = _direct_recording(m, B, H, W, prec)
     assert len(rec.calls) == n_calls and len(rec.launches()) == n_launches
     assert rec.digest() == want
     # the body holds only allowlisted state-changing calls
@@ -98,6 +92,32 @@ def test_export_is_deterministic_and_keyed_by_the_weights(tmp_path):
     pa, pc = engine.read_engine(a), engine.read_engine(c)
     assert pa['state_digest'] == state_dict_digest(m._sd) and pa['state_digest'] != pc['state_digest']
     assert pa['blobs'] != pc['blobs']
+
+
+def test_export_does_not_need_the_loader(tmp_path, monkeypatch):
+    """save_engine "needs neither a GPU nor the library": with a loader that refuses, export and record_plan still work."""
+    def refuse():
+        raise AssertionError('export loaded the library')
+    monkeypatch.setattr('rtm3d_amd._lib.load', refuse)
+    m = make_model('DLA-34')
+    path = str(tmp_path / 'e.rtm3d')
+    assert m.save_engine(path, 1, 64, 128)['B'] == 1 and engine.read_engine(path)['records']
+    records, blobs = engine.record_plan(plan_mod.build_plan(m._sd, 'DLA-34', 2, 64, 128))
+    assert len(blobs) == sum(1 for name, _ in records if name == 'rtm3d_blob_create') > 0
+
+
+def test_export_never_replaces_the_loader(tmp_path, monkeypatch):
+    """While an export records, rtm3d_amd._lib.load is the function it always was: a thread that decodes or builds a real
+    plan beside it gets the library."""
+    original, seen = _lib.load, []
+
+    class Watching(engine._Recorder):
+        def _record(self, name, args):
+            seen.append(_lib.load is original)
+            return super(Watching, self)._record(name, args)
+    monkeypatch.setattr(engine, '_Recorder', Watching)
+    make_model('DLA-34').save_engine(str(tmp_path / 'e.rtm3d'), 1, 64, 128)
+    assert len(seen) > 100 and all(seen) and _lib.load is original
 
 
 def test_sparse_heads_and_other_head_tables_are_not_exported(tmp_path):

@@ -3,11 +3,10 @@ the GPU cases of tests/test_gpu_fused.py against it; and a coverage guard: every
 one that some GPU case runs."""
 import pytest
 
-from rtm3d_amd import _lib, plan as plan_mod, weights
+from rtm3d_amd import plan as plan_mod, weights
 from tests import fused_routes as fr
 from tests import test_gpu_fused as gpu_cases
-from tests.abi_recorder import AbiRecorder
-from tests.test_realize_abi import DEFAULTS
+from tests.abi_recorder import pin_switches, record
 
 
 def test_root_instances_and_names():
@@ -104,18 +103,13 @@ def product_regimes(calls):
 
 
 def test_every_product_regime_has_a_gpu_case(monkeypatch):
-    for k, v in DEFAULTS.items():
-        monkeypatch.setattr(plan_mod, k, v)
+    pin_switches(monkeypatch)
     sd = weights.synth_state_dict('DLA-34', 3, 'trained')
     covered = {gpu_cases.regime(sp) for sp in gpu_cases.CASES.values()}
     seen, missing = set(), {}
     for B in (1, 2, 32):
         for H in (384, 416):
-            rec = AbiRecorder()
-            monkeypatch.setattr(_lib, 'load', lambda: rec)
-            R = plan_mod.RealizedPlan(plan_mod.build_plan(sd, 'DLA-34', B, H, 1280), 0)
-            R.close()
-            for key, where in product_regimes(rec.calls).items():
+            for key, where in product_regimes(record(plan_mod.build_plan(sd, 'DLA-34', B, H, 1280)).calls).items():
                 seen.add(key)
                 if key not in covered:
                     missing[key] = where

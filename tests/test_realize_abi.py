@@ -1,4 +1,4 @@
-"""CPU: the exact stream of C ABI calls ``plan.RealizedPlan`` makes for a fixed set of plans - tensors, packed weight blobs,
+"""CPU: the exact stream of C ABI calls ``plan.PlanRecorder`` makes for a fixed set of plans - tensors, packed weight blobs,
 every launch with its descriptor - recorded through tests/abi_recorder.py instead of librtm3d_hip.so and compared with
 digests recorded when the test was written: a change of the host-side lowering that means to keep the launches must keep
 these digests.  The set covers every realize-level rewrite and
@@ -8,11 +8,7 @@ import numpy as np
 import pytest
 
 from rtm3d_amd import _lib, plan as plan_mod, weights
-from tests.abi_recorder import AbiRecorder
-
-# the module switches as the product sets them (the test pins them so that RTM3D_* environment variables change nothing)
-DEFAULTS = {'V2_MIN_TILES': 200, 'FUSE_LEVEL_ENTRY': True, 'FUSE_LEVEL_TAIL': True, 'FOLD_PROJECT': True, 'FOLD_PROJECT_C128': True,
-            'FOLD_NECK_UP': True, 'FUSE_STEM': True, 'USE_CONV128': True, 'USE_CONV64S2': True, 'S2D_ONLY': True, 'BN_TILE_OVERRIDE': {}}
+from tests.abi_recorder import pin_switches, record
 
 _SD = {}
 
@@ -44,7 +40,7 @@ def _softmax_partials_plan():
     return P
 
 
-# case: (plan builder, switches other than DEFAULTS, (calls, launches), sha256 of the call log)
+# case: (plan builder, switches other than abi_recorder.DEFAULTS, (calls, launches), sha256 of the call log)
 CASES = {
     'dla34_b32_384x1280': (_dense('DLA-34', 32, 384, 1280), {}, (182, 47),
         'e8dcb993a5cd13d574f1c73a294ccfc0731b0c5d3fde3c087c7e32136233c469'),
@@ -92,12 +88,8 @@ CASES = {
 @pytest.mark.parametrize('case', sorted(CASES))
 def test_realized_call_stream_is_pinned(case, monkeypatch):
     build, switches, counts, want = CASES[case]
-    for k, v in dict(DEFAULTS, **switches).items():
-        monkeypatch.setattr(plan_mod, k, v)
-    rec = AbiRecorder()
-    monkeypatch.setattr(_lib, 'load', lambda: rec)
-    R = plan_mod.RealizedPlan(build(), 0)
+    pin_switches(monkeypatch, **switches)
+    rec = record(build())
     got = (len(rec.calls), len(rec.launches())), rec.digest()
-    R.close()
-    assert len(R.op_names) == len(rec.launches())
+    assert len(rec.recorded.op_names) == len(rec.launches())
     assert got == (counts, want), got

@@ -8,8 +8,7 @@ import pytest
 from rtm3d_amd import _lib, plan as plan_mod, weights
 from tests import smallc_routes as sr
 from tests import test_gpu_smallc as gpu_cases
-from tests.abi_recorder import AbiRecorder
-from tests.test_realize_abi import DEFAULTS
+from tests.abi_recorder import pin_switches, record
 
 T4_64, T4_16, T16_16, T16_32, T32_64, T32_64P = (gpu_cases.T4_64, gpu_cases.T4_16, gpu_cases.T16_16, gpu_cases.T16_32, gpu_cases.T32_64,
                                                  gpu_cases.T32_64P)
@@ -142,8 +141,6 @@ def product_regimes(calls):
 
 
 def test_every_product_regime_has_a_gpu_case(monkeypatch):
-    for k, v in DEFAULTS.items():
-        monkeypatch.setattr(plan_mod, k, v)
     sds = {bb: weights.synth_state_dict(bb, 3, 'trained') for bb in ('DLA-34', 'RESNET-18', 'RESNET-34')}
     # (build, switches): the ResNet stems; the DLA stem and level-2 entry with their fusions off, and on a map the level entry's
     # fused kernel does not admit (W % 128 != 0)
@@ -153,13 +150,8 @@ def test_every_product_regime_has_a_gpu_case(monkeypatch):
     covered = {gpu_cases.regime(sp) for sp in gpu_cases.CASES.values()}
     seen, missing = set(), {}
     for bb, B, H, W, switches in plans:
-        for k, v in dict(DEFAULTS, **switches).items():
-            monkeypatch.setattr(plan_mod, k, v)
-        rec = AbiRecorder()
-        monkeypatch.setattr(_lib, 'load', lambda: rec)
-        R = plan_mod.RealizedPlan(plan_mod.build_plan(sds[bb], bb, B, H, W), 0)
-        R.close()
-        for key, where in product_regimes(rec.calls).items():
+        pin_switches(monkeypatch, **switches)
+        for key, where in product_regimes(record(plan_mod.build_plan(sds[bb], bb, B, H, W)).calls).items():
             seen.add(key)
             if key not in covered:
                 missing[key] = (bb,) + where
@@ -168,38 +160,28 @@ def test_every_product_regime_has_a_gpu_case(monkeypatch):
     assert {k[0] for k in seen} == set(sr.INSTANCES) - {T4_16, T16_16}, {k[0] for k in seen}
 
 
-def _record(P, monkeypatch):
-    rec = AbiRecorder()
-    monkeypatch.setattr(_lib, 'load', lambda: rec)
-    plan_mod.RealizedPlan(P, 0).close()
-    blobs = [a for fn, a in rec.calls if fn == 'rtm3d_blob_create']
-    (d,) = [a[0] for fn, a in rec.calls if fn == 'rtm3d_op_conv']
-    return d, blobs
+def _record(P):
+    """(rtm3d_op_conv descriptors, blob entries) of a plan's recorded call log."""
+    calls = record(P).calls
+    return [a[0] for fn, a in calls if fn == 'rtm3d_op_conv'], [a for fn, a in calls if fn == 'rtm3d_blob_create']
 
 
 @pytest.mark.parametrize('dil,stride,rows', [(1, 1, True), (2, 1, False), (1, 2, False)])
-def test_only_the_plain_3x3_takes_the_row_packing(monkeypatch, dil, stride, rows):
+def test_only_the_plain_3x3_takes_the_row_packing(dil, stride, rows):
     """A 16 -> 16 conv is packed by filter rows (6 K-steps, the vertical-walk kernel) only with the plain dilation-1 taps at
     stride 1: a dilated one keeps the per-tap packing of the per-tile kernel, which indexes every tap."""
     P = plan_mod.Plan(1, 32, 32)
     x, y = P.tensor(32, 32, 16, 2), P.tensor(32 // stride, 32 // stride, 16, 1)
     P.conv(x, y, np.ones((16, 16, 3, 3), np.float32), np.zeros(16, np.float32), stride=stride, dil=dil, name='c')
-    d, blobs = _record(P, monkeypatch)
+    (d,), blobs = _record(P)
     assert d['kernel'] == _lib.CONV_SMALLC and _rows_packing(d, blobs) == rows
     assert blobs[d['w_blob']][0] == (6 if rows else 5) * 64 * 8 * 2
     assert (d['tap_dy'][0][0], d['tap_dx'][0][8]) == (-dil, dil)
 
 
-def test_gpu_cases_record_the_instance_the_mirror_names(monkeypatch):
+def test_gpu_cases_record_the_instance_the_mirror_names():
     """Each GPU case, recorded without a device: one kernel-3 descriptor per op, with the weight packing (5 or 6 K-steps for
     16 -> 16) that makes launch_conv_smallc pick the instance the case declares; likewise the every-pair chain as one plan."""
-    def recorded(P):
-        rec = AbiRecorder()
-        monkeypatch.setattr(_lib, 'load', lambda: rec)
-        plan_mod.RealizedPlan(P, 0).close()
-        blobs = [a for fn, a in rec.calls if fn == 'rtm3d_blob_create']
-        return [a[0] for fn, a in rec.calls if fn == 'rtm3d_op_conv'], blobs
-
     def matches(d, blobs, sp):
         inst = gpu_cases.mirror(sp)['instance']
         assert d['kernel'] == _lib.CONV_SMALLC and (d['cin'], d['cout'], d['ntaps'], d['in_stride'], d['out_scale']) == (
@@ -211,14 +193,14 @@ def test_gpu_cases_record_the_instance_the_mirror_names(monkeypatch):
     for name, sp in gpu_cases.CASES.items():
         P = plan_mod.Plan(sp['B'], sp['H'], sp['W'])
         gpu_cases.SmallC(P, sp, gpu_cases.case_seed(name))
-        (d,), blobs = recorded(P)
+        (d,), blobs = _record(P)
         matches(d, blobs, sp)
     keys = list(gpu_cases.CHAIN)
     order = gpu_cases.every_pair_order(len(keys))
     P = plan_mod.Plan(2, 64, 64)
     for i in order:
         gpu_cases.SmallC(P, gpu_cases.CHAIN[keys[i]], gpu_cases.case_seed(keys[i]))
-    ds, blobs = recorded(P)
+    ds, blobs = _record(P)
     assert len(ds) == len(order) == 57
     for d, i in zip(ds, order):
         matches(d, blobs, gpu_cases.CHAIN[keys[i]])

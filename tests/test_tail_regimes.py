@@ -3,12 +3,11 @@ k x k max-pool, peak patches), checked by hand-worked launches; the GPU cases of
 guard: every regime the product plans send to these kernels is one that some GPU case runs."""
 import pytest
 
-from rtm3d_amd import _lib, plan as plan_mod, weights
+from rtm3d_amd import plan as plan_mod, weights
 from tests import conv256_tiles as ct
 from tests import tail_regimes as tr
 from tests import test_gpu_tail as gpu_cases
-from tests.abi_recorder import AbiRecorder
-from tests.test_realize_abi import DEFAULTS
+from tests.abi_recorder import pin_switches, record
 
 
 def test_softmax_fuse_by_hand():
@@ -162,8 +161,7 @@ MASK_CASES = {tr.regime_key('patch_mask', S=5, origin=2), tr.regime_key('patch_m
 
 
 def test_every_product_regime_has_a_gpu_case(monkeypatch):
-    for k, v in DEFAULTS.items():
-        monkeypatch.setattr(plan_mod, k, v)
+    pin_switches(monkeypatch)
     covered = {k for sp in gpu_cases.CASES.values() for k in gpu_cases.regimes(sp)} | MASK_CASES
     seen, missing, by_plan = set(), {}, {}
     for bb in ('DLA-34', 'RESNET-18'):
@@ -173,11 +171,7 @@ def test_every_product_regime_has_a_gpu_case(monkeypatch):
         if bb == 'DLA-34':
             plans += [((bb, 'peaks', B), (lambda B=B: plan_mod.build_peak_plan(sd, B * 100, (96, 320)))) for B in (1, 32)]
         for tag, build in plans:
-            rec = AbiRecorder()
-            monkeypatch.setattr(_lib, 'load', lambda: rec)
-            R = plan_mod.RealizedPlan(build(), 0)
-            R.close()
-            by_plan[tag] = product_regimes(rec.calls)
+            by_plan[tag] = product_regimes(record(build()).calls)
             for key, where in by_plan[tag].items():
                 seen.add(key)
                 if key not in covered:
