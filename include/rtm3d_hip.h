@@ -518,6 +518,70 @@ size_t rtm3d_engine_workspace_bytes(rtm3d_ctx* ctx);
 int rtm3d_engine_detect(rtm3d_ctx* ctx, void* stream, const float* d_in, const double* d_K_per_image, float* d_rec,
                         void* d_workspace);
 
+/* ------------------------------------------------------------------ camera frames (csrc/frames_host.cpp, csrc/frames.hip, csrc/engine.cpp)
+ * What lies on either side of a detect step when the caller holds uint8 camera frames and the camera's own intrinsics: the
+ * reference's TestTransform bookkeeping (Normalize, Resize, letterbox; preprocess/transforms.py, datasets/dataset_reader.py)
+ * and the way back from the pixels of the network canvas to the pixels of the frame.  Added in ABI 9 without changing any
+ * existing declaration.
+ *
+ * HOST helpers (no device access; usable on a machine without a GPU):
+ * rtm3d_normalize_luts: h_lut32 [3][256] = float32((v / 255. - mean[c]) / std[c]) evaluated in float64 with float32
+ * mean / std (transforms.py:110-120, 312-317), h_lut16 [3][256] = that value rounded to nearest even to IEEE binary16 -
+ * the d_lut / d_lut16 operands of rtm3d_preprocess_batch.  Either table may be NULL.
+ * rtm3d_frame_geometry: per frame (h, w) = h_hw[2b], h_hw[2b + 1] the size after Resize - resize_to == 0: (h, w);
+ * otherwise rate = (double)resize_to / max(h, w), rh = (int)(h * rate), rw = (int)(w * rate) (transforms.py:484-490) - and
+ * its centred place on the H x W canvas: pad_w = (W - rw) / 2, pad_h = (H - rh) / 2.  A frame with a side < 1 or one that
+ * does not fit the canvas is an error that names the frame.                                                             */
+typedef struct rtm3d_frame_geom {
+    int h, w;                              /* the camera frame */
+    int rh, rw;                            /* after Resize */
+    int pad_w, pad_h;                      /* left / top letterbox border on the canvas */
+} rtm3d_frame_geom;
+int rtm3d_normalize_luts(const float mean[3], const float std[3], float* h_lut32, uint16_t* h_lut16);
+int rtm3d_frame_geometry(int B, const int* h_hw, int resize_to, int H, int W, rtm3d_frame_geom* out);
+
+/* Device kernels; h_geom[B] is HOST memory and travels as a kernel argument (no copy, no memset).  All arithmetic is fp64
+ * in a fixed operation order, compiled without contraction, so the results are defined bit for bit.
+ * rtm3d_frames_adjust_k: d_K_net = the intrinsics of the network canvas from the camera's (both B x 9 fp64): row 0 / w
+ * then * rw, row 1 / h then * rh (ToPercentCoords -> Resize -> ToAbsoluteCoords, transforms.py:146-176; the pair is
+ * executed for equal sizes too), then cx + pad_w, cy + pad_h (dataset_reader.py:189-193); row 2 is copied.
+ * rtm3d_records_to_camera: in place on the B * topk * 32 records of rtm3d_pack_records.  In every slot with flag [31] >= 1
+ * the 2D fields - key point [2:4], vertices [4:20], box [20:24] - become
+ *   (float)(((double)x - pad_w) * ((double)w / (double)rw)),  (float)(((double)y - pad_h) * ((double)h / (double)rh));
+ * [0:2] and [24:32] stay (with consistently adjusted intrinsics the 3D box is the same box); empty slots stay 32 zeros.
+ * d_kitti (may be NULL, and then d_K_camera / d_x / d_fun / d_status may be too): B * topk * 16 fp64, one row per slot,
+ * all zero unless the slot is kept (flag 2: d_status >= 0 and d_fun < fun_accept).  The row holds the numbers of a KITTI
+ * label line (rtm3d_amd/kitti_results.py):
+ *   [0] class  [1] alpha = ry - atan2(x, z) wrapped to [-pi, pi)  [2:6] x1 y1 x2 y2 = the bounding rectangle of the eight
+ *   corners projected through the CAMERA's intrinsics (the arithmetic of rtm3d_project_boxes), clipped to [0, w - 1] x
+ *   [0, h - 1] of the frame  [6:9] h w l  [9:12] x, y + h / 2, z (centre of the bottom face)  [12] ry = atan2(x0, x1)
+ *   [13] score  [14] 2  [15] 0.
+ * d_x / d_fun / d_status: the outputs of rtm3d_decode3d_slots for the same slots.                                         */
+int rtm3d_frames_adjust_k(void* stream, int B, const rtm3d_frame_geom* h_geom, const double* d_K_camera, double* d_K_net);
+int rtm3d_records_to_camera(void* stream, int B, int topk, const rtm3d_frame_geom* h_geom, float* d_rec,
+                            const double* d_K_camera, const double* d_x, const double* d_fun, const int32_t* d_status,
+                            double fun_accept, double* d_kitti);
+
+/* One detect step of an engine fed by camera frames, stream-ordered, no host synchronisation:
+ * rtm3d_frame_geometry -> rtm3d_preprocess_batch (out_mode 1, into the plan's own input tensor) -> rtm3d_frames_adjust_k ->
+ * rtm3d_forward (d_in == NULL) -> rtm3d_decode2d -> rtm3d_decode3d_slots -> rtm3d_pack_records -> rtm3d_records_to_camera.
+ * rtm3d_engine_set_frame_params: once per context made by rtm3d_engine_load, before the first frames step: builds both
+ * normalisation tables and keeps them on the device.  resize_to: 0 = the frames are fed at their own size, otherwise the
+ * longest side after Resize (the reference's INPUT_SIZE).
+ * rtm3d_engine_detect_frames: h_imgs[B] HOST array of DEVICE pointers to uint8 (h, w, 3) frames, h_hw[2B] their (h, w);
+ * d_K_camera B x 9 fp64, the cameras' own intrinsics; d_rec B * topk * 32 fp32 records in the pixels of each frame;
+ * d_kitti NULL or B * topk * 16 fp64 rows (layouts above); d_workspace: rtm3d_engine_frames_workspace_bytes(ctx) bytes =
+ * the detect workspace, the channel sums (B x 3 uint64) and the canvas intrinsics.  Keep d_workspace fixed across calls:
+ * a graph replay of the forward is keyed by the logit addresses inside it.                                              */
+typedef struct rtm3d_frame_params {
+    float mean[3], std[3];
+    int resize_to;
+} rtm3d_frame_params;
+int rtm3d_engine_set_frame_params(rtm3d_ctx* ctx, const rtm3d_frame_params* params);
+size_t rtm3d_engine_frames_workspace_bytes(rtm3d_ctx* ctx);
+int rtm3d_engine_detect_frames(rtm3d_ctx* ctx, void* stream, const uint8_t* const* h_imgs, const int* h_hw,
+                               const double* d_K_camera, float* d_rec, double* d_kitti, void* d_workspace);
+
 #ifdef __cplusplus
 }
 #endif

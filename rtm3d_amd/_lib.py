@@ -67,6 +67,16 @@ class ConvMx8Desc(ctypes.Structure):
     ]
 
 
+class FrameGeom(ctypes.Structure):
+    """Mirror of struct rtm3d_frame_geom."""
+    _fields_ = [('h', c_int), ('w', c_int), ('rh', c_int), ('rw', c_int), ('pad_w', c_int), ('pad_h', c_int)]
+
+
+class FrameParams(ctypes.Structure):
+    """Mirror of struct rtm3d_frame_params."""
+    _fields_ = [('mean', c_float * 3), ('std', c_float * 3), ('resize_to', c_int)]
+
+
 # name -> (restype, argtypes); also the list of symbols include/rtm3d_hip.h declares
 SIGNATURES = {
     'rtm3d_last_error': (ctypes.c_char_p, []),
@@ -141,6 +151,15 @@ SIGNATURES = {
     'rtm3d_engine_load': (c_int, [ctypes.c_char_p, c_int, ctypes.POINTER(c_void_p), c_void_p]),
     'rtm3d_engine_workspace_bytes': (c_size_t, [c_void_p]),
     'rtm3d_engine_detect': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # camera frames (rtm3d_amd/preprocess.py, rtm3d_amd/engine.py)
+    'rtm3d_normalize_luts': (c_int, [ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_void_p]),
+    'rtm3d_frame_geometry': (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(FrameGeom)]),
+    'rtm3d_frames_adjust_k': (c_int, [c_void_p, c_int, ctypes.POINTER(FrameGeom), c_void_p, c_void_p]),
+    'rtm3d_records_to_camera': (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(FrameGeom), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_double, c_void_p]),
+    'rtm3d_engine_set_frame_params': (c_int, [c_void_p, ctypes.POINTER(FrameParams)]),
+    'rtm3d_engine_frames_workspace_bytes': (c_size_t, [c_void_p]),
+    'rtm3d_engine_detect_frames': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@
 #include "lbfgsb.h"
 #include "lbfgsb_wave.h"
 #include "lbfgsb_wave_pub.h"
+#include "box_project.h"
 #include "../../include/rtm3d_hip.h"
 
 // slot mode (n_per_image != nullptr): object i lives in slot (image = i / topk, rank = i % topk) of
@@ -251,20 +252,9 @@ __global__ __launch_bounds__(256) void project_boxes_kernel(int N, int topk, con
     double u = 0.0, v = 0.0;
     if (status[slot] >= 0) {
         const double* xs = x + (size_t)slot * 8;
-        const double* k = K + (size_t)(topk > 0 ? slot / topk : slot) * 9;
-        const double ry = atan2(xs[0], xs[1]);                      // :300
-        double sn = sin(ry), cs = cos(ry);
-        if (fabs(sn) < 1e-3) sn = 0.0;
-        if (fabs(cs) < 1e-3) cs = 0.0;
-        const double dx = xs[2] / 2, dy = xs[3] / 2, dz = xs[4] / 2;  // dimension = (h, w, l) = (x3, x4, x2): half extents (l, h, w) / 2
-        const double sx = c == 8 ? 0.0 : ((c & 4) ? -1.0 : 1.0), sy = c == 8 ? 0.0 : ((c & 2) ? -1.0 : 1.0), sz = c == 8 ? 0.0 : ((c & 1) ? -1.0 : 1.0);
-        // corners = (R diag(dx, dy, dz)) signs + location
-        const double X = (cs * dx) * sx + (sn * dz) * sz + xs[5];
-        const double Y = dy * sy + xs[6];
-        const double Z = (-sn * dx) * sx + (cs * dz) * sz + xs[7];
-        const double pu = k[0] * X + k[1] * Y + k[2] * Z, pv = k[3] * X + k[4] * Y + k[5] * Z, pw = k[6] * X + k[7] * Y + k[8] * Z;
-        u = pu / (pw + 1e-6);
-        v = pv / (pw + 1e-6);
+        double sn, cs;
+        box_yaw(xs, sn, cs);
+        box_project_corner(xs, K + (size_t)(topk > 0 ? slot / topk : slot) * 9, sn, cs, c, u, v);
     }
     proj[(size_t)t * 2] = u;
     proj[(size_t)t * 2 + 1] = v;
@@ -275,17 +265,12 @@ __global__ __launch_bounds__(256) void project_boxes_kernel(int N, int topk, con
         if (status[slot] >= 0) {
             const double* xs = x + (size_t)slot * 8;
             const double* k = K + (size_t)(topk > 0 ? slot / topk : slot) * 9;
-            const double ry = atan2(xs[0], xs[1]);
-            double sn = sin(ry), cs = cos(ry);
-            if (fabs(sn) < 1e-3) sn = 0.0;
-            if (fabs(cs) < 1e-3) cs = 0.0;
-            const double dx = xs[2] / 2, dy = xs[3] / 2, dz = xs[4] / 2;
+            double sn, cs;
+            box_yaw(xs, sn, cs);
             x1 = y1 = 1e300; x2 = y2 = -1e300;
             for (int cc = 0; cc < 8; ++cc) {
-                const double sx = (cc & 4) ? -1.0 : 1.0, sy = (cc & 2) ? -1.0 : 1.0, sz = (cc & 1) ? -1.0 : 1.0;
-                const double X = (cs * dx) * sx + (sn * dz) * sz + xs[5], Y = dy * sy + xs[6], Z = (-sn * dx) * sx + (cs * dz) * sz + xs[7];
-                const double pw = k[6] * X + k[7] * Y + k[8] * Z;
-                const double uu = (k[0] * X + k[1] * Y + k[2] * Z) / (pw + 1e-6), vv = (k[3] * X + k[4] * Y + k[5] * Z) / (pw + 1e-6);
+                double uu, vv;
+                box_project_corner(xs, k, sn, cs, cc, uu, vv);
                 x1 = fmin(x1, uu); y1 = fmin(y1, vv); x2 = fmax(x2, uu); y2 = fmax(y2, vv);
             }
         }

@@ -365,6 +365,13 @@ struct EngineState {
     rtm3d_engine_info info;
     const double* d_dim_ref = nullptr;   // blobs of the context
     const double* d_ref_loc = nullptr;
+    // camera-frame steps (rtm3d_engine_set_frame_params): the normalisation tables (blobs too) and the per-call geometry
+    bool frames = false;
+    int resize_to = 0;
+    const float* d_lut32 = nullptr;
+    const uint16_t* d_lut16 = nullptr;
+    std::vector<rtm3d_frame_geom> geom;
+    std::vector<int> resized_hw;
 };
 
 void free_state(void* p) { delete (EngineState*)p; }
@@ -397,12 +404,23 @@ Layout layout(const rtm3d_engine_info& I) {
     return L;
 }
 
-int device_blob(rtm3d_ctx* ctx, const void* h, size_t bytes, const double** d) {
+template <class T> int device_blob(rtm3d_ctx* ctx, const void* h, size_t bytes, const T** d) {
     int id = -1;
     void* p = nullptr;
     if (rtm3d_blob_create(ctx, h, bytes, &id) || rtm3d_blob_address(ctx, id, &p, nullptr)) return 1;
-    *d = (const double*)p;
+    *d = (const T*)p;
     return 0;
+}
+
+// the workspace of a frames step: the detect workspace, then the channel sums of the letterbox and the canvas intrinsics
+struct FramesLayout { size_t sums, K_net, total; };
+
+FramesLayout frames_layout(const rtm3d_engine_info& I) {
+    FramesLayout F;
+    F.sums = layout(I).total;
+    F.K_net = align_up(F.sums + (size_t)I.B * 3 * sizeof(unsigned long long));
+    F.total = align_up(F.K_net + (size_t)I.B * 9 * sizeof(double));
+    return F;
 }
 
 }  // namespace
@@ -445,11 +463,9 @@ extern "C" size_t rtm3d_engine_workspace_bytes(rtm3d_ctx* ctx) {
     return st ? layout(st->info).total : 0;
 }
 
-extern "C" int rtm3d_engine_detect(rtm3d_ctx* ctx, void* stream, const float* d_in, const double* d_K_per_image, float* d_rec,
-                                   void* d_workspace) {
-    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
-    if (!st) EFAIL("engine_detect: the context was not made by rtm3d_engine_load");
-    if (!d_in || !d_K_per_image || !d_rec || !d_workspace) EFAIL("engine_detect: null argument");
+// forward -> decode2d -> decode3d_slots -> pack_records on the workspace; d_in == nullptr: the plan's input tensor is filled
+static int detect_step(rtm3d_ctx* ctx, EngineState* st, void* stream, const float* d_in, const double* d_K_per_image, float* d_rec,
+                       void* d_workspace) {
     const rtm3d_engine_info& I = st->info;
     const Layout L = layout(I);
     char* w = (char*)d_workspace;
@@ -468,4 +484,68 @@ extern "C" int rtm3d_engine_detect(rtm3d_ctx* ctx, void* stream, const float* d_
                              status, I.solver_form))
         return 1;
     return rtm3d_pack_records(stream, I.B, I.topk, n, cls, score, mproj, verts, bbox, x, fun, status, I.fun_accept, d_rec);
+}
+
+extern "C" int rtm3d_engine_detect(rtm3d_ctx* ctx, void* stream, const float* d_in, const double* d_K_per_image, float* d_rec,
+                                   void* d_workspace) {
+    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
+    if (!st) EFAIL("engine_detect: the context was not made by rtm3d_engine_load");
+    if (!d_in || !d_K_per_image || !d_rec || !d_workspace) EFAIL("engine_detect: null argument");
+    return detect_step(ctx, st, stream, d_in, d_K_per_image, d_rec, d_workspace);
+}
+
+extern "C" int rtm3d_engine_set_frame_params(rtm3d_ctx* ctx, const rtm3d_frame_params* params) {
+    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
+    if (!st) EFAIL("engine_set_frame_params: the context was not made by rtm3d_engine_load");
+    if (!params) EFAIL("engine_set_frame_params: null argument");
+    if (st->frames) EFAIL("engine_set_frame_params: the frame parameters of this context are already set");
+    if (params->resize_to < 0) EFAIL("engine_set_frame_params: resize_to = %d", params->resize_to);
+    float lut32[3 * 256];
+    uint16_t lut16[3 * 256];
+    if (rtm3d_normalize_luts(params->mean, params->std, lut32, lut16)) return 1;
+    void* base = nullptr;
+    int B, H, W, border;
+    if (rtm3d_input_tensor(ctx, &base, &B, &H, &W, &border)) return 1;      // a plan that cannot be fed in place is refused here
+    if (B != st->info.B || H != st->info.H || W != st->info.W)
+        EFAIL("engine_set_frame_params: the plan's input tensor is %dx%dx%d, the engine's batch %dx%dx%d", B, H, W, st->info.B,
+              st->info.H, st->info.W);
+    if (device_blob(ctx, lut32, sizeof lut32, &st->d_lut32) || device_blob(ctx, lut16, sizeof lut16, &st->d_lut16)) return 1;
+    st->resize_to = params->resize_to;
+    st->geom.resize((size_t)st->info.B);
+    st->resized_hw.resize((size_t)st->info.B * 2);
+    st->frames = true;
+    return 0;
+}
+
+extern "C" size_t rtm3d_engine_frames_workspace_bytes(rtm3d_ctx* ctx) {
+    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
+    return st ? frames_layout(st->info).total : 0;
+}
+
+extern "C" int rtm3d_engine_detect_frames(rtm3d_ctx* ctx, void* stream, const uint8_t* const* h_imgs, const int* h_hw,
+                                          const double* d_K_camera, float* d_rec, double* d_kitti, void* d_workspace) {
+    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
+    if (!st) EFAIL("engine_detect_frames: the context was not made by rtm3d_engine_load");
+    if (!h_imgs || !h_hw || !d_K_camera || !d_rec || !d_workspace) EFAIL("engine_detect_frames: null argument");
+    if (!st->frames) EFAIL("engine_detect_frames: call rtm3d_engine_set_frame_params first");
+    const rtm3d_engine_info& I = st->info;
+    for (int b = 0; b < I.B; ++b)
+        if (!h_imgs[b]) EFAIL("engine_detect_frames: frame %d is a null pointer", b);
+    rtm3d_frame_geom* geom = st->geom.data();
+    if (rtm3d_frame_geometry(I.B, h_hw, st->resize_to, I.H, I.W, geom)) return 1;
+    for (int b = 0; b < I.B; ++b) { st->resized_hw[2 * b] = geom[b].rh; st->resized_hw[2 * b + 1] = geom[b].rw; }
+    void* base = nullptr;
+    int tB, tH, tW, border;
+    if (rtm3d_input_tensor(ctx, &base, &tB, &tH, &tW, &border)) return 1;
+    const FramesLayout F = frames_layout(I);
+    const Layout L = layout(I);
+    char* w = (char*)d_workspace;
+    double* K_net = (double*)(w + F.K_net);
+    if (rtm3d_preprocess_batch(stream, I.B, h_imgs, h_hw, st->resized_hw.data(), base, 1, I.H, I.W, border, st->d_lut32, st->d_lut16,
+                               (unsigned long long*)(w + F.sums)))
+        return 1;
+    if (rtm3d_frames_adjust_k(stream, I.B, geom, d_K_camera, K_net)) return 1;
+    if (detect_step(ctx, st, stream, nullptr, K_net, d_rec, d_workspace)) return 1;
+    return rtm3d_records_to_camera(stream, I.B, I.topk, geom, d_rec, d_K_camera, (const double*)(w + L.x), (const double*)(w + L.fun),
+                                   (const int32_t*)(w + L.status), I.fun_accept, d_kitti);
 }

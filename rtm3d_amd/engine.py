@@ -406,6 +406,44 @@ class Engine(object):
                        'engine_detect')
         return rec
 
+    def set_frame_params(self, mean, std, resize_to=None):
+        """Once, before detect_frames (rtm3d_engine_set_frame_params): the Normalize mean / std of the frames (cfg.DATASET.MEAN /
+        STD) and the longest side after Resize (None: the frames are fed at their own size)."""
+        import torch
+        p = _lib.FrameParams((ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std]),
+                             int(resize_to or 0))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rtm3d_engine_set_frame_params(self.ctx, ctypes.byref(p)), 'engine_set_frame_params')
+            self.frames_workspace = torch.empty(int(self.lib.rtm3d_engine_frames_workspace_bytes(self.ctx)), dtype=torch.uint8,
+                                                device=self.device)
+
+    def detect_frames(self, images, K_camera, kitti=False, out=None):
+        """One detect step fed by camera frames (rtm3d_engine_detect_frames): images = list of B uint8 (h, w, 3) CUDA tensors of
+        any sizes that fit the canvas after Resize, K_camera = the cameras' own (B, 9) intrinsics.  Returns the (B, topk, 32)
+        records with their 2D fields in the pixels of each frame; kitti=True: (records, (B, topk, 16) float64 KITTI rows)."""
+        import torch
+        B, topk = self.info['B'], self.info['topk']
+        if getattr(self, 'frames_workspace', None) is None:
+            raise RuntimeError('Engine.detect_frames: call set_frame_params(mean, std, resize_to) first')
+        if len(images) != B:
+            raise ValueError('this engine runs batches of %d frames, got %d' % (B, len(images)))
+        imgs = []
+        for img in images:
+            if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_cuda:
+                raise ValueError('expected uint8 (h, w, 3) CUDA frames')
+            imgs.append(img.contiguous())
+        ptrs = (ctypes.c_void_p * B)(*[i.data_ptr() for i in imgs])
+        hw = (ctypes.c_int * (2 * B))(*[int(v) for i in imgs for v in i.shape[:2]])
+        K = torch.as_tensor(K_camera, dtype=torch.float64, device=self.device).reshape(B, 9).contiguous()
+        with torch.cuda.device(self.device):
+            rec = torch.empty(B, topk, 32, dtype=torch.float32, device=self.device) if out is None else out
+            rows = torch.empty(B, topk, 16, dtype=torch.float64, device=self.device) if kitti else None
+            _lib.check(self.lib.rtm3d_engine_detect_frames(self.ctx, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
+                                                           ptrs, hw, ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+                                                           ctypes.c_void_p(rows.data_ptr()) if kitti else None,
+                                                           ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames')
+        return (rec, rows) if kitti else rec
+
     def close(self):
         if self.ctx:
             self.lib.rtm3d_ctx_destroy(self.ctx)

@@ -25,6 +25,7 @@ import torch
 from .model import Detections
 from .model_utils import Boxes3D, decode3d_slots
 from . import distributed as rdist
+from . import preprocess
 
 
 SMALL_BATCH = 2      # batches whose 3D decode (a serial fp64 iteration per object, ~1 ms) is about as long as the network
@@ -100,12 +101,14 @@ class Detect3DPipeline(object):
         prio = int(prio) if prio is not None else (-1 if n_side == 1 else 0)
         return torch.cuda.Stream(device=self.dev, priority=prio)
 
-    def submit_uint8(self, images, K_per_image, size, resize_to=None):
+    def submit_uint8(self, images, K_per_image, size, resize_to=None, camera_K=False):
         """The same step fed by camera images: ``images`` = list of B uint8 (h, w, 3) CUDA tensors of any
         sizes; Resize (longest side -> resize_to) + letterbox into the (H, W) canvas + normalise run as two launches that
         write the network's own fp16 NHWC4 input tensor (rtm3d_amd.preprocess.preprocess_batch), then the plan is replayed
-        on it.  K_per_image must already carry the Resize / padding bookkeeping (preprocess.resize_K / adjust_K)."""
-        from . import preprocess
+        on it.  camera_K=False: K_per_image must already carry the Resize / padding bookkeeping (preprocess.resize_K /
+        adjust_K) and the records are in the pixels of the canvas.  camera_K=True: K_per_image holds the cameras' own
+        intrinsics; the bookkeeping runs on the device (preprocess.adjust_K_device) and the records come back in the pixels of
+        each frame (preprocess.records_to_camera on the side stream, behind pack_records)."""
         if len(images) != self.B:
             raise ValueError('Detect3DPipeline was built for batches of %d images, got %d' % (self.B, len(images)))
         cfg = self.model.config
@@ -116,7 +119,8 @@ class Detect3DPipeline(object):
                                         head_precision=self.head_precision)
             return self.model.forward_logits(None, preloaded=(self.B, H, W), out='reuse', heads=self.heads,
                                             head_precision=self.head_precision)
-        return self._submit(feed, K_per_image)
+        geom = preprocess.frame_geometry([i.shape[:2] for i in images], (H, W), resize_to) if camera_K else None
+        return self._submit(feed, K_per_image, geom)
 
     def submit(self, x, K_per_image):
         """Enqueue one batch; returns its step index.  Asynchronous."""
@@ -128,7 +132,7 @@ class Detect3DPipeline(object):
                              % (self.B, tuple(x.shape)))
         return self._submit(lambda: self.model.forward_logits(x, out='reuse', heads=self.heads, head_precision=self.head_precision), K_per_image)
 
-    def _submit(self, run_network, K_per_image):
+    def _submit(self, run_network, K_per_image, geom=None):
         if not isinstance(K_per_image, torch.Tensor) or K_per_image.numel() != self.B * 9 or not K_per_image.is_cuda:
             raise ValueError('K_per_image must be a CUDA tensor with %d x 9 intrinsics' % self.B)
         i = self.count
@@ -141,7 +145,10 @@ class Detect3DPipeline(object):
             self.model.decode2d_sparse(logits, out=self.det[s])
         else:
             self.model.decode2d(logits, out=self.det[s])
-        self.K_slot[s].copy_(K_per_image.reshape(self.B, 9), non_blocking=True)     # main stream, ordered before A_s
+        if geom is None:
+            self.K_slot[s].copy_(K_per_image.reshape(self.B, 9), non_blocking=True)     # main stream, ordered before A_s
+        else:                                       # the cameras' intrinsics -> the canvas', written straight into the slot
+            preprocess.adjust_K_device(K_per_image.to(torch.float64), geom, out=self.K_slot[s])
         K_per_image = self.K_slot[s]
         self.ev_a[s].record(main)
         side = self.sides[s % len(self.sides)]
@@ -152,6 +159,8 @@ class Detect3DPipeline(object):
             d = self.det[s]
             rec = rdist.pack_records(d.n, d.cls, d.score, d.mproj, d.verts, d.bbox, self.topk,
                                      self.boxes[s] if self.decode3d else None, out=self.rec_local[s])
+            if geom is not None:
+                preprocess.records_to_camera(rec, geom)
             if self.time_gather:
                 self.ev_g0[s].record(side)
             self.rec[s] = rdist.all_gather_records(rec, always=self.gather == 'always',

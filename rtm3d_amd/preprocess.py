@@ -143,3 +143,65 @@ def preprocess_batch(images, size, mean, std, resize_to=None, out=None, model=No
                                               sums.data_ptr()), 'preprocess_batch')
     pads = [((W - int(w)) // 2, (H - int(h)) // 2) for h, w in rhw]
     return ret, pads, [(int(h), int(w)) for h, w in rhw]
+
+
+# ------------------------------------------------------------------------------------------------ camera-frame bookkeeping
+def frame_geometry(hw, size, resize_to=None):
+    """rtm3d_frame_geometry (host, no device): per frame (h, w) its size after Resize and its centred place on the (H, W)
+    canvas - ``resized_size`` and the pad rule of ``preprocess_batch`` - as the ctypes array of ``_lib.FrameGeom`` that the
+    device entries below take.  A frame that does not fit is a ValueError naming it, like ``preprocess_batch``'s."""
+    lib = _lib.load()
+    hw = np.ascontiguousarray(np.asarray(hw, np.int32).reshape(-1, 2))
+    geom = (_lib.FrameGeom * len(hw))()
+    if lib.rtm3d_frame_geometry(len(hw), hw.ctypes.data_as(ctypes.c_void_p), int(resize_to or 0), int(size[0]), int(size[1]), geom) != 0:
+        raise ValueError(lib.rtm3d_last_error().decode())
+    return geom
+
+
+def adjust_K_device(K_camera, geom, out=None):
+    """``adjust_K(resize_K(K, (h, w), (h', w')), pad_w, pad_h)`` per image on the device (rtm3d_frames_adjust_k, fp64, the same
+    operation order, bit for bit): K_camera (B, 9) float64 CUDA tensor of the cameras' own intrinsics, geom =
+    ``frame_geometry(...)``.  Stream-ordered, no host-to-device copy.  Returns the (B, 9) intrinsics of the network canvas."""
+    lib = _lib.load()
+    B = len(geom)
+    if not isinstance(K_camera, torch.Tensor) or not K_camera.is_cuda or K_camera.dtype != torch.float64 or K_camera.numel() != B * 9:
+        raise ValueError('K_camera must be a float64 CUDA tensor with %d x 9 intrinsics' % B)
+    dev = K_camera.device
+    K_camera = K_camera.contiguous()
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(B, 9, dtype=torch.float64, device=dev)
+        if out.dtype != torch.float64 or out.numel() != B * 9 or not out.is_contiguous() or out.device != dev:
+            raise ValueError('out must be a contiguous float64 tensor of %d x 9 on %s' % (B, dev))
+        _lib.check(lib.rtm3d_frames_adjust_k(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), B, geom, K_camera.data_ptr(),
+                                             out.data_ptr()), 'frames_adjust_K')
+    return out
+
+
+def records_to_camera(rec, geom, K_camera=None, boxes=None, kitti=False):
+    """Un-letterbox detection records IN PLACE (rtm3d_records_to_camera): rec (B, topk, 32) fp32 CUDA records of
+    ``distributed.pack_records`` in canvas pixels -> the same records with key point, vertices and 2D box in the pixels of
+    each camera frame.  kitti=True (needs K_camera, the cameras' own (B, 9) float64 intrinsics, and boxes, the
+    ``model_utils.Boxes3D`` the records were packed from): also returns (B, topk, 16) float64 rows, the numbers of a KITTI
+    label line per kept box (``kitti_results.kitti_label_values`` + flag), zeros elsewhere.  Returns rec or (rec, rows)."""
+    from .model_utils import FUN_ACCEPT
+    lib = _lib.load()
+    B = len(geom)
+    if not isinstance(rec, torch.Tensor) or not rec.is_cuda or rec.dtype != torch.float32 or rec.dim() != 3 or rec.shape[0] != B or \
+            rec.shape[2] != 32 or not rec.is_contiguous():
+        raise ValueError('rec must be a contiguous fp32 CUDA tensor (%d, topk, 32)' % B)
+    dev, topk = rec.device, int(rec.shape[1])
+    rows, args = None, [None] * 4
+    if kitti:
+        if K_camera is None or boxes is None:
+            raise ValueError('the KITTI rows need K_camera and the solver outputs (boxes)')
+        K_camera = torch.as_tensor(K_camera, dtype=torch.float64, device=dev).reshape(B, 9).contiguous()
+        if boxes.x.shape[0] != B * topk:
+            raise ValueError('boxes hold %d slots, the records %d' % (boxes.x.shape[0], B * topk))
+        args = [K_camera.data_ptr(), boxes.x.data_ptr(), boxes.fun.data_ptr(), boxes.status.data_ptr()]
+    with torch.cuda.device(dev):
+        if kitti:
+            rows = torch.empty(B, topk, 16, dtype=torch.float64, device=dev)
+        _lib.check(lib.rtm3d_records_to_camera(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), B, topk, geom, rec.data_ptr(),
+                                               *args, float(FUN_ACCEPT), rows.data_ptr() if kitti else None), 'records_to_camera')
+    return (rec, rows) if kitti else rec
