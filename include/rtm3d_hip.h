@@ -582,6 +582,45 @@ size_t rtm3d_engine_frames_workspace_bytes(rtm3d_ctx* ctx);
 int rtm3d_engine_detect_frames(rtm3d_ctx* ctx, void* stream, const uint8_t* const* h_imgs, const int* h_hw,
                                const double* d_K_camera, float* d_rec, double* d_kitti, void* d_workspace);
 
+/* ------------------------------------------------------------------ box overlaps (csrc/box_overlap.hip)
+ * Rotated-box overlaps in the ground plane and 3D non-maximum suppression of detection records.  Added in ABI 9 without
+ * changing any existing declaration; nothing calls these unless the caller does (no plan, engine file or record changes).
+ *
+ * BOX: 7 values in the order of record fields [24:31] - h, w, l, X, Y, Z, ry.  (X, Y, Z) is the box CENTRE in camera
+ * coordinates (y down), as rtm3d_pack_records writes it (a KITTI label line carries the bottom face instead: y + h / 2).
+ * The footprint lies in the x-z plane: half extents l / 2 along local x and w / 2 along local z, rotated by
+ * R = [[c,0,s],[0,1,0],[-s,0,c]] with plain c = cos(ry), s = sin(ry) - NOT the rotation_matrix of the reference's drawing
+ * code, which snaps |s|, |c| < 1e-3 to zero.  Vertical extent [Y - h / 2, Y + h / 2].
+ * ARITHMETIC: fp64 throughout, one fixed operation order for both entry points, compiled without contraction.  The BEV
+ * intersection is rectangle A clipped against the four half-planes of B (Sutherland-Hodgman, at most 8 vertices) with CLOSED
+ * inside tests (>= 0): identical boxes, boxes sharing an edge and nested boxes give the exact intersection, not an empty
+ * polygon.  3D intersection = BEV intersection * overlap of the vertical extents.  A box with h, w or l <= 0 or with any
+ * non-finite value overlaps nothing (0); a denominator of 0 gives 0; no result is NaN.
+ *
+ * rtm3d_box_overlaps: per image two ragged lists d_a [B][cap_a][7], d_b [B][cap_b][7] with d_na[B], d_nb[B] valid entries.
+ * criterion: 0 = intersection / union, 1 = intersection / size of a, 2 = intersection / size of b (KITTI's -1 / 0 / 1 cases);
+ * "size" is the footprint area for d_bev and the volume for d_3d.  Outputs [B][cap_a][cap_b] fp64, either may be NULL (not
+ * both); entries with i >= d_na[image] or j >= d_nb[image] are written as 0, so the outputs are fully defined.  One lane per
+ * pair, one launch.  (The matrices are the part of a KITTI BEV / 3D evaluation that needs the device; difficulty filtering,
+ * matching and the AP integral are not in this library.)
+ *
+ * rtm3d_records_nms3d: greedy NMS in place on B * topk * 32 records (rtm3d_pack_records, before or after
+ * rtm3d_records_to_camera, local or all-gathered: B is just the number of images).  Candidates are the slots with flag
+ * [31] == 2; their boxes are fields [24:31] widened to fp64 (exact), so the arithmetic is that of rtm3d_box_overlaps on
+ * (double)rec[24:31].  Slots are score-descending within an image (rtm3d_decode2d; ties by flat index): slot i survives if
+ * no SURVIVING slot j < i has IoU STRICTLY GREATER than iou_thresh with it.  metric: 0 = BEV IoU, 1 = 3D IoU.
+ * class_aware != 0: only boxes of the same class [0] suppress each other.  A suppressed slot's flag goes 2 -> 1 and nothing
+ * else of the record changes, so it still reads as "a detection" (> 0) and no longer as "3D kept" (> 1).  NOTE: a flag-1
+ * slot may therefore carry a 3D box in [24:31] that is not kept - as it already may after rtm3d_pack_records, which writes
+ * the solver's output of a solved-but-rejected slot (fun >= fun_accept) into those fields.  d_kitti (NULL or the B * topk *
+ * 16 rows of rtm3d_records_to_camera): the row of a suppressed slot is zeroed, that array's rule for not-kept slots.
+ * One workgroup per image; topk > 256 is refused.  Stream-ordered: one kernel, no host synchronisation, no memset / memcpy
+ * node, no allocation.                                                                                                      */
+int rtm3d_box_overlaps(void* stream, int B, int cap_a, int cap_b, const int32_t* d_na, const int32_t* d_nb,
+                       const double* d_a, const double* d_b, int criterion, double* d_bev, double* d_3d);
+int rtm3d_records_nms3d(void* stream, int B, int topk, float* d_rec, double iou_thresh, int metric, int class_aware,
+                        double* d_kitti);
+
 #ifdef __cplusplus
 }
 #endif

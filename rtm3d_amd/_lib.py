@@ -160,6 +160,9 @@ SIGNATURES = {
     'rtm3d_engine_set_frame_params': (c_int, [c_void_p, ctypes.POINTER(FrameParams)]),
     'rtm3d_engine_frames_workspace_bytes': (c_size_t, [c_void_p]),
     'rtm3d_engine_detect_frames': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # box overlaps / 3D NMS of records (rtm3d_amd/box_overlap.py)
+    'rtm3d_box_overlaps': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'rtm3d_records_nms3d': (c_int, [c_void_p, c_int, c_int, c_void_p, c_double, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -391,9 +391,12 @@ class Engine(object):
                                               ctypes.c_void_p(x.data_ptr()), ptrs), 'forward')
         return tuple(outs)
 
-    def detect(self, x, K_per_image, out=None):
+    def detect(self, x, K_per_image, out=None, nms3d=None):
         """One detect step (rtm3d_engine_detect): (B, topk, 32) fp32 records, the layout of Detect3DPipeline.results.
-        K_per_image: (B, 9) intrinsics (fp64 on the device)."""
+        K_per_image: (B, 9) intrinsics (fp64 on the device).  nms3d: None | IoU threshold | dict of
+        box_overlap.nms3d_records' keywords: 3D NMS of the returned records (one more launch behind the step)."""
+        from . import box_overlap
+        nms3d = box_overlap.nms3d_options(nms3d)
         import torch
         x = self._input(x)
         B, topk = self.info['B'], self.info['topk']
@@ -404,6 +407,8 @@ class Engine(object):
                                                     ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(K.data_ptr()),
                                                     ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(self.workspace.data_ptr())),
                        'engine_detect')
+            if nms3d is not None:
+                box_overlap.nms3d_records(rec, **nms3d)
         return rec
 
     def set_frame_params(self, mean, std, resize_to=None):
@@ -417,11 +422,14 @@ class Engine(object):
             self.frames_workspace = torch.empty(int(self.lib.rtm3d_engine_frames_workspace_bytes(self.ctx)), dtype=torch.uint8,
                                                 device=self.device)
 
-    def detect_frames(self, images, K_camera, kitti=False, out=None):
+    def detect_frames(self, images, K_camera, kitti=False, out=None, nms3d=None):
         """One detect step fed by camera frames (rtm3d_engine_detect_frames): images = list of B uint8 (h, w, 3) CUDA tensors of
         any sizes that fit the canvas after Resize, K_camera = the cameras' own (B, 9) intrinsics.  Returns the (B, topk, 32)
-        records with their 2D fields in the pixels of each frame; kitti=True: (records, (B, topk, 16) float64 KITTI rows)."""
+        records with their 2D fields in the pixels of each frame; kitti=True: (records, (B, topk, 16) float64 KITTI rows).
+        nms3d: as for detect; applied to the records and, with kitti=True, to the rows (a suppressed slot's row is zeroed)."""
         import torch
+        from . import box_overlap
+        nms3d = box_overlap.nms3d_options(nms3d)
         B, topk = self.info['B'], self.info['topk']
         if getattr(self, 'frames_workspace', None) is None:
             raise RuntimeError('Engine.detect_frames: call set_frame_params(mean, std, resize_to) first')
@@ -442,6 +450,8 @@ class Engine(object):
                                                            ptrs, hw, ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
                                                            ctypes.c_void_p(rows.data_ptr()) if kitti else None,
                                                            ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames')
+            if nms3d is not None:
+                box_overlap.nms3d_records(rec, kitti_rows=rows, **nms3d)
         return (rec, rows) if kitti else rec
 
     def close(self):

@@ -5,7 +5,7 @@ work on thousands of workgroups.  Running them on two HIP streams lets the decod
 idle issue slots while batch i+1's backbone is already running:
 
     main stream : forward(i) -> decode2d(i) -> [event A_i] ............. forward(i+1) -> ...
-    side stream :                               wait A_i -> decode3d(i) -> pack -> all-gather(i) -> [event B_i]
+    side stream :                               wait A_i -> decode3d(i) -> pack [-> nms3d] -> all-gather(i) -> [event B_i]
 
 Outputs are multi-buffered (slot i % depth); the main stream waits for B_{i-depth} before decode2d
 overwrites slot i % depth.  No host synchronisation inside; `results(i)` hands out the records of a
@@ -26,6 +26,7 @@ from .model import Detections
 from .model_utils import Boxes3D, decode3d_slots
 from . import distributed as rdist
 from . import preprocess
+from . import box_overlap
 
 
 SMALL_BATCH = 2      # batches whose 3D decode (a serial fp64 iteration per object, ~1 ms) is about as long as the network
@@ -33,8 +34,11 @@ SMALL_BATCH = 2      # batches whose 3D decode (a serial fp64 iteration per obje
 
 class Detect3DPipeline(object):
     def __init__(self, model, batch, device, dim_ref=None, ref_loc=(0.0, -0.5, 20.0), gather=True, depth=None, decode3d=True,
-                 side_cus=0, side_streams=None, sparse_heads=False, solver_form=None, head_precision=None):
+                 side_cus=0, side_streams=None, sparse_heads=False, solver_form=None, head_precision=None, nms3d=None):
         self.model, self.B, self.dev = model, batch, torch.device(device)
+        # nms3d: None | IoU threshold | dict of box_overlap.nms3d_records' keywords: 3D NMS of each step's records on the side
+        # stream, behind pack_records (one more launch; None issues nothing)
+        self.nms3d = box_overlap.nms3d_options(nms3d)
         # sparse_heads: this call surface hands out detection records, never the dense logits, so the regression branches are
         # evaluated at the detected peaks only (Model.decode2d_sparse); the records agree with the dense path's to fp16 round-off
         self.sparse_heads = bool(sparse_heads)
@@ -159,6 +163,8 @@ class Detect3DPipeline(object):
             d = self.det[s]
             rec = rdist.pack_records(d.n, d.cls, d.score, d.mproj, d.verts, d.bbox, self.topk,
                                      self.boxes[s] if self.decode3d else None, out=self.rec_local[s])
+            if self.nms3d is not None:
+                box_overlap.nms3d_records(rec, **self.nms3d)
             if geom is not None:
                 preprocess.records_to_camera(rec, geom)
             if self.time_gather:
