@@ -601,8 +601,8 @@ int rtm3d_engine_detect_frames(rtm3d_ctx* ctx, void* stream, const uint8_t* cons
  * criterion: 0 = intersection / union, 1 = intersection / size of a, 2 = intersection / size of b (KITTI's -1 / 0 / 1 cases);
  * "size" is the footprint area for d_bev and the volume for d_3d.  Outputs [B][cap_a][cap_b] fp64, either may be NULL (not
  * both); entries with i >= d_na[image] or j >= d_nb[image] are written as 0, so the outputs are fully defined.  One lane per
- * pair, one launch.  (The matrices are the part of a KITTI BEV / 3D evaluation that needs the device; difficulty filtering,
- * matching and the AP integral are not in this library.)
+ * pair, one launch.  (These matrices feed the BEV / 3D scores of the KITTI evaluation: rtm3d_kitti_match below does the matching
+ * on them, rtm3d_amd/kitti_eval.py the difficulty filtering and the AP integral.)
  *
  * rtm3d_records_nms3d: greedy NMS in place on B * topk * 32 records (rtm3d_pack_records, before or after
  * rtm3d_records_to_camera, local or all-gathered: B is just the number of images).  Candidates are the slots with flag
@@ -620,6 +620,56 @@ int rtm3d_box_overlaps(void* stream, int B, int cap_a, int cap_b, const int32_t*
                        const double* d_a, const double* d_b, int criterion, double* d_bev, double* d_3d);
 int rtm3d_records_nms3d(void* stream, int B, int topk, float* d_rec, double iou_thresh, int metric, int class_aware,
                         double* d_kitti);
+
+/* ------------------------------------------------------------------ KITTI evaluation (csrc/kitti_eval.hip)
+ * The device side of the KITTI object-detection AP protocol (bbox / BEV / 3D / AOS); the host side - label files, difficulty
+ * filtering, score thresholds, the AP integral - is rtm3d_amd/kitti_eval.py.  Added in ABI 9 without changing any existing
+ * declaration; nothing calls these unless the caller does.  The protocol is restated from the published devkit's behaviour;
+ * that program was not available to compare against, so parity with it is UNPINNED: the contract is the rules written here.
+ * Both entry points are stream-ordered: one kernel, no host synchronisation, no memset / memcpy node, no allocation.
+ *
+ * rtm3d_rect_overlaps: pairwise overlaps of axis-aligned image rectangles (x1, y1, x2, y2), layout as rtm3d_box_overlaps:
+ * d_a [B][cap_a][4], d_b [B][cap_b][4], d_na[B], d_nb[B] valid entries, d_out [B][cap_a][cap_b] fp64; entries with
+ * i >= d_na[image] or j >= d_nb[image] are written as 0.  fp64 in this order, compiled without contraction:
+ *   w = fmin(ax2, bx2) - fmax(ax1, bx1);  h = fmin(ay2, by2) - fmax(ay1, by1);  w <= 0 or h <= 0 -> 0;
+ *   inter = w * h;  sa = (ax2 - ax1) * (ay2 - ay1);  sb = (bx2 - bx1) * (by2 - by1);
+ *   criterion 0: inter / ((sa + sb) - inter)   1: inter / sa   2: inter / sb.
+ * A rectangle with a coordinate that is not finite overlaps nothing (0); a denominator that is zero or not finite gives 0,
+ * and so does a quotient that is not finite: no result is NaN or infinite.  There is no "+1" pixel convention.
+ *
+ * rtm3d_kitti_match: the greedy matching.  It computes no overlap itself: d_overlap [n_frames][cap_d][cap_g] fp64 is one
+ * matrix per frame (detection x ground truth) of whatever metric.  One ITEM is one (frame, group): item = frame * n_groups +
+ * group, a group being one (class, difficulty).  cap_d <= 256, more is refused; cap_g is not limited.
+ *   d_nd / d_ng [n_frames]           detections / ground truths of the frame (entries beyond them are never read)
+ *   d_gflag [n_frames][n_groups][cap_g], d_dflag [n_frames][n_groups][cap_d]   int8: 0 counted, 1 ignored, -1 other class
+ *   d_score [n_frames][cap_d]        fp64 detection scores; they must be finite
+ *   d_dc_hit [n_frames][n_groups][cap_d] or NULL   uint8, 1: the detection overlaps a DontCare region beyond min_overlap
+ *   d_alpha_g [n_frames][cap_g], d_alpha_d [n_frames][cap_d], both or neither   observation angles (AOS only)
+ *   d_min_overlap [n_groups]         fp64, >= 0
+ * The ground truths of an item are walked in index order; one with flag -1 is skipped.  ELIGIBLE for a ground truth g: the
+ * detections that are not assigned yet, have flag != -1 and overlap[d][g] > min_overlap (strict).
+ * mode 0, SCORES (the devkit's compute_fp = false), one wavefront per item.  Candidate: the eligible detection of highest
+ * score; strict >, so the lowest index wins a tie.  No candidate: a miss.  A candidate and (gflag == 1 or its dflag == 1): the
+ * detection becomes assigned, nothing is counted.  Otherwise a true positive: the detection becomes assigned and its score
+ * is written to d_match_score[item][g].  Every other entry of d_match_score [n_frames][n_groups][cap_g] is -infinity.
+ * max_thr and the counts-mode pointers are not used.
+ * mode 1, COUNTS (compute_fp = true), one wavefront per (item, k), k < d_nthr[group] <= max_thr, with the threshold
+ * t = d_thr[group][k] of d_thr [n_groups][max_thr]: detections with score < t (strict) do not exist.  Candidate: if any
+ * eligible detection has flag 0, the one of largest overlap among those (strict >: lowest index at a tie); otherwise the
+ * lowest-index eligible detection with flag 1 - the closed form of the devkit's sequential max_overlap /
+ * assigned_ignored_det update.  Miss / assign-only / true positive as in scores mode; a true positive adds
+ * (1 + cos(alpha_g - alpha_d)) / 2 to the item's similarity (0 without the angles).  After the walk, the false positives are
+ * the detections with flag 0, score >= t, not assigned and not d_dc_hit.
+ * Outputs: d_tp / d_fp / d_fn [n_groups][max_thr] int32 are ADDED TO (vector atomics; the caller zeroes them, and may run
+ * several frame chunks into the same arrays); d_sim [n_frames][n_groups][max_thr] fp64 holds the similarity of every
+ * (item, k), 0 for k >= d_nthr[group], for the caller to sum.  d_match_score is not used.                                 */
+int rtm3d_rect_overlaps(void* stream, int B, int cap_a, int cap_b, const int32_t* d_na, const int32_t* d_nb,
+                        const double* d_a, const double* d_b, int criterion, double* d_out);
+int rtm3d_kitti_match(void* stream, int mode, int n_frames, int n_groups, int cap_d, int cap_g, const int32_t* d_nd,
+                      const int32_t* d_ng, const int8_t* d_gflag, const int8_t* d_dflag, const double* d_score,
+                      const uint8_t* d_dc_hit, const double* d_alpha_g, const double* d_alpha_d, const double* d_overlap,
+                      const double* d_min_overlap, double* d_match_score, int max_thr, const int32_t* d_nthr,
+                      const double* d_thr, int32_t* d_tp, int32_t* d_fp, int32_t* d_fn, double* d_sim);
 
 #ifdef __cplusplus
 }

@@ -163,6 +163,9 @@ SIGNATURES = {
     # box overlaps / 3D NMS of records (rtm3d_amd/box_overlap.py)
     'rtm3d_box_overlaps': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'rtm3d_records_nms3d': (c_int, [c_void_p, c_int, c_int, c_void_p, c_double, c_int, c_int, c_void_p]),
+    # KITTI evaluation (rtm3d_amd/kitti_eval.py)
+    'rtm3d_rect_overlaps': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'rtm3d_kitti_match': (c_int, [c_void_p] + [c_int] * 5 + [c_void_p] * 11 + [c_int] + [c_void_p] * 6),
 }
 
 _lib = None

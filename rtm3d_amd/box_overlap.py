@@ -5,8 +5,8 @@ coordinates (y down), the footprint l x w in the x-z plane rotated by plain cos(
 unlike ``kitti_results.rotation_matrix``), the vertical extent [Y - h/2, Y + h/2].  Everything is fp64 on the device; the
 conventions are stated in include/rtm3d_hip.h, "box overlaps".
 
-``overlaps`` gives the pairwise BEV / 3D overlap matrices a KITTI-style evaluation is built on (the part of it that needs the
-device; difficulty filtering, matching and the AP integral are not here).  ``nms3d_records`` removes duplicate 3D boxes from
+``overlaps`` gives the pairwise BEV / 3D overlap matrices the KITTI evaluation is built on (``rtm3d_amd.kitti_eval``: difficulty
+filtering, device-side matching and the AP integral).  ``nms3d_records`` removes duplicate 3D boxes from
 the (B, topk, 32) records of ``distributed.pack_records`` in place: a suppressed slot's flag goes 2 -> 1.
 Device tensors only: there is no CPU path.
 """
