@@ -350,6 +350,26 @@ int rtm3d_preprocess_batch(void* stream, int B, const uint8_t* const* h_imgs, co
                            void* d_out, int out_mode, int H, int W, int out_border, const float* d_lut, const void* d_lut16,
                            unsigned long long* d_sums);
 
+/* The schedule rtm3d_preprocess_batch gives a batch, from the host-side sizes alone (HOST function, no device access; added
+ * without changing any existing declaration).  The batch runs in sub-batches of 64 images; out[(B + 63) / 64] receives one
+ * entry per sub-batch - the very numbers the launcher uses, it calls the same function.  An image with a side < 1 or one
+ * that does not fit the canvas, and a resized width whose column table does not fit the LDS (rw > 7500), are refused with
+ * the launcher's own message.  rtm3d_preprocess_batch validates the WHOLE batch this way (and every image pointer) before
+ * its first memset or launch: a refused call has launched nothing.
+ * A band of band_rows resized rows is staged in LDS iff its source span fits: (yhi - ylo + 1) * w * 3 + 15 <= stage_bytes
+ * (ylo .. yhi: the source rows the band's first and last row interpolate from); otherwise it gathers from global memory.
+ * A workgroup takes more than one band when bands > grid_x.                                                          */
+typedef struct rtm3d_preprocess_plan {
+    int first, count;                      /* images first .. first + count - 1 */
+    int col_bytes;                         /* LDS column-coefficient table: widest resized row x 8 B, rounded up to 16 */
+    int stage_bytes;                       /* LDS stage of source rows behind it */
+    int band_rows;                         /* resized rows per band */
+    int bands;                             /* bands of the tallest resized image */
+    int grid_x;                            /* interior launch: grid (grid_x, count) x 256 threads, col_bytes + stage_bytes of dynamic LDS */
+    int border_grid_x;                     /* border launch: grid (border_grid_x, count) x 256; 0 = every image fills the canvas, no launch */
+} rtm3d_preprocess_plan;
+int rtm3d_preprocess_batch_plan(int B, const int* h_hw, const int* h_resized_hw, int H, int W, rtm3d_preprocess_plan* out);
+
 /* Device address and geometry of the plan's 4-channel fp16 input tensor (written by rtm3d_op_input_nhwc4 from the caller's
  * fp32 batch, or directly by rtm3d_preprocess_batch in out_mode 1, after which rtm3d_forward is called with d_in == NULL
  * and skips the conversion).  Fails if the plan has no such tensor.                                                  */

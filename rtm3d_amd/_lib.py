@@ -77,6 +77,12 @@ class FrameParams(ctypes.Structure):
     _fields_ = [('mean', c_float * 3), ('std', c_float * 3), ('resize_to', c_int)]
 
 
+class PreprocessPlan(ctypes.Structure):
+    """Mirror of struct rtm3d_preprocess_plan (one per sub-batch of 64 images)."""
+    _fields_ = [('first', c_int), ('count', c_int), ('col_bytes', c_int), ('stage_bytes', c_int), ('band_rows', c_int), ('bands', c_int),
+                ('grid_x', c_int), ('border_grid_x', c_int)]
+
+
 # name -> (restype, argtypes); also the list of symbols include/rtm3d_hip.h declares
 SIGNATURES = {
     'rtm3d_last_error': (ctypes.c_char_p, []),
@@ -125,6 +131,7 @@ SIGNATURES = {
     'rtm3d_preprocess': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'rtm3d_preprocess_batch': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p]),
+    'rtm3d_preprocess_batch_plan': (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(PreprocessPlan)]),
     'rtm3d_input_tensor': (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                                    ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'rtm3d_stream_create_cumask': (c_int, [c_int, c_int, ctypes.POINTER(c_void_p)]),

@@ -238,55 +238,87 @@ __global__ __launch_bounds__(256) void pre_border_kernel(const PreBatch pb, void
     }
 }
 
+// The schedule of one sub-batch (images b0 .. b0 + nb - 1), from the host's sizes alone: what rtm3d_preprocess_batch launches and
+// what rtm3d_preprocess_batch_plan reports.  Refuses (error set, 1) an image that does not fit and a column table beyond the LDS.
+static int pre_plan_sub(int b0, int nb, const int* h_hw, const int* h_resized_hw, int H, int W, rtm3d_preprocess_plan* p) {
+    int max_border = 0, max_rh = 0, max_rw = 0, max_w = 0;
+    double max_scale = 0.0;
+    for (int i = 0; i < nb; ++i) {
+        const int h = h_hw[2 * (b0 + i)], w = h_hw[2 * (b0 + i) + 1];
+        const int rh = h_resized_hw ? h_resized_hw[2 * (b0 + i)] : h, rw = h_resized_hw ? h_resized_hw[2 * (b0 + i) + 1] : w;
+        if (h < 1 || w < 1 || rh < 1 || rw < 1 || rh > H || rw > W) {
+            rt_set_error("preprocess_batch: image %d (%dx%d -> %dx%d) does not fit the %dx%d canvas", b0 + i, h, w, rh, rw, H, W);
+            return 1;
+        }
+        max_rh = rh > max_rh ? rh : max_rh; max_rw = rw > max_rw ? rw : max_rw; max_w = w > max_w ? w : max_w;
+        max_scale = (double)h / rh > max_scale ? (double)h / rh : max_scale;
+        max_border = H * W - rh * rw > max_border ? H * W - rh * rw : max_border;
+    }
+    // bands of rows per workgroup: the stage holds (band_rows * scale + 2) source rows of the widest image; 48 KB of stage
+    // leave room for two workgroups per CU.  About 8 workgroups per CU over the sub-batch.
+    const int col_bytes = (int)(((size_t)max_rw * sizeof(int2) + 15) & ~(size_t)15);
+    if (col_bytes > 60000) { rt_set_error("preprocess_batch: resized width %d exceeds the kernel's column table", max_rw); return 1; }
+    int stage_bytes = 64 * 1024 - 8 * 1024 - col_bytes;            // total dynamic + static LDS stays under 64 KB
+    stage_bytes = stage_bytes < 0 ? 0 : (stage_bytes > 48 * 1024 ? 48 * 1024 : stage_bytes);
+    const size_t row_bytes = (size_t)max_w * 3;
+    const int cap_rows = (int)((stage_bytes > 15 ? stage_bytes - 15 : 0) / (row_bytes ? row_bytes : 1));
+    int band_rows = (int)((cap_rows - 2) / (max_scale > 1.0 ? max_scale : 1.0));
+    band_rows = band_rows < 1 ? 1 : (band_rows > 16 ? 16 : band_rows);
+    int bx = (2048 + nb - 1) / nb;
+    const int bands = (max_rh + band_rows - 1) / band_rows;
+    bx = bx > bands ? bands : bx;
+    bx = bx < 1 ? 1 : bx;
+    int gx = 0;
+    if (max_border > 0) {
+        gx = (max_border + 255) / 256;
+        gx = gx > 256 ? 256 : gx;
+    }
+    p->first = b0; p->count = nb;
+    p->col_bytes = col_bytes; p->stage_bytes = stage_bytes; p->band_rows = band_rows; p->bands = bands;
+    p->grid_x = bx; p->border_grid_x = gx;
+    return 0;
+}
+
+extern "C" int rtm3d_preprocess_batch_plan(int B, const int* h_hw, const int* h_resized_hw, int H, int W, rtm3d_preprocess_plan* out) {
+    if (B < 1 || !h_hw || !out) { rt_set_error("preprocess_batch_plan: bad arguments"); return 1; }
+    for (int b0 = 0; b0 < B; b0 += PRE_MAX_BATCH)
+        if (pre_plan_sub(b0, B - b0 < PRE_MAX_BATCH ? B - b0 : PRE_MAX_BATCH, h_hw, h_resized_hw, H, W, &out[b0 / PRE_MAX_BATCH])) return 1;
+    return 0;
+}
+
 extern "C" int rtm3d_preprocess_batch(void* stream, int B, const uint8_t* const* h_imgs, const int* h_hw, const int* h_resized_hw,
                                       void* d_out, int out_mode, int H, int W, int out_border, const float* d_lut,
                                       const void* d_lut16, unsigned long long* d_sums) {
     if (B < 1 || !h_imgs || !h_hw || !d_out || !d_lut || !d_sums) { rt_set_error("preprocess_batch: bad arguments"); return 1; }
     if (out_mode != 0 && out_mode != 1) { rt_set_error("preprocess_batch: out_mode must be 0 (fp32 NCHW) or 1 (fp16 NHWC4)"); return 1; }
-    if (out_mode == 1 && (!d_lut16 || out_border < 0)) { rt_set_error("preprocess_batch: the NHWC4 output needs the fp16 table and a border >= 0"); return 1; }
+    if (out_mode == 1 && !d_lut16) { rt_set_error("preprocess_batch: the NHWC4 output needs the fp16 table"); return 1; }
+    if (out_mode == 1 && out_border < 0) { rt_set_error("preprocess_batch: the NHWC4 output needs a border >= 0, not %d", out_border); return 1; }
+    // all or nothing: every image and every sub-batch is checked before the first memset or launch
+    rtm3d_preprocess_plan plan;
+    for (int b = 0; b < B; ++b)
+        if (!h_imgs[b]) { rt_set_error("preprocess_batch: image %d is a null pointer", b); return 1; }
+    for (int b0 = 0; b0 < B; b0 += PRE_MAX_BATCH)
+        if (pre_plan_sub(b0, B - b0 < PRE_MAX_BATCH ? B - b0 : PRE_MAX_BATCH, h_hw, h_resized_hw, H, W, &plan)) return 1;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(d_sums, 0, (size_t)B * 3 * sizeof(unsigned long long), s) != hipSuccess) { rt_set_error("preprocess_batch: memset failed"); return 1; }
     for (int b0 = 0; b0 < B; b0 += PRE_MAX_BATCH) {
         const int nb = B - b0 < PRE_MAX_BATCH ? B - b0 : PRE_MAX_BATCH;
+        if (pre_plan_sub(b0, nb, h_hw, h_resized_hw, H, W, &plan)) return 1;      // (cannot refuse any more)
         PreBatch pb;
-        int max_border = 0, max_rh = 0, max_rw = 0, max_w = 0;
-        double max_scale = 0.0;
         for (int i = 0; i < nb; ++i) {
-            const int h = h_hw[2 * (b0 + i)], w = h_hw[2 * (b0 + i) + 1];
-            const int rh = h_resized_hw ? h_resized_hw[2 * (b0 + i)] : h, rw = h_resized_hw ? h_resized_hw[2 * (b0 + i) + 1] : w;
-            if (!h_imgs[b0 + i] || h < 1 || w < 1 || rh < 1 || rw < 1 || rh > H || rw > W) {
-                rt_set_error("preprocess_batch: image %d (%dx%d -> %dx%d) does not fit the %dx%d canvas", b0 + i, h, w, rh, rw, H, W);
-                return 1;
-            }
-            pb.img[i] = h_imgs[b0 + i]; pb.h[i] = h; pb.w[i] = w; pb.rh[i] = rh; pb.rw[i] = rw;
-            max_rh = rh > max_rh ? rh : max_rh; max_rw = rw > max_rw ? rw : max_rw; max_w = w > max_w ? w : max_w;
-            max_scale = (double)h / rh > max_scale ? (double)h / rh : max_scale;
-            max_border = H * W - rh * rw > max_border ? H * W - rh * rw : max_border;
+            pb.img[i] = h_imgs[b0 + i]; pb.h[i] = h_hw[2 * (b0 + i)]; pb.w[i] = h_hw[2 * (b0 + i) + 1];
+            pb.rh[i] = h_resized_hw ? h_resized_hw[2 * (b0 + i)] : pb.h[i]; pb.rw[i] = h_resized_hw ? h_resized_hw[2 * (b0 + i) + 1] : pb.w[i];
         }
         // offsets of this sub-batch in the outputs
         void* o = out_mode == 0 ? (void*)((float*)d_out + (size_t)b0 * 3 * H * W)
                                 : (void*)((f16*)d_out + (size_t)b0 * (H + 2 * out_border) * (W + 2 * out_border) * 4);
         unsigned long long* sm = d_sums + (size_t)b0 * 3;
-        // bands of rows per workgroup: the stage holds (band_rows * scale + 2) source rows of the widest image; 48 KB of stage
-        // leave room for two workgroups per CU.  About 8 workgroups per CU over the sub-batch.
-        const int col_bytes = (int)(((size_t)max_rw * sizeof(int2) + 15) & ~(size_t)15);
-        if (col_bytes > 60000) { rt_set_error("preprocess_batch: resized width %d exceeds the kernel's column table", max_rw); return 1; }
-        int stage_bytes = 64 * 1024 - 8 * 1024 - col_bytes;            // total dynamic + static LDS stays under 64 KB
-        stage_bytes = stage_bytes < 0 ? 0 : (stage_bytes > 48 * 1024 ? 48 * 1024 : stage_bytes);
-        const size_t row_bytes = (size_t)max_w * 3;
-        const int cap_rows = (int)((stage_bytes > 15 ? stage_bytes - 15 : 0) / (row_bytes ? row_bytes : 1));
-        int band_rows = (int)((cap_rows - 2) / (max_scale > 1.0 ? max_scale : 1.0));
-        band_rows = band_rows < 1 ? 1 : (band_rows > 16 ? 16 : band_rows);
-        int bx = (2048 + nb - 1) / nb;
-        const int bands = (max_rh + band_rows - 1) / band_rows;
-        bx = bx > bands ? bands : bx;
-        bx = bx < 1 ? 1 : bx;
+        const int bx = plan.grid_x, band_rows = plan.band_rows, col_bytes = plan.col_bytes, stage_bytes = plan.stage_bytes;
         const size_t dyn = (size_t)col_bytes + stage_bytes;
         if (out_mode == 0) hipLaunchKernelGGL(pre_interior_kernel<0>, dim3(bx, nb), dim3(256), dyn, s, pb, o, H, W, out_border, d_lut, (const f16*)d_lut16, sm, band_rows, col_bytes, stage_bytes);
         else hipLaunchKernelGGL(pre_interior_kernel<1>, dim3(bx, nb), dim3(256), dyn, s, pb, o, H, W, out_border, d_lut, (const f16*)d_lut16, sm, band_rows, col_bytes, stage_bytes);
-        if (max_border > 0) {
-            int gx = (max_border + 255) / 256;
-            gx = gx > 256 ? 256 : gx;
+        if (plan.border_grid_x > 0) {
+            const int gx = plan.border_grid_x;
             if (out_mode == 0) hipLaunchKernelGGL(pre_border_kernel<0>, dim3(gx, nb), dim3(256), 0, s, pb, o, H, W, out_border, d_lut, (const f16*)d_lut16, sm);
             else hipLaunchKernelGGL(pre_border_kernel<1>, dim3(gx, nb), dim3(256), 0, s, pb, o, H, W, out_border, d_lut, (const f16*)d_lut16, sm);
         }
