@@ -691,6 +691,75 @@ int rtm3d_kitti_match(void* stream, int mode, int n_frames, int n_groups, int ca
                       const double* d_min_overlap, double* d_match_score, int max_thr, const int32_t* d_nthr,
                       const double* d_thr, int32_t* d_tp, int32_t* d_fp, int32_t* d_fn, double* d_sim);
 
+/* ------------------------------------------------------------------ drawing (csrc/draw.hip)
+ * Detection records painted into the camera frames and into a bird's-eye panel, on the device: the counterpart of the
+ * reference's utils/visual_utils.py (key points, 2D boxes, the eight vertices as a wireframe with a shaded front face, the
+ * solved box through the camera, a bird's-eye view).  Added in ABI 9 without changing any existing declaration; nothing calls
+ * this unless the caller does (no plan, engine file or record changes).  The rule below is the project's own and replaces
+ * OpenCV's rasteriser, whose pixel values were never pinned here: everything is an integer, so the result is defined BIT FOR
+ * BIT.  OUT OF SCOPE: text labels (there is no font in the library), anti-aliasing, clipping of boxes that cross the image
+ * plane, the reference's heat-map overlays.
+ *
+ * FRAMES: h_imgs[B] HOST array of DEVICE pointers to uint8 (h, w, 3) frames, contiguous, h_hw[2B] their (h, w), as for
+ * rtm3d_engine_detect_frames; painted IN PLACE.  The channel order is the caller's and colours are given in the same order.
+ * A side longer than 8192 (or < 1) is refused with an error that names the frame; the whole batch is checked first.
+ * d_rec: B * topk * 32 records in the pixels of each frame (the output of rtm3d_engine_detect_frames).
+ * PAINTER'S ORDER: the result is that of painting the slots of an image one after the other FROM THE LAST TO THE FIRST - slot
+ * 0, the best score, ends on top - and within a slot the layers in the order front-face shade, 2D box, wireframe, key-point
+ * disc.  Only slots with flag [31] >= min_flag are painted (1 = every detection, 2 = 3D-kept only).  Empty slots and images
+ * without a detection leave the frame untouched, byte for byte.
+ * COORDINATES: a coordinate becomes an integer by truncation toward zero (the reference's astype(int)).  A primitive - one
+ * segment, one disc, one face - with a coordinate that is not finite or whose integer lies outside [-8192, 8192] is not
+ * drawn; the other primitives of the slot are.
+ * COLOUR: color[class] with class = (int)[0]; ncls = the number of RGB triples in the table (1..RTM3D_ENGINE_MAX_CLASSES,
+ * anything else is refused).  The records are device memory and the call does not synchronise, so a RECORD whose class lies
+ * outside [0, ncls) cannot be turned into a return code: such a slot is not drawn (rtm3d_amd.draw.draw_records checks the
+ * classes on the host and raises).
+ * LAYERS (bit mask `layers`):
+ *   thick segment P-Q of thickness t: covers pixel p iff the squared distance from p to the closed segment is <= t^2 / 4,
+ *     in integers: d = Q - P, v = p - P, k = v.d;  k <= 0: 4 |v|^2 <= t^2;  k >= d.d: 4 |p - Q|^2 <= t^2;  otherwise
+ *     (2 (v x d))^2 <= t^2 (d.d).  P == Q is the disc of radius t / 2 (first case).  With t = 1 the cover is gap-free: along
+ *     the major direction some pixel centre lies within 0.5 of the line in every column (row).  (Ranges: csrc/draw.hip.)
+ *   RTM3D_DRAW_KEYPOINT  disc |p - c|^2 <= radius^2 at [2:4] (radius 0..64);
+ *   RTM3D_DRAW_BOX2D     the four sides of [20:24] = (x1, y1, x2, y2) as thick segments of `thickness` (1..15);
+ *   RTM3D_DRAW_WIREFRAME the twelve edges 01 13 32 20 04 45 57 76 64 51 37 62 of the box over vertices 0..7 - the edges the
+ *     reference's outline path 0 1 3 2 0 4 5 7 6 4 5 1 3 7 6 2 traces, each once - as thick segments of `thickness`;
+ *   RTM3D_DRAW_FACE      the front face, vertices 0 1 3 2: a pixel is covered iff it lies in the closed triangle (0, 1, 3) or
+ *     in the closed triangle (0, 3, 2) - integer edge functions (b - a) x (p - a), all three >= 0 or all three <= 0; a
+ *     triangle of zero area covers nothing - and becomes (px * (256 - a) + colour * a + 128) >> 8 per channel, a =
+ *     face_alpha (0..256), ONCE per slot.  Slots are painted in sequence, so overlapping faces compound by this formula.
+ *   The vertices: source 0 = the regressed vertices [4:20]; source 1 = the solved box [24:31] widened to fp64 and projected
+ *     through d_K_camera (B x 9 fp64; may be NULL unless source == 1) with the corner order and operation sequence of
+ *     rtm3d_project_boxes (csrc/box_project.h) on x = [., ., l, h, w, X, Y, Z], fed with PLAIN sin(ry) and cos(ry) (no snap
+ *     of small values), compiled without contraction.  Source 1 draws wireframe and face for slots with flag 2 only, and a
+ *     slot with any corner at camera depth Z below 0.1 (or NaN) gets neither: there is no clipping against the image plane.
+ *   RTM3D_DRAW_BEV       the bird's-eye panel: d_bev (may be NULL unless this bit is set), B caller-owned uint8 (bev_h, bev_w,
+ *     3) images (sides 1..8192), painted in place by the same rules, slots with flag 2 (and >= min_flag) only.  The footprint
+ *     is that of "box overlaps": half extents hl = l / 2 along local x, hw = w / 2 along local z, c = cos(ry), s = sin(ry);
+ *     a local point (lx, lz) lies at world x = (c * lx + s * lz) + X, z = (c * lz - s * lx) + Z.  The corners (hl, hw),
+ *     (-hl, hw), (-hl, -hw), (hl, -hw), the centre (X, Z) and the midpoint (hl, 0) of the +x edge are mapped by
+ *     u = trunc(bev_w / 2. + x / m), v = trunc(bev_h - z / m), m = bev_m_per_px (fp64, positive): the outline is the four
+ *     segments between consecutive corners, the heading mark the segment centre - midpoint, all of thickness 1.
+ * rtm3d_draw_default_params: the four frame layers, source 0, min_flag 1, thickness 1, radius 5, face_alpha 77, a palette of
+ * the project's own choosing for all RTM3D_ENGINE_MAX_CLASSES classes, no panel.
+ * rtm3d_records_draw: one launch per 64 frames, one workgroup per 64 x 16 tile of a frame or panel that gathers the
+ * primitives touching it (a tile none touches neither reads nor writes memory).  Stream-ordered: no host synchronisation, no
+ * memset / memcpy node, no allocation.  Bad arguments return non-zero with the reason in rtm3d_last_error().              */
+#define RTM3D_DRAW_FACE 1
+#define RTM3D_DRAW_BOX2D 2
+#define RTM3D_DRAW_WIREFRAME 4
+#define RTM3D_DRAW_KEYPOINT 8
+#define RTM3D_DRAW_BEV 16
+typedef struct rtm3d_draw_params {
+    int layers, source, min_flag, thickness, radius, face_alpha, ncls;
+    uint8_t color[RTM3D_ENGINE_MAX_CLASSES][3];
+    int bev_h, bev_w;
+    double bev_m_per_px;
+} rtm3d_draw_params;
+int rtm3d_draw_default_params(rtm3d_draw_params* p);
+int rtm3d_records_draw(void* stream, int B, int topk, const float* d_rec, uint8_t* const* h_imgs, const int* h_hw,
+                       const double* d_K_camera, const rtm3d_draw_params* params, uint8_t* d_bev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,12 @@ class FrameParams(ctypes.Structure):
     _fields_ = [('mean', c_float * 3), ('std', c_float * 3), ('resize_to', c_int)]
 
 
+class DrawParamsC(ctypes.Structure):
+    """Mirror of struct rtm3d_draw_params (rtm3d_amd/draw.py)."""
+    _fields_ = [('layers', c_int), ('source', c_int), ('min_flag', c_int), ('thickness', c_int), ('radius', c_int), ('face_alpha', c_int),
+                ('ncls', c_int), ('color', (ctypes.c_uint8 * 3) * 16), ('bev_h', c_int), ('bev_w', c_int), ('bev_m_per_px', c_double)]
+
+
 class PreprocessPlan(ctypes.Structure):
     """Mirror of struct rtm3d_preprocess_plan (one per sub-batch of 64 images)."""
     _fields_ = [('first', c_int), ('count', c_int), ('col_bytes', c_int), ('stage_bytes', c_int), ('band_rows', c_int), ('bands', c_int),
@@ -173,6 +179,9 @@ SIGNATURES = {
     # KITTI evaluation (rtm3d_amd/kitti_eval.py)
     'rtm3d_rect_overlaps': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'rtm3d_kitti_match': (c_int, [c_void_p] + [c_int] * 5 + [c_void_p] * 11 + [c_int] + [c_void_p] * 6),
+    # drawing of records into frames and a bird's-eye panel (rtm3d_amd/draw.py)
+    'rtm3d_draw_default_params': (c_int, [ctypes.POINTER(DrawParamsC)]),
+    'rtm3d_records_draw': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(DrawParamsC), c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,104 @@
+"""Detection records painted into the camera frames and a bird's-eye panel on the device (csrc/draw.hip).
+
+The drawing rule - integer coordinates by truncation, exact integer coverage tests, painter's order with slot 0 on top - is
+stated in include/rtm3d_hip.h, "drawing"; the result is defined bit for bit.  ``draw_records`` paints a list of uint8
+(h, w, 3) CUDA frames IN PLACE from the (B, topk, 32) records of ``Engine.detect_frames`` (one launch on the current stream);
+``to_ppm`` writes a frame or panel as binary PPM, so looking at a result needs neither OpenCV nor an image library.
+Device tensors only: there is no CPU path.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+FACE, BOX2D, WIREFRAME, KEYPOINT, BEV = 1, 2, 4, 8, 16
+FRAME_LAYERS = FACE | BOX2D | WIREFRAME | KEYPOINT
+MAX_CLASSES = 16
+# the default palette (RGB; the channel order of the frames is the caller's): eight well separated hues, repeated
+PALETTE = ((255, 64, 64), (64, 224, 64), (64, 128, 255), (255, 208, 0), (255, 64, 224), (0, 224, 224), (255, 144, 32), (176, 112, 255))
+
+
+class DrawParams(object):
+    """The fields of struct rtm3d_draw_params.  layers: mask of FACE | BOX2D | WIREFRAME | KEYPOINT | BEV; source: 0 = the
+    regressed vertices, 1 = the solved box projected through K_camera; min_flag: 1 = every detection, 2 = 3D-kept only;
+    thickness 1..15; radius of the key-point disc; face_alpha 0..256; colors: up to 16 triples indexed by class; bev_hw,
+    bev_m_per_px: size and scale of the bird's-eye panels."""
+
+    def __init__(self, layers=FRAME_LAYERS, source=0, min_flag=1, thickness=1, radius=5, face_alpha=77, colors=None, bev_hw=(400, 400),
+                 bev_m_per_px=0.2):
+        self.layers, self.source, self.min_flag, self.thickness = int(layers), int(source), int(min_flag), int(thickness)
+        self.radius, self.face_alpha = int(radius), int(face_alpha)
+        self.colors = [tuple(int(v) for v in c) for c in (colors if colors is not None else [PALETTE[i % 8] for i in range(MAX_CLASSES)])]
+        self.bev_hw, self.bev_m_per_px = (int(bev_hw[0]), int(bev_hw[1])), float(bev_m_per_px)
+
+    def to_c(self):
+        if not 1 <= len(self.colors) <= MAX_CLASSES or any(len(c) != 3 or min(c) < 0 or max(c) > 255 for c in self.colors):
+            raise ValueError('DrawParams: colors must be 1..%d triples of 0..255, got %r' % (MAX_CLASSES, self.colors))
+        p = _lib.DrawParamsC()
+        p.layers, p.source, p.min_flag, p.thickness, p.radius = self.layers, self.source, self.min_flag, self.thickness, self.radius
+        p.face_alpha, p.ncls = self.face_alpha, len(self.colors)
+        for i, c in enumerate(self.colors):
+            for k in range(3):
+                p.color[i][k] = c[k]
+        if self.layers & BEV:
+            p.bev_h, p.bev_w, p.bev_m_per_px = self.bev_hw[0], self.bev_hw[1], self.bev_m_per_px
+        return p
+
+
+def draw_records(images, rec, K_camera=None, params=None, bev=None, check_classes=True):
+    """Paint the records into ``images`` IN PLACE (rtm3d_records_draw on the current stream).  images: list of B contiguous
+    uint8 (h, w, 3) CUDA tensors; rec: contiguous fp32 (B, topk, 32) CUDA records in the pixels of each frame; K_camera:
+    (B, 9) camera intrinsics, needed by params.source == 1; params: DrawParams (None: the defaults).  With the BEV layer set
+    the panels are painted as well and returned: ``bev`` = a contiguous uint8 (B, bev_h, bev_w, 3) CUDA tensor painted in
+    place, or None for new black panels.  check_classes: compare the classes of the live slots with the colour table on the
+    host (one synchronisation) and raise ValueError for one outside it; False: no synchronisation, such a slot is not drawn.
+    Returns the panels, or None without the BEV layer."""
+    params = DrawParams() if params is None else params
+    if not isinstance(rec, torch.Tensor) or not rec.is_cuda:
+        raise RuntimeError('rtm3d_amd.draw.draw_records needs CUDA (ROCm) tensors; there is no CPU path')
+    if rec.dtype != torch.float32 or rec.dim() != 3 or rec.shape[-1] != 32 or not rec.is_contiguous():
+        raise ValueError('draw_records: rec must be a contiguous fp32 tensor (B, topk, 32), got %s %s' % (rec.dtype, tuple(rec.shape)))
+    B, topk, dev = int(rec.shape[0]), int(rec.shape[1]), rec.device
+    if len(images) != B:
+        raise ValueError('draw_records: %d frames for the records of %d images' % (len(images), B))
+    for i, img in enumerate(images):
+        if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 \
+                or not img.is_contiguous() or img.device != dev:
+            raise ValueError('draw_records: frame %d must be a contiguous uint8 (h, w, 3) tensor on %s (it is painted in place)' % (i, dev))
+    p = params.to_c()
+    if check_classes:
+        live = rec[..., 31] >= float(params.min_flag)
+        bad = live & ~((rec[..., 0] >= 0) & (rec[..., 0] < p.ncls))
+        if bool(bad.any()):
+            raise ValueError('draw_records: a record has a class outside the colour table of %d classes' % p.ncls)
+    K = None
+    if K_camera is not None:
+        K = torch.as_tensor(K_camera, dtype=torch.float64, device=dev).reshape(B, 9).contiguous()
+    with torch.cuda.device(dev):
+        panels = None
+        if params.layers & BEV:
+            shape = (B, params.bev_hw[0], params.bev_hw[1], 3)
+            if bev is None:
+                panels = torch.zeros(shape, dtype=torch.uint8, device=dev)
+            elif not isinstance(bev, torch.Tensor) or bev.dtype != torch.uint8 or tuple(bev.shape) != shape or not bev.is_contiguous() \
+                    or bev.device != dev:
+                raise ValueError('draw_records: bev must be a contiguous uint8 tensor %s on %s' % (shape, dev))
+            else:
+                panels = bev
+        ptrs = (ctypes.c_void_p * B)(*[i.data_ptr() for i in images])
+        hw = (ctypes.c_int * (2 * B))(*[int(v) for i in images for v in i.shape[:2]])
+        _lib.check(_lib.load().rtm3d_records_draw(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), B, topk, rec.data_ptr(), ptrs, hw,
+                                                  K.data_ptr() if K is not None else None, ctypes.byref(p),
+                                                  panels.data_ptr() if panels is not None else None), 'records_draw')
+    return panels
+
+
+def to_ppm(path, image):
+    """Write a uint8 (h, w, 3) tensor or array as binary PPM (P6), channels as they are."""
+    a = image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else image
+    if a.dtype.name != 'uint8' or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError('to_ppm: a uint8 (h, w, 3) image, got %s %s' % (a.dtype, a.shape))
+    with open(path, 'wb') as f:
+        f.write(b'P6\n%d %d\n255\n' % (a.shape[1], a.shape[0]))
+        f.write(a.tobytes())

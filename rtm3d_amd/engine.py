@@ -422,11 +422,14 @@ class Engine(object):
             self.frames_workspace = torch.empty(int(self.lib.rtm3d_engine_frames_workspace_bytes(self.ctx)), dtype=torch.uint8,
                                                 device=self.device)
 
-    def detect_frames(self, images, K_camera, kitti=False, out=None, nms3d=None):
+    def detect_frames(self, images, K_camera, kitti=False, out=None, draw=None, nms3d=None):
         """One detect step fed by camera frames (rtm3d_engine_detect_frames): images = list of B uint8 (h, w, 3) CUDA tensors of
         any sizes that fit the canvas after Resize, K_camera = the cameras' own (B, 9) intrinsics.  Returns the (B, topk, 32)
         records with their 2D fields in the pixels of each frame; kitti=True: (records, (B, topk, 16) float64 KITTI rows).
-        nms3d: as for detect; applied to the records and, with kitti=True, to the rows (a suppressed slot's row is zeroed)."""
+        nms3d: as for detect; applied to the records and, with kitti=True, to the rows (a suppressed slot's row is zeroed).
+        draw: None (nothing is painted, nothing is launched) or a draw.DrawParams: the records, after nms3d, are painted into
+        ``images`` in place (draw.draw_records, one more launch behind the step; the frames must be contiguous); with the BEV
+        layer set the new (B, bev_h, bev_w, 3) panels are appended to what is returned."""
         import torch
         from . import box_overlap
         nms3d = box_overlap.nms3d_options(nms3d)
@@ -452,7 +455,14 @@ class Engine(object):
                                                            ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames')
             if nms3d is not None:
                 box_overlap.nms3d_records(rec, kitti_rows=rows, **nms3d)
-        return (rec, rows) if kitti else rec
+            panels = None
+            if draw is not None:
+                from . import draw as _draw
+                panels = _draw.draw_records(list(images), rec, K, draw, check_classes=False)
+        res = (rec, rows) if kitti else (rec,)
+        if panels is not None:
+            res = res + (panels,)
+        return res if len(res) > 1 else res[0]
 
     def close(self):
         if self.ctx:
