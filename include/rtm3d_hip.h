@@ -760,6 +760,95 @@ int rtm3d_draw_default_params(rtm3d_draw_params* p);
 int rtm3d_records_draw(void* stream, int B, int topk, const float* d_rec, uint8_t* const* h_imgs, const int* h_hw,
                        const double* d_K_camera, const rtm3d_draw_params* params, uint8_t* d_bev);
 
+/* ------------------------------------------------------------------ tracking (csrc/track.hip)
+ * The kept 3D boxes of the records followed from frame to frame on the device: an identity and a velocity per object, by the
+ * tracking-by-detection baseline of the KITTI 3D trackers (a constant-velocity Kalman filter per object, a greedy match of this
+ * frame's boxes to the live tracks on 3D overlap or centre distance).  Added in ABI 9 without changing any existing
+ * declaration; nothing calls these unless the caller does (no plan, engine file or record changes).  The records are READ ONLY.
+ * The rule below is complete: tests/track_ref.py is written from it.  Everything is fp64, in the operation order written here,
+ * compiled without contraction; "a * b + c" below means the rounded product, then the rounded sum, and sums associate left
+ * to right unless bracketed.
+ *
+ * STREAMS: B independent streams, stream b = batch index b of the records.  d_state is caller-owned device memory,
+ * rtm3d_tracks_state_bytes(B, T) bytes: per stream RTM3D_TRACK_HEADER_DOUBLES + T * RTM3D_TRACK_SLOT_DOUBLES doubles, T track
+ * slots, 1 <= T <= 256.  An all-zero table is an empty stream: hipMemsetAsync of a stream's part is its reset.  LAYOUT, all fp64:
+ *   header [0] ids issued so far (the next id is this + 1)  [1] frames seen  [2] dropped births so far  [3:8] zero
+ *   slot   [0] id (0 = free slot, and then all 24 values are zero)  [1] class  [2] age in frames, 1 at birth  [3] hits = matched
+ *          frames in a row, the birth included  [4] misses in a row  [5] score of the last matched detection  [6] record slot it
+ *          matched in THIS frame, -1 if none  [7:10] h w l  [10:13] X Y Z  [13] ry  [14:17] vx vy vz (per unit of dt)
+ *          [17] Ppp [18] Ppv [19] Pvv: the 2 x 2 (position, velocity) covariance all three axes share - what a filter started
+ *          from isotropic diagonal noise stays equal to  [20] variance of ry  [21] variance shared by h, w, l  [22:24] zero
+ * DETECTIONS of a frame: the record slots k < topk with flag [31] == 2 and (double)[1] >= min_score, in slot order; box
+ * z = (double)[24:31] = h w l X Y Z ry (centre convention of "box overlaps"), class (double)[0].  The caller's boxes are taken
+ * as they are: a box that is not finite makes a track that is not finite, matches nothing and dies of its misses.
+ * wrap(a) = a - TWO_PI * floor((a + PI) / TWO_PI), PI = 3.141592653589793, TWO_PI = 6.283185307179586: [-pi, pi).
+ *
+ * One call = one frame of every stream, in these steps.  frame = header[1] + 1.
+ * 1 PREDICT every live slot (id != 0), dt > 0 the time since the previous call:
+ *     X = X + dt * vx (Y, Z alike);  age = age + 1;
+ *     ego motion, if d_ego != NULL: e = d_ego + 12 * b is the row-major 3 x 4 [R | t] that takes a point of the previous
+ *     frame's camera coordinates to the current frame's.  With the stepped position (x, y, z) and the velocity:
+ *       X = ((e[0] * x + e[1] * y) + e[2] * z) + e[3]   (rows 1, 2 alike with e[4..7], e[8..11]);
+ *       vx = (e[0] * vx + e[1] * vy) + e[2] * vz        (rows alike; all three from the old velocity);
+ *       the heading vector (c, 0, -s), c = cos(ry), s = sin(ry), turns with R:  ry = atan2(-(e[8] * c - e[10] * s), e[0] * c - e[2] * s).
+ *     The covariances are isotropic, so a rotation leaves them as they are.
+ *     ry = wrap(ry)
+ *     a = Ppp + dt * Ppv;  b = Ppv + dt * Pvv;  Ppp = (a + dt * b) + q_pos * dt;  Ppv = b;  Pvv = Pvv + q_vel * dt   (b, Pvv: old)
+ *     Pry = Pry + q_ry * dt;  Pdim = Pdim + q_dim * dt.   h, w, l, class, id are kept.
+ * 2 AFFINITY of every (live slot t, detection k), track first: metric 0 = BEV IoU, 1 = 3D IoU of the predicted box (h, w, l,
+ *     X, Y, Z, ry of step 1) as box a and the detection as box b, by the arithmetic of rtm3d_box_overlaps, criterion 0 - with
+ *     one shortcut: with (ex, ey, ez) = predicted centre - detection centre and
+ *     reach = 0.5 * sqrt(w_a * w_a + l_a * l_a) + 0.5 * sqrt(w_b * w_b + l_b * l_b), a pair with ex * ex + ez * ez > reach * reach
+ *     has affinity 0 (the footprints cannot meet; nothing is clipped).  metric 2 = -sqrt((ex * ex + ey * ey) + ez * ez), minus
+ *     the centre distance.  The pair is a CANDIDATE iff affinity > thresh (strict; never for NaN) and, with class_aware != 0,
+ *     slot class == detection class.
+ * 3 MATCH: the sequential global greedy one - take the remaining candidate of highest affinity, the lower track slot at a tie,
+ *     then the lower record slot; remove its track and its detection; repeat until no candidate remains.  (The kernel runs
+ *     rounds of mutual best, which gives this result: csrc/track.hip.)
+ * 4 UPDATE a matched slot with its detection z (zry = wrap(z ry)), everything on the right of one line from before that line:
+ *     S = Ppp + r_pos;  Kp = Ppp / S;  Kv = Ppv / S
+ *     per axis: y = zX - X;  X = X + Kp * y;  vx = vx + Kv * y
+ *     Ppp' = Ppp - Kp * Ppp;  Ppv' = Ppv - Kp * Ppv;  Pvv' = Pvv - Kv * Ppv   (all three from the predicted values)
+ *     heading: if |wrap(zry - ry)| > 1.5707963267948966: ry = wrap(ry + PI) - a box seen from the other end is the same box;
+ *     y = wrap(zry - ry);  K = Pry / (Pry + r_ry);  ry = wrap(ry + K * y);  Pry = Pry - K * Pry
+ *     K = Pdim / (Pdim + r_dim);  h = h + K * (zh - h) (w, l alike);  Pdim = Pdim - K * Pdim
+ *     hits = hits + 1;  misses = 0;  [5] = detection score;  [6] = k.
+ *   An UNMATCHED live slot keeps its predicted state: hits = 0, misses = misses + 1, [6] = -1; once misses > max_misses the slot
+ *   is freed (all zero) - so a track survives max_misses frames without a detection and loses its id on the next.
+ * 5 BIRTHS: the unmatched detections, in slot order, open tracks in the free slots, in slot order (slots freed in step 4 of
+ *   this call included); the n-th of them (n = 1 ..) gets id = header[0] + n.  Ids start at 1 and are never reused.  A new
+ *   slot: class, box and score of the detection, ry = wrap(z ry), velocity 0, Ppp = p0_pos, Ppv = 0, Pvv = p0_vel, Pry =
+ *   p0_ry, Pdim = p0_dim, age 1, hits 1, misses 0, [6] = k.  When the free slots run out the remaining births are dropped -
+ *   the lower scores, records being score-ordered - and counted: header[2] += dropped;  header[0] += births;  header[1] = frame.
+ * 6 IDS: d_ids [B][topk] int32, one per record slot: 0 = not tracked (no detection, or a dropped birth); otherwise the id of the
+ *   slot the detection was matched to or born into, +id if that track is CONFIRMED - hits >= min_hits, or frame <= min_hits -
+ *   and -id while it is tentative.
+ *
+ * rtm3d_track_default_params: metric 1, thresh 0.01, class_aware 0, max_misses 2, min_hits 3, min_score 0, initial variances
+ * position 10, velocity 1e4, ry 10, dimensions 10, process noise (per unit of dt) 0.01 on the velocity and 0 elsewhere,
+ * measurement noise 1 - the usual baseline's.
+ * rtm3d_tracks_update: two launches - the affinity matrix of all streams, one lane per (slot, record slot) pair, into d_ws
+ * (rtm3d_tracks_workspace_bytes(B, topk, T) bytes, fully rewritten by every call); then one workgroup per stream for steps 1
+ * and 3 - 6.  Stream-ordered: no host synchronisation, no memset / memcpy node, no allocation.  topk <= 256 and T <= 256, more is
+ * refused.  Refused before anything is launched, non-zero with the reason in rtm3d_last_error(): B < 1, T or topk outside
+ * 1..256, dt not positive and finite, a NULL d_rec / params / d_state / d_ids / d_ws, metric outside 0..2, negative max_misses
+ * or min_hits, NaN thresh or min_score, a variance or process noise that is negative or not finite, measurement noise that is
+ * not positive and finite.  The two size functions return 0 for sizes the update would refuse.                            */
+#define RTM3D_TRACK_HEADER_DOUBLES 8
+#define RTM3D_TRACK_SLOT_DOUBLES 24
+typedef struct rtm3d_track_params {
+    int metric, class_aware, max_misses, min_hits;
+    double thresh, min_score;
+    double p0_pos, p0_vel, p0_ry, p0_dim;
+    double q_pos, q_vel, q_ry, q_dim;
+    double r_pos, r_ry, r_dim;
+} rtm3d_track_params;
+int rtm3d_track_default_params(rtm3d_track_params* p);
+size_t rtm3d_tracks_state_bytes(int B, int T);
+size_t rtm3d_tracks_workspace_bytes(int B, int topk, int T);
+int rtm3d_tracks_update(void* stream, int B, int topk, int T, const float* d_rec, double dt, const double* d_ego /* or NULL */,
+                        const rtm3d_track_params* params, double* d_state, int32_t* d_ids, void* d_ws);
+
 #ifdef __cplusplus
 }
 #endif

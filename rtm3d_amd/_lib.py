@@ -83,6 +83,15 @@ class DrawParamsC(ctypes.Structure):
                 ('ncls', c_int), ('color', (ctypes.c_uint8 * 3) * 16), ('bev_h', c_int), ('bev_w', c_int), ('bev_m_per_px', c_double)]
 
 
+class TrackParamsC(ctypes.Structure):
+    """Mirror of struct rtm3d_track_params (rtm3d_amd/track.py)."""
+    _fields_ = [('metric', c_int), ('class_aware', c_int), ('max_misses', c_int), ('min_hits', c_int),
+                ('thresh', c_double), ('min_score', c_double),
+                ('p0_pos', c_double), ('p0_vel', c_double), ('p0_ry', c_double), ('p0_dim', c_double),
+                ('q_pos', c_double), ('q_vel', c_double), ('q_ry', c_double), ('q_dim', c_double),
+                ('r_pos', c_double), ('r_ry', c_double), ('r_dim', c_double)]
+
+
 class PreprocessPlan(ctypes.Structure):
     """Mirror of struct rtm3d_preprocess_plan (one per sub-batch of 64 images)."""
     _fields_ = [('first', c_int), ('count', c_int), ('col_bytes', c_int), ('stage_bytes', c_int), ('band_rows', c_int), ('bands', c_int),
@@ -182,6 +191,12 @@ SIGNATURES = {
     # drawing of records into frames and a bird's-eye panel (rtm3d_amd/draw.py)
     'rtm3d_draw_default_params': (c_int, [ctypes.POINTER(DrawParamsC)]),
     'rtm3d_records_draw': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(DrawParamsC), c_void_p]),
+    # tracking of the kept boxes across frames (rtm3d_amd/track.py)
+    'rtm3d_track_default_params': (c_int, [ctypes.POINTER(TrackParamsC)]),
+    'rtm3d_tracks_state_bytes': (c_size_t, [c_int, c_int]),
+    'rtm3d_tracks_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'rtm3d_tracks_update': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_void_p, ctypes.POINTER(TrackParamsC), c_void_p,
+                                    c_void_p, c_void_p]),
 }
 
 _lib = None

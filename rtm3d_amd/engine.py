@@ -391,10 +391,14 @@ class Engine(object):
                                               ctypes.c_void_p(x.data_ptr()), ptrs), 'forward')
         return tuple(outs)
 
-    def detect(self, x, K_per_image, out=None, nms3d=None):
+    # (nms3d stays the LAST parameter of detect and detect_frames - tests/test_box_overlap_cpu.py pins it - so tracker, which runs
+    # after nms3d, stands before it in the signatures; pass both by keyword)
+    def detect(self, x, K_per_image, out=None, tracker=None, nms3d=None):
         """One detect step (rtm3d_engine_detect): (B, topk, 32) fp32 records, the layout of Detect3DPipeline.results.
         K_per_image: (B, 9) intrinsics (fp64 on the device).  nms3d: None | IoU threshold | dict of
-        box_overlap.nms3d_records' keywords: 3D NMS of the returned records (one more launch behind the step)."""
+        box_overlap.nms3d_records' keywords: 3D NMS of the returned records (one more launch behind the step).
+        tracker: None (nothing is launched, the records alone are returned) or a track.Tracker of B streams: the records, after
+        nms3d, are one more frame of its streams (tracker.update with tracker.dt / tracker.ego); returns (records, ids)."""
         from . import box_overlap
         nms3d = box_overlap.nms3d_options(nms3d)
         import torch
@@ -409,6 +413,8 @@ class Engine(object):
                        'engine_detect')
             if nms3d is not None:
                 box_overlap.nms3d_records(rec, **nms3d)
+            if tracker is not None:
+                return rec, tracker.update(rec, dt=tracker.dt, ego=tracker.ego)
         return rec
 
     def set_frame_params(self, mean, std, resize_to=None):
@@ -422,14 +428,16 @@ class Engine(object):
             self.frames_workspace = torch.empty(int(self.lib.rtm3d_engine_frames_workspace_bytes(self.ctx)), dtype=torch.uint8,
                                                 device=self.device)
 
-    def detect_frames(self, images, K_camera, kitti=False, out=None, draw=None, nms3d=None):
+    def detect_frames(self, images, K_camera, kitti=False, out=None, draw=None, tracker=None, nms3d=None):
         """One detect step fed by camera frames (rtm3d_engine_detect_frames): images = list of B uint8 (h, w, 3) CUDA tensors of
         any sizes that fit the canvas after Resize, K_camera = the cameras' own (B, 9) intrinsics.  Returns the (B, topk, 32)
         records with their 2D fields in the pixels of each frame; kitti=True: (records, (B, topk, 16) float64 KITTI rows).
         nms3d: as for detect; applied to the records and, with kitti=True, to the rows (a suppressed slot's row is zeroed).
         draw: None (nothing is painted, nothing is launched) or a draw.DrawParams: the records, after nms3d, are painted into
         ``images`` in place (draw.draw_records, one more launch behind the step; the frames must be contiguous); with the BEV
-        layer set the new (B, bev_h, bev_w, 3) panels are appended to what is returned."""
+        layer set the new (B, bev_h, bev_w, 3) panels are appended to what is returned.
+        tracker: as for detect; it runs after nms3d and before draw, and the (B, topk) int32 ids are the last element of what is
+        returned.  None launches nothing and returns what is returned without it."""
         import torch
         from . import box_overlap
         nms3d = box_overlap.nms3d_options(nms3d)
@@ -455,6 +463,7 @@ class Engine(object):
                                                            ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames')
             if nms3d is not None:
                 box_overlap.nms3d_records(rec, kitti_rows=rows, **nms3d)
+            ids = None if tracker is None else tracker.update(rec, dt=tracker.dt, ego=tracker.ego)
             panels = None
             if draw is not None:
                 from . import draw as _draw
@@ -462,6 +471,8 @@ class Engine(object):
         res = (rec, rows) if kitti else (rec,)
         if panels is not None:
             res = res + (panels,)
+        if ids is not None:
+            res = res + (ids,)
         return res if len(res) > 1 else res[0]
 
     def close(self):
