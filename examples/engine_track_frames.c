@@ -1,6 +1,6 @@
 /* engine_track_frames.c - consecutive camera frames in, a track id per kept 3D box out, from plain C (no Python, no torch).
  *
- *   engine_track_frames ENGINE IDS.i32 FRAMES.bin [FRAMES.bin ...]
+ *   engine_track_frames ENGINE IDS.i32 FRAMES.bin [FRAMES.bin ...] [optimal]
  *
  * ENGINE      an engine file written by rtm3d_amd.engine.save_engine (Model.save_engine)
  * FRAMES.bin  one per time step, in order, each in the format of engine_detect_frames.c: int32 B (the engine's batch); per
@@ -9,10 +9,12 @@
  * IDS.i32     output: per file B x topk raw int32, one per record slot: +id confirmed track, -id tentative, 0 not tracked
  *
  * Per file, on one stream and without a synchronisation in between: rtm3d_engine_detect_frames, then rtm3d_tracks_update with
- * the default parameters (rtm3d_track_default_params), 128 track slots per stream, dt = 1, no ego motion.
+ * the default parameters (rtm3d_track_default_params), 128 track slots per stream, dt = 1, no ego motion.  A trailing word
+ * "optimal" runs rtm3d_tracks_update_assign with RTM3D_TRACK_ASSIGN_OPTIMAL instead (the optimal assignment, not the greedy match).
  * Build: make -C rtm3d_amd/csrc example  (links librtm3d_hip.so and libamdhip64 only).                                 */
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <hip/hip_runtime_api.h>
 
@@ -65,10 +67,10 @@ done:
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s ENGINE IDS.i32 FRAMES.bin [FRAMES.bin ...]\n", argv[0]);
+        fprintf(stderr, "usage: %s ENGINE IDS.i32 FRAMES.bin [FRAMES.bin ...] [optimal]\n", argv[0]);
         return 2;
     }
-    int rc = 1, b, f, n_files = argc - 3, B, params_set = 0, tracked = 0;
+    int rc = 1, b, f, n_files = argc - 3, B, params_set = 0, tracked = 0, optimal = 0;
     rtm3d_ctx* ctx = NULL;
     rtm3d_engine_info info;
     rtm3d_frame_params fparams;
@@ -83,6 +85,7 @@ int main(int argc, char** argv) {
     size_t n_slots, i;
     FILE* out = NULL;
 
+    if (n_files > 1 && strcmp(argv[argc - 1], "optimal") == 0) { optimal = 1; --n_files; }
     if (rtm3d_engine_load(argv[1], 0, &ctx, &info) != 0) {
         fprintf(stderr, "engine_track_frames: %s\n", rtm3d_last_error());
         return 1;
@@ -114,7 +117,11 @@ int main(int argc, char** argv) {
         }
         HIP_OK(hipMemcpyAsync(d_K, h_K, (size_t)B * 9 * sizeof(double), hipMemcpyHostToDevice, stream));
         RT_OK(rtm3d_engine_detect_frames(ctx, stream, (const uint8_t* const*)d_imgs, h_hw, d_K, d_rec, NULL, d_ws));
-        RT_OK(rtm3d_tracks_update(stream, B, info.topk, TRACK_SLOTS, d_rec, 1.0, NULL, &tparams, d_state, d_ids, d_tws));
+        if (optimal)
+            RT_OK(rtm3d_tracks_update_assign(stream, B, info.topk, TRACK_SLOTS, d_rec, 1.0, NULL, &tparams, RTM3D_TRACK_ASSIGN_OPTIMAL, d_state,
+                                             d_ids, d_tws));
+        else
+            RT_OK(rtm3d_tracks_update(stream, B, info.topk, TRACK_SLOTS, d_rec, 1.0, NULL, &tparams, d_state, d_ids, d_tws));
         HIP_OK(hipMemcpyAsync(h_ids, d_ids, n_slots * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));                        /* the ids of this frame are wanted on the host */
         if (fwrite(h_ids, sizeof(int32_t), n_slots, out) != n_slots) { fprintf(stderr, "engine_track_frames: cannot write %s\n", argv[2]); goto done; }

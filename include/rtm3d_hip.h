@@ -805,6 +805,20 @@ int rtm3d_records_draw(void* stream, int B, int topk, const float* d_rec, uint8_
  * 3 MATCH: the sequential global greedy one - take the remaining candidate of highest affinity, the lower track slot at a tie,
  *     then the lower record slot; remove its track and its detection; repeat until no candidate remains.  (The kernel runs
  *     rounds of mutual best, which gives this result: csrc/track.hip.)
+ * 3b MATCH, optimal (rtm3d_tracks_update_assign with RTM3D_TRACK_ASSIGN_OPTIMAL; steps 1, 2, 4, 5, 6 as they are, and the
+ *     candidates exactly those of step 2).  The GAIN of a candidate pair is g(t, k) = affinity - thresh, strictly positive by
+ *     the definition of a candidate.  A matching is a set of candidate pairs in which no track slot and no record slot appears
+ *     twice; the match is a matching of the largest sum of gains, the sum associated as the implementation likes.  Leaving a
+ *     track or a detection unmatched costs nothing, and a pair that is no candidate is never matched, so nothing is filtered
+ *     afterwards.  This is NOT "solve the assignment on the full affinity matrix, then drop the pairs under the threshold":
+ *     that rule spends tracks and detections on pairs it then throws away, while here a pair at or below the threshold is
+ *     simply absent and its track and its detection stay free for others.  (Tracks A, B, detections x, y, centre distances
+ *     A-x 1.0, B-x 1.2, A-y 2.1, B-y 3.0, thresh -2: the full matrix is solved by A-y and B-x, 3.3 against 4.0; A-y is dropped
+ *     and B-x stays, gain 0.8.  The rule here has the candidates A-x and B-x only and matches A-x, gain 1.0.)
+ *     Where several matchings attain the maximum, within the fp64 rounding of the sums, any one of them may be returned - the
+ *     same one on every call with the same inputs: no result depends on the order in which lanes or atomics retire.  (The
+ *     kernel runs shortest augmenting paths over the live slots that have a candidate, in slot order, taking the lowest record
+ *     slot at equal slack: csrc/track.hip.)  thresh must be finite under this rule (the gains are differences from it).
  * 4 UPDATE a matched slot with its detection z (zry = wrap(z ry)), everything on the right of one line from before that line:
  *     S = Ppp + r_pos;  Kp = Ppp / S;  Kv = Ppv / S
  *     per axis: y = zX - X;  X = X + Kp * y;  vx = vx + Kv * y
@@ -833,7 +847,12 @@ int rtm3d_records_draw(void* stream, int B, int topk, const float* d_rec, uint8_
  * refused.  Refused before anything is launched, non-zero with the reason in rtm3d_last_error(): B < 1, T or topk outside
  * 1..256, dt not positive and finite, a NULL d_rec / params / d_state / d_ids / d_ws, metric outside 0..2, negative max_misses
  * or min_hits, NaN thresh or min_score, a variance or process noise that is negative or not finite, measurement noise that is
- * not positive and finite.  The two size functions return 0 for sizes the update would refuse.                            */
+ * not positive and finite.  The two size functions return 0 for sizes the update would refuse.
+ * rtm3d_tracks_update_assign (additive, still ABI 9): the same call with the rule of step 3 chosen by `assign`.
+ * RTM3D_TRACK_ASSIGN_GREEDY is rtm3d_tracks_update itself - the same two kernels, the same results bit for bit;
+ * RTM3D_TRACK_ASSIGN_OPTIMAL runs step 3b in place of step 3, in the same two launches, the same workspace and without a host
+ * synchronisation.  Every refusal of rtm3d_tracks_update applies, in its words; refused too, before anything is launched: an
+ * assign outside 0..1 (the value is in rtm3d_last_error()) and, under the optimal rule, a thresh that is not finite.        */
 #define RTM3D_TRACK_HEADER_DOUBLES 8
 #define RTM3D_TRACK_SLOT_DOUBLES 24
 typedef struct rtm3d_track_params {
@@ -848,6 +867,10 @@ size_t rtm3d_tracks_state_bytes(int B, int T);
 size_t rtm3d_tracks_workspace_bytes(int B, int topk, int T);
 int rtm3d_tracks_update(void* stream, int B, int topk, int T, const float* d_rec, double dt, const double* d_ego /* or NULL */,
                         const rtm3d_track_params* params, double* d_state, int32_t* d_ids, void* d_ws);
+#define RTM3D_TRACK_ASSIGN_GREEDY 0
+#define RTM3D_TRACK_ASSIGN_OPTIMAL 1
+int rtm3d_tracks_update_assign(void* stream, int B, int topk, int T, const float* d_rec, double dt, const double* d_ego /* or NULL */,
+                               const rtm3d_track_params* params, int assign, double* d_state, int32_t* d_ids, void* d_ws);
 
 #ifdef __cplusplus
 }

@@ -197,6 +197,8 @@ SIGNATURES = {
     'rtm3d_tracks_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'rtm3d_tracks_update': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_void_p, ctypes.POINTER(TrackParamsC), c_void_p,
                                     c_void_p, c_void_p]),
+    'rtm3d_tracks_update_assign': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_void_p, ctypes.POINTER(TrackParamsC), c_int,
+                                           c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -12,6 +12,16 @@
 // can block it, and taking it removes exactly its row and column.  Every round with a candidate left matches at least the first
 // pair of the whole order, so the rounds end.  Candidates are kept as two LDS bit matrices (rows, columns); the fp64 affinities
 // stay in the workspace and are read for set bits only.
+// The OPTIMAL match (step 3b; track_step_kernel<1>, reached only through rtm3d_tracks_update_assign) replaces the rounds by
+// shortest augmenting paths (Hungarian method in the Jonker-Volgenant form) over the same candidates, cost = -(affinity - thresh).
+// "Stay unmatched" is a zero-cost column private to every row, kept as one scalar per path (the smallest slack of the scanned
+// rows' private columns) instead of in memory: such a column is reachable from its own row only, is free whenever that row is
+// scanned, and a free column's dual is 0.  ONE wave runs the paths, so a path step has no block barrier: lane L owns the record
+// slots 4L .. 4L + 3 with their duals and slacks in registers; row duals, predecessors and the two owner arrays are in LDS.  Per
+// step every lane relaxes its unscanned candidate columns against the newly scanned row, a wave minimum and a ballot pick the
+// column of least slack - the lowest record slot at equal slack, the private column at a tie with it - and nothing depends on
+// the order in which lanes retire.  The rows are the live slots with a candidate, in slot order: at most T augmentations of at
+// most topk + 1 path steps each, both loops counted.
 #include "common.h"
 #include "../../include/rtm3d_hip.h"
 #include "box_geom.h"
@@ -48,6 +58,15 @@ __device__ __forceinline__ TrkPose trk_predict_pose(const double* __restrict__ s
     }
     p.ry = trk_wrap(p.ry);
     return p;
+}
+
+// a wave's LDS instructions execute in order: between lanes of ONE wave this is only a compiler / LDS ordering fence
+#define TRK_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
+
+__device__ __forceinline__ double trk_wave_min(double x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x = fmin(x, __shfl_xor(x, m, 64));
+    return x;
 }
 
 __device__ __forceinline__ bool trk_is_detection(const float* __restrict__ r, double min_score) {
@@ -93,12 +112,19 @@ __global__ __launch_bounds__(BO_LANES) void track_affinity_kernel(long long tota
     aff[t] = out;
 }
 
+// ASSIGN: RTM3D_TRACK_ASSIGN_GREEDY (step 3) or RTM3D_TRACK_ASSIGN_OPTIMAL (step 3b); everything else is one code
+template <int ASSIGN>
 __global__ __launch_bounds__(BO_LANES) void track_step_kernel(int topk, int T, const float* __restrict__ rec, double dt,
                                                              const double* __restrict__ ego, rtm3d_track_params P,
                                                              double* __restrict__ state, int32_t* __restrict__ ids,
                                                              const double* __restrict__ aff) {
+    constexpr bool OPT = ASSIGN == RTM3D_TRACK_ASSIGN_OPTIMAL;
     __shared__ uint32_t rowmask[TRK_MAX][TRK_MAX / 32];       // [track slot]: candidate record slots
-    __shared__ uint32_t colmask[TRK_MAX][TRK_MAX / 32];       // [record slot]: candidate track slots
+    __shared__ uint32_t colmask[OPT ? 1 : TRK_MAX][TRK_MAX / 32];   // [record slot]: candidate track slots (greedy only)
+    __shared__ double row_dual[OPT ? TRK_MAX : 1];            // optimal only: [track slot] dual of the row
+    __shared__ int trk_det[OPT ? TRK_MAX : 1];                //   track slot -> record slot it holds, -1 none
+    __shared__ int pred[OPT ? TRK_MAX : 1];                   //   record slot -> the row its slack came from, this path
+    __shared__ unsigned long long rowsel[OPT ? BO_LANES / 64 : 1];   //   the rows: live slots with a candidate
     __shared__ uint32_t det_free[TRK_MAX / 32], trk_free[TRK_MAX / 32];
     __shared__ int cbest[TRK_MAX];
     __shared__ int det_owner[TRK_MAX];                        // record slot -> track slot (match or birth), -1 none
@@ -117,7 +143,7 @@ __global__ __launch_bounds__(BO_LANES) void track_step_kernel(int topk, int T, c
     const double issued = hdr[0], frame = hdr[1] + 1.0, dropped = hdr[2];
 
 #pragma unroll
-    for (int w = 0; w < TRK_MAX / 32; ++w) { rowmask[tid][w] = 0u; colmask[tid][w] = 0u; }
+    for (int w = 0; w < TRK_MAX / 32; ++w) { rowmask[tid][w] = 0u; if constexpr (!OPT) colmask[tid][w] = 0u; }
     if (tid < TRK_MAX / 32) { det_free[tid] = 0xffffffffu; trk_free[tid] = 0xffffffffu; }
     det_owner[tid] = -1; birth_det[tid] = -1; sid[tid] = 0;
     __syncthreads();
@@ -147,49 +173,151 @@ __global__ __launch_bounds__(BO_LANES) void track_step_kernel(int topk, int T, c
         if (A[q] > TRK_NEG_INF) {
             const int t = q / topk, k = q - t * topk;
             atomicOr(&rowmask[t][k >> 5], 1u << (k & 31));
-            atomicOr(&colmask[k][t >> 5], 1u << (t & 31));
+            if constexpr (!OPT) atomicOr(&colmask[k][t >> 5], 1u << (t & 31));
         }
     }
     __syncthreads();
 
-    // rounds of mutual best
     int match = -1;
-    for (;;) {
-        int rb = -1;
-        if (live && match < 0) {
-            double rv = TRK_NEG_INF;
-            for (int wd = 0; wd < TRK_MAX / 32; ++wd) {
-                uint32_t m = rowmask[tid][wd] & det_free[wd];
-                while (m) {
-                    const int k = wd * 32 + __ffs(m) - 1;
-                    m &= m - 1u;
-                    const double v = A[(size_t)tid * topk + k];
-                    if (v > rv) { rv = v; rb = k; }
+    if constexpr (!OPT) {
+        // rounds of mutual best
+        for (;;) {
+            int rb = -1;
+            if (live && match < 0) {
+                double rv = TRK_NEG_INF;
+                for (int wd = 0; wd < TRK_MAX / 32; ++wd) {
+                    uint32_t m = rowmask[tid][wd] & det_free[wd];
+                    while (m) {
+                        const int k = wd * 32 + __ffs(m) - 1;
+                        m &= m - 1u;
+                        const double v = A[(size_t)tid * topk + k];
+                        if (v > rv) { rv = v; rb = k; }
+                    }
                 }
             }
-        }
-        int cb = -1;
-        if (isdet && det_owner[tid] < 0) {
-            double cv = TRK_NEG_INF;
-            for (int wd = 0; wd < TRK_MAX / 32; ++wd) {
-                uint32_t m = colmask[tid][wd] & trk_free[wd];
-                while (m) {
-                    const int t = wd * 32 + __ffs(m) - 1;
-                    m &= m - 1u;
-                    const double v = A[(size_t)t * topk + tid];
-                    if (v > cv) { cv = v; cb = t; }
+            int cb = -1;
+            if (isdet && det_owner[tid] < 0) {
+                double cv = TRK_NEG_INF;
+                for (int wd = 0; wd < TRK_MAX / 32; ++wd) {
+                    uint32_t m = colmask[tid][wd] & trk_free[wd];
+                    while (m) {
+                        const int t = wd * 32 + __ffs(m) - 1;
+                        m &= m - 1u;
+                        const double v = A[(size_t)t * topk + tid];
+                        if (v > cv) { cv = v; cb = t; }
+                    }
                 }
             }
+            cbest[tid] = cb;
+            __syncthreads();
+            if (rb >= 0 && cbest[rb] == tid) {
+                match = rb;
+                det_owner[rb] = tid;
+                atomicAnd(&det_free[rb >> 5], ~(1u << (rb & 31)));
+                atomicAnd(&trk_free[tid >> 5], ~(1u << (tid & 31)));
+            }
+            if (!__syncthreads_or(rb >= 0 ? 1 : 0)) break;
         }
-        cbest[tid] = cb;
+    } else {
+        // shortest augmenting paths, one wave; lane wl owns the record slots 4 * wl + c, c = 0 .. 3
+        bool has = false;
+#pragma unroll
+        for (int wd = 0; wd < TRK_MAX / 32; ++wd) has = has || rowmask[tid][wd] != 0u;
+        const unsigned long long hb = __ballot(has);
+        if (wl == 0) rowsel[wave] = hb;
+        row_dual[tid] = 0.0; trk_det[tid] = -1;
         __syncthreads();
-        if (rb >= 0 && cbest[rb] == tid) {
-            match = rb;
-            det_owner[rb] = tid;
-            atomicAnd(&det_free[rb >> 5], ~(1u << (rb & 31)));
-            atomicAnd(&trk_free[tid >> 5], ~(1u << (tid & 31)));
+        if (wave == 0) {
+            unsigned long long rs[BO_LANES / 64];
+#pragma unroll
+            for (int wv = 0; wv < BO_LANES / 64; ++wv) rs[wv] = rowsel[wv];
+            auto pop_row = [&]() -> int {                         // the next row in slot order, -1 when there is none
+                int r = -1;
+#pragma unroll
+                for (int wv = 0; wv < BO_LANES / 64; ++wv)
+                    if (r < 0 && rs[wv]) { r = 64 * wv + __ffsll(rs[wv]) - 1; rs[wv] &= rs[wv] - 1ull; }
+                return r;
+            };
+            // the candidate bits of this lane's four columns in row i and their affinities (read for set bits only)
+            auto load_row = [&](int i, double (&a)[4], uint32_t& nib) {
+                nib = (rowmask[i][wl >> 3] >> ((wl & 7) * 4)) & 0xfu;
+                const double* Ai = A + (size_t)i * topk + 4 * wl;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) a[c] = (nib >> c) & 1u ? Ai[c] : 0.0;
+            };
+            double v[4] = {0.0, 0.0, 0.0, 0.0};                   // column duals
+            double an[4] = {0.0, 0.0, 0.0, 0.0};
+            uint32_t nibn = 0u;
+            int next = pop_row();
+            if (next >= 0) load_row(next, an, nibn);
+            for (int n = 0; n < T && next >= 0; ++n) {            // one augmentation per row: at most T
+                const int cur = next;
+                double a[4] = {an[0], an[1], an[2], an[3]};
+                uint32_t nib = nibn;
+                next = pop_row();
+                if (next >= 0) load_row(next, an, nibn);          // the next root's row is fetched behind this path
+                double sp[4] = {__builtin_inf(), __builtin_inf(), __builtin_inf(), __builtin_inf()};   // slacks: shortest path costs
+                uint32_t sc = 0u;                                 // this lane's scanned columns
+                double minval = 0.0, dbest = __builtin_inf();     // dbest / drow: least slack of a scanned row's private column
+                int drow = -1, sink = -2;                         // sink: -2 none yet, -1 the private column of drow, else a record slot
+                int i = cur;
+                for (int step = 0; step <= topk; ++step) {        // every step scans another matched row or ends: at most topk + 1
+                    const double ui = row_dual[i];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        if (((nib & ~sc) >> c) & 1u) {
+                            const double r = ((minval - (a[c] - P.thresh)) - ui) - v[c];
+                            if (r < sp[c]) { sp[c] = r; pred[4 * wl + c] = i; }
+                        }
+                    }
+                    const double dv = minval - ui;
+                    if (dv < dbest) { dbest = dv; drow = i; }
+                    double lv = __builtin_inf();
+                    int lc = 0;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (!((sc >> c) & 1u) && sp[c] < lv) { lv = sp[c]; lc = c; }
+                    const double m = trk_wave_min(lv);
+                    const unsigned long long win = __ballot(lv == m);
+                    if (!(m < dbest) || win == 0ull) { sink = -1; minval = dbest; break; }
+                    const int wlane = __ffsll(win) - 1;           // lowest lane, and in it the lowest c: the lowest record slot
+                    const int j = __builtin_amdgcn_readfirstlane(4 * wlane + __shfl(lc, wlane, 64));
+                    minval = m;
+                    if (wl == wlane) sc |= 1u << lc;
+                    const int o = __builtin_amdgcn_readfirstlane(det_owner[j]);
+                    if (o < 0) { sink = j; break; }
+                    i = o;
+                    load_row(i, a, nib);
+                }
+                if (sink != -2 && drow >= 0) {
+                    // duals: scanned columns and the rows that hold them move by what the path still had to go; the root by all of it
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        if ((sc >> c) & 1u) {
+                            const double d = minval - sp[c];
+                            v[c] = v[c] - d;
+                            const int o = det_owner[4 * wl + c];
+                            if (o >= 0) row_dual[o] = row_dual[o] + d;
+                        }
+                    }
+                    if (wl == 0) row_dual[cur] = row_dual[cur] + minval;
+                    TRK_WSYNC();
+                    // augment back along the predecessors (every lane walks the same path and writes the same values)
+                    int j = sink, r = -1;
+                    if (sink == -1) { r = drow; j = trk_det[r]; trk_det[r] = -1; }
+                    for (int g = 0; g <= topk && r != cur && j >= 0; ++g) {
+                        r = pred[j];
+                        det_owner[j] = r;
+                        const int t = trk_det[r];
+                        trk_det[r] = j;
+                        j = t;
+                    }
+                    TRK_WSYNC();
+                }
+            }
         }
-        if (!__syncthreads_or(rb >= 0 ? 1 : 0)) break;
+        __syncthreads();
+        match = trk_det[tid];
     }
 
     // update of matched tracks, misses and deaths of the others
@@ -305,8 +433,8 @@ extern "C" size_t rtm3d_tracks_workspace_bytes(int B, int topk, int T) {
 
 static bool trk_nonneg(double v) { return v >= 0.0 && v < __builtin_inf(); }
 
-extern "C" int rtm3d_tracks_update(void* stream, int B, int topk, int T, const float* d_rec, double dt, const double* d_ego,
-                                   const rtm3d_track_params* params, double* d_state, int32_t* d_ids, void* d_ws) {
+static int trk_update(void* stream, int B, int topk, int T, const float* d_rec, double dt, const double* d_ego,
+                      const rtm3d_track_params* params, int assign, double* d_state, int32_t* d_ids, void* d_ws) {
     if (B <= 0) { rt_set_error("tracks_update: bad batch size B %d", B); return 1; }
     if (T < 1 || T > TRK_MAX) { rt_set_error("tracks_update: T %d track slots per stream (1..%d)", T, TRK_MAX); return 1; }
     if (topk < 1 || topk > TRK_MAX) { rt_set_error("tracks_update: topk %d record slots per image (1..%d)", topk, TRK_MAX); return 1; }
@@ -324,6 +452,9 @@ extern "C" int rtm3d_tracks_update(void* stream, int B, int topk, int T, const f
     if (!(P.r_pos > 0.0) || !(P.r_ry > 0.0) || !(P.r_dim > 0.0) || !trk_nonneg(P.r_pos) || !trk_nonneg(P.r_ry) || !trk_nonneg(P.r_dim)) {
         rt_set_error("tracks_update: measurement noise must be positive and finite"); return 1;
     }
+    if (assign == RTM3D_TRACK_ASSIGN_OPTIMAL && !(P.thresh > -__builtin_inf() && P.thresh < __builtin_inf())) {
+        rt_set_error("tracks_update_assign: the optimal assignment needs a finite thresh (gain = affinity - thresh), got %g", P.thresh); return 1;
+    }
     const long long total = (long long)B * T * topk;
     const long long blocks = (total + BO_LANES - 1) / BO_LANES;
     if (blocks > 0x7fffffffLL) { rt_set_error("tracks_update: %lld pairs are more than one launch holds", total); return 1; }
@@ -331,9 +462,26 @@ extern "C" int rtm3d_tracks_update(void* stream, int B, int topk, int T, const f
                        (const double*)d_state, (double*)d_ws);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { rt_set_error("tracks_update affinity launch: %s", hipGetErrorString(e)); return 1; }
-    hipLaunchKernelGGL(track_step_kernel, dim3(B), dim3(BO_LANES), 0, (hipStream_t)stream, topk, T, d_rec, dt, d_ego, P, d_state, d_ids,
-                       (const double*)d_ws);
+    if (assign == RTM3D_TRACK_ASSIGN_OPTIMAL)
+        hipLaunchKernelGGL(track_step_kernel<RTM3D_TRACK_ASSIGN_OPTIMAL>, dim3(B), dim3(BO_LANES), 0, (hipStream_t)stream, topk, T, d_rec, dt, d_ego,
+                           P, d_state, d_ids, (const double*)d_ws);
+    else
+        hipLaunchKernelGGL(track_step_kernel<RTM3D_TRACK_ASSIGN_GREEDY>, dim3(B), dim3(BO_LANES), 0, (hipStream_t)stream, topk, T, d_rec, dt, d_ego,
+                           P, d_state, d_ids, (const double*)d_ws);
     e = hipGetLastError();
     if (e != hipSuccess) { rt_set_error("tracks_update step launch: %s", hipGetErrorString(e)); return 1; }
     return 0;
+}
+
+extern "C" int rtm3d_tracks_update(void* stream, int B, int topk, int T, const float* d_rec, double dt, const double* d_ego,
+                                   const rtm3d_track_params* params, double* d_state, int32_t* d_ids, void* d_ws) {
+    return trk_update(stream, B, topk, T, d_rec, dt, d_ego, params, RTM3D_TRACK_ASSIGN_GREEDY, d_state, d_ids, d_ws);
+}
+
+extern "C" int rtm3d_tracks_update_assign(void* stream, int B, int topk, int T, const float* d_rec, double dt, const double* d_ego,
+                                          const rtm3d_track_params* params, int assign, double* d_state, int32_t* d_ids, void* d_ws) {
+    if (assign != RTM3D_TRACK_ASSIGN_GREEDY && assign != RTM3D_TRACK_ASSIGN_OPTIMAL) {
+        rt_set_error("tracks_update_assign: unknown assign %d (0 greedy, 1 optimal)", assign); return 1;
+    }
+    return trk_update(stream, B, topk, T, d_rec, dt, d_ego, params, assign, d_state, d_ids, d_ws);
 }

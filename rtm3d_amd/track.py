@@ -14,6 +14,7 @@ from . import _lib
 METRICS = {'bev': 0, '3d': 1, 'dist': 2}
 MAX_TRACKS = 256
 MAX_TOPK = 256
+ASSIGNMENTS = {'greedy': 0, 'optimal': 1}     # RTM3D_TRACK_ASSIGN_GREEDY, RTM3D_TRACK_ASSIGN_OPTIMAL
 HEADER, SLOT = 8, 24          # RTM3D_TRACK_HEADER_DOUBLES, RTM3D_TRACK_SLOT_DOUBLES
 
 _DEFAULTS = dict(metric='3d', class_aware=False, max_misses=2, min_hits=3, thresh=0.01, min_score=0.0, p0_pos=10.0, p0_vel=1e4,
@@ -51,9 +52,14 @@ class Tracker(object):
     ``update`` when they are given this tracker.
     A Tracker belongs to ONE torch stream: the table and the affinity workspace are its own and every ``update`` / ``reset`` is
     ordered only by the stream it is issued on.  Calling it from a second stream needs the caller's event between the two (as for
-    any tensor shared between streams); use one Tracker per stream otherwise."""
+    any tensor shared between streams); use one Tracker per stream otherwise.
+    assignment: 'greedy' (step 3 of the rule: the best remaining pair first) or 'optimal' (step 3b: the matching of candidate pairs
+    with the largest sum of affinity - thresh; keeps the identities of neighbours that greedy swaps); kept as ``tracker.assignment``."""
 
-    def __init__(self, B, capacity=128, params=None, device='cuda'):
+    def __init__(self, B, capacity=128, params=None, device='cuda', assignment='greedy'):
+        if assignment not in ASSIGNMENTS:
+            raise ValueError("Tracker: assignment must be one of %s, got %r" % (sorted(ASSIGNMENTS), assignment))
+        self.assignment = assignment
         lib = _lib.load()
         d = torch.device(device)
         if d.type != 'cuda':
@@ -70,7 +76,7 @@ class Tracker(object):
         self._ws = None
 
     def update(self, rec, dt=1.0, ego=None):
-        """One frame of every stream (rtm3d_tracks_update) on the current stream.  rec: the contiguous (B, topk, 32) fp32 CUDA
+        """One frame of every stream (rtm3d_tracks_update_assign) on the current stream.  rec: the contiguous (B, topk, 32) fp32 CUDA
         records of this frame (read only).  dt: time since the previous call.  ego: None or (B, 12) / (B, 3, 4) float64 CUDA
         [R | t] per stream, previous camera coordinates -> current.  Returns the (B, topk) int32 ids: +id confirmed track, -id
         tentative track, 0 not tracked."""
@@ -96,10 +102,10 @@ class Tracker(object):
                 self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
             ids = torch.empty(self.B, topk, dtype=torch.int32, device=self.device)
             p = self.params.to_c()
-            _lib.check(lib.rtm3d_tracks_update(ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), self.B, topk,
-                                               self.capacity, ctypes.c_void_p(rec.data_ptr()), float(dt), e_ptr, ctypes.byref(p),
-                                               ctypes.c_void_p(self.state.data_ptr()), ctypes.c_void_p(ids.data_ptr()),
-                                               ctypes.c_void_p(self._ws.data_ptr())), 'tracks_update')
+            _lib.check(lib.rtm3d_tracks_update_assign(ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), self.B, topk,
+                                                      self.capacity, ctypes.c_void_p(rec.data_ptr()), float(dt), e_ptr, ctypes.byref(p),
+                                                      ASSIGNMENTS[self.assignment], ctypes.c_void_p(self.state.data_ptr()),
+                                                      ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(self._ws.data_ptr())), 'tracks_update')
         return ids
 
     def tracks(self):
