@@ -872,6 +872,102 @@ int rtm3d_tracks_update(void* stream, int B, int topk, int T, const float* d_rec
 int rtm3d_tracks_update_assign(void* stream, int B, int topk, int T, const float* d_rec, double dt, const double* d_ego /* or NULL */,
                                const rtm3d_track_params* params, int assign, double* d_state, int32_t* d_ids, void* d_ws);
 
+/* ------------------------------------------------------------------ tracking evaluation (csrc/mot_eval.hip)
+ * The quality of a tracker on labelled sequences: HOTA and CLEAR-MOT over per-frame similarity matrices of whatever metric (3D
+ * IoU, BEV IoU, IoU of the image rectangles: rtm3d_box_overlaps / rtm3d_rect_overlaps).  Added in ABI 9 without changing any
+ * existing declaration; nothing calls these unless the caller does.  The host side - label files, the KITTI preprocessing, the
+ * closing formulas - is rtm3d_amd/mot_eval.py.  The protocol is restated from the published behaviour of the HOTA / CLEAR
+ * evaluation (TrackEval) and of the KITTI tracking benchmark's preprocessing; those programs were not available to compare
+ * against, so parity with them is UNPINNED: the contract is the rules written here, and tests/mot_eval_ref.py is written from
+ * them.  Everything is fp64, compiled without contraction; "a * b + c" is the rounded product, then the rounded sum; sums run in
+ * the order named, left to right; no result depends on the order in which lanes or atomics retire.  EPS = 2.220446049250313e-16.
+ *
+ * INPUTS.  S sequences, their frames concatenated, F in all: d_seq_start [S + 1] int32, sequence s = frames seq_start[s] ..
+ * seq_start[s + 1] - 1 (seq_start[0] = 0, seq_start[S] = F, not decreasing).  Per frame d_ng[f] <= cap_g ground truths and
+ * d_nt[f] <= cap_t tracker boxes, 1 <= cap_g, cap_t <= 256 (the limit of rtm3d_tracks_update).  d_gid [F][cap_g], d_tid [F][cap_t]
+ * int32: DENSE ids, 0 .. n_gid - 1 / 0 .. n_tid - 1 within each sequence (n_gid, n_tid: the largest count of any sequence; the
+ * arrays below are padded to them), an id at most once per frame (the host checks; the device does not).  d_sim [F][cap_g][cap_t]
+ * fp64 in [0, 1].  Entries beyond ng / nt are never read.  d_gslot [F][n_gid] / d_tslot [F][n_tid] int32: the slot at which the
+ * id stands in the frame, -1 if it is absent (the inverse of d_gid / d_tid, built by the host).
+ *
+ * ASSIGN, the shared primitive (rtm3d_mot_assign).  For one frame, a score matrix w [cap_g][cap_t] >= 0.  The CANDIDATES are the
+ * pairs (g < ng, t < nt) with w > 0 (never NaN).  The match is a matching over candidates - no row and no column twice - with
+ * the largest sum of scores; unmatched rows and columns cost nothing; a non-candidate is never matched.  This is step 3b of
+ * "tracking" with gain = w.  Where several matchings attain the maximum within the fp64 rounding of the sums, any one may be
+ * returned, the same one on every call with the same inputs.  d_match [F][cap_g] int32: the tracker slot, or -1 (also beyond
+ * ng).  One wavefront per frame runs shortest augmenting paths; a frame with ng, nt <= 64 with one column per lane, a larger one
+ * with four - the frame's own size decides, not the caps.
+ *
+ * HOTA (rtm3d_mot_hota), per sequence:
+ * 1 ALIGNMENT, for every frame in frame order: rowsum[g] = sum over t < nt of sim[g][t] in t order, colsum[t] = sum over g < ng
+ *   in g order; den = (rowsum[g] + colsum[t]) - sim[g][t]; simn = sim[g][t] / den where den > 0, else 0;
+ *   potential[gid[g]][tid[t]] += simn - per pair ONE running sum in frame order; gcount[gid] += 1, tcount[tid] += 1 for every id
+ *   present in the frame.
+ * 2 A[i][j] = potential[i][j] / ((gcount[i] + tcount[j]) - potential[i][j]) - the counts added as integers, then converted - or 0
+ *   where that denominator is not positive.
+ * 3 per frame: w[g][t] = A[gid[g]][tid[t]] * sim[g][t]; ASSIGN.
+ * 4 thresholds a = 0 .. 18 (RTM3D_MOT_ALPHAS of them): alpha_a = 0.05 + a * 0.05; a matched pair COUNTS at a iff
+ *   sim >= alpha_a - EPS.
+ * 5 per a: TP[a] = counted pairs; FN[a] = sum over frames of ng - counted; FP[a] = sum of nt - counted; loc[a] = the sum of sim
+ *   over the counted pairs, ONE running sum in frame order, then ground-truth slot order; mc[a][gid][tid] = the number of frames
+ *   in which the pair counted.
+ * Device outputs: d_potential [S][n_gid][n_tid] fp64, d_gcount [S][n_gid], d_tcount [S][n_tid] int32, d_match [F][cap_g], d_loc
+ * [S][19] fp64 are WRITTEN; d_tp / d_fn / d_fp [S][19] int32 and d_mc [S][19][n_gid][n_tid] int32 are ADDED TO (vector atomics on
+ * integers; the caller zeroes them).  Four launches - the sums of every frame; one lane per (gid, tid) pair of a sequence that
+ * walks its frames in order (steps 1, 2); one wavefront per frame (3 - 5); one wavefront per sequence for loc - and no host
+ * synchronisation, no allocation, no memset / memcpy node.  The closing formulas are the host's (rtm3d_amd/mot_eval.py), per a
+ * over all sequences, sums over sequences in sequence order: DetA = TP / max(1, TP + FN + FP), DetRe = TP / max(1, TP + FN),
+ * DetPr = TP / max(1, TP + FP); per pair of a sequence assa = mc / max(1, (gcount + tcount) - mc), AssA = sum(mc * assa) /
+ * max(1, TP), AssRe with mc / max(1, gcount), AssPr with mc / max(1, tcount) in the place of assa; LocA = loc / max(1, TP), 1.0
+ * where TP = 0; HOTA = sqrt(DetA * AssA); every one also as the mean over the 19 thresholds.
+ *
+ * CLEAR-MOT (rtm3d_mot_clear), per sequence, frames in order with carried state: last[gid] = the tracker id of the ground truth's
+ * most recent match, or none; prev[gid] = the tracker id it was matched to in the most recent PROCESSED frame, or none.  thr is
+ * the similarity threshold (0.5 in the host's default).  Per frame:
+ *   ng == 0: FP += nt, nothing else changes.  nt == 0: FN += ng, nothing else changes.  Neither frame is PROCESSED: the carried
+ *   state, prev included, stays as it is.
+ *   otherwise w[g][t] = 1000 * (prev[gid[g]] == tid[t]) + sim[g][t] (1000 + sim, or sim), set to 0 where sim < thr - EPS; ASSIGN.
+ *   A matched pair is an identity switch (IDSW += 1) iff last[gid] exists and differs from the matched tid.
+ *   idcount[gid] += 1 for every ground truth present, matched[gid] += 1 for the matched ones.  A ground truth whose prev was none
+ *   before this frame and is set after it adds 1 to frag[gid].  last is updated for the matched ground truths; prev is cleared
+ *   for every id of the sequence, then set for the matched ones.  TP += matched pairs, FN += ng - matched, FP += nt - matched,
+ *   simsum += sim of every matched pair: ONE running sum in frame order, then ground-truth slot order.
+ * Device outputs: d_match [F][cap_g] and d_simsum [S] fp64 are WRITTEN; d_counts [S][4] int32 = TP, FN, FP, IDSW and d_idcount /
+ * d_matched / d_frag [S][n_gid] int32 are ADDED TO (plain adds of the sequence's one wavefront; the caller zeroes them).  One
+ * launch, one wavefront per sequence: a frame's scores depend on the previous frame's match, so the frames of a sequence are a
+ * chain and S wavefronts are all the parallelism there is.  Host closing formulas: MOTA = (TP - FP - IDSW) / max(1, TP + FN);
+ * MOTP = simsum / max(1, TP); Recall = TP / max(1, TP + FN); Precision = TP / max(1, TP + FP); with ratio = matched / idcount
+ * over the ids with idcount > 0: MT = ratio > 0.8, PT = ratio >= 0.2 and not MT, ML = the rest; Frag = sum of (frag - 1) over the
+ * ids with frag > 0.
+ *
+ * KITTI PREPROCESSING (host rule, rtm3d_amd/mot_eval.py, optional), per evaluated class C (Car: distractor Van; Pedestrian:
+ * distractor Person_sitting; any other class: no distractor), per frame, type comparison ignoring case.  The tracker boxes of type
+ * C are ASSIGNed against ALL ground truths of the frame that are not DontCare, rows = ground truths in file order, columns = the
+ * tracker boxes in file order, w = sim where sim >= 0.5 - EPS, else 0.  A tracker box is REMOVED if it is matched to a ground
+ * truth of the distractor type, or to one of type C with occlusion > 2 or truncation > 0 (the label file's values compared as
+ * they are).  An UNMATCHED tracker box is removed if (intersection / its own area) of its image rectangle with any DontCare
+ * rectangle of the frame (rtm3d_rect_overlaps, criterion 1) is > 0.5, strictly.  A tracker box matched to any other ground truth
+ * stays.  The ground truths KEPT are those of type C with occlusion <= 2 and truncation <= 0.  Then ids are made dense per
+ * sequence in order of first appearance (frame order, then file order) and the similarity matrix is cut to the kept rows and
+ * columns, both in file order.  Without preprocessing: ground truths = all of type C, tracker boxes = all of type C.
+ *
+ * rtm3d_mot_workspace_bytes: what d_ws of rtm3d_mot_hota / rtm3d_mot_clear must hold (either; fully rewritten by every call); 0
+ * for sizes that would be refused.  Refused before anything is launched, non-zero with the reason in rtm3d_last_error(): S or F
+ * < 1, cap_g or cap_t outside 1..256, n_gid or n_tid < 1, S * 19 * n_gid * n_tid beyond 2^31 - 1, a NULL pointer, a thr that is
+ * not finite (NaN included); by rtm3d_mot_hota also S > 65535.                                                            */
+#define RTM3D_MOT_ALPHAS 19
+size_t rtm3d_mot_workspace_bytes(int S, int F, int cap_g, int cap_t, int n_gid, int n_tid);
+int rtm3d_mot_assign(void* stream, int F, int cap_g, int cap_t, const int32_t* d_ng, const int32_t* d_nt, const double* d_w,
+                     int32_t* d_match);
+int rtm3d_mot_hota(void* stream, int S, int F, int cap_g, int cap_t, int n_gid, int n_tid, const int32_t* d_seq_start,
+                   const int32_t* d_ng, const int32_t* d_nt, const int32_t* d_gid, const int32_t* d_tid, const int32_t* d_gslot,
+                   const int32_t* d_tslot, const double* d_sim, double* d_potential, int32_t* d_gcount, int32_t* d_tcount,
+                   int32_t* d_match, int32_t* d_tp, int32_t* d_fn, int32_t* d_fp, double* d_loc, int32_t* d_mc, void* d_ws);
+int rtm3d_mot_clear(void* stream, int S, int F, int cap_g, int cap_t, int n_gid, int n_tid, const int32_t* d_seq_start,
+                    const int32_t* d_ng, const int32_t* d_nt, const int32_t* d_gid, const int32_t* d_tid, const double* d_sim,
+                    double thr, int32_t* d_match, int32_t* d_counts, double* d_simsum, int32_t* d_idcount, int32_t* d_matched,
+                    int32_t* d_frag, void* d_ws);
+
 #ifdef __cplusplus
 }
 #endif

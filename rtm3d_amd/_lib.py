@@ -199,6 +199,11 @@ SIGNATURES = {
                                     c_void_p, c_void_p]),
     'rtm3d_tracks_update_assign': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_void_p, ctypes.POINTER(TrackParamsC), c_int,
                                            c_void_p, c_void_p, c_void_p]),
+    # tracking evaluation: HOTA / CLEAR-MOT (rtm3d_amd/mot_eval.py)
+    'rtm3d_mot_workspace_bytes': (c_size_t, [c_int] * 6),
+    'rtm3d_mot_assign': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rtm3d_mot_hota': (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 18),
+    'rtm3d_mot_clear': (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 6 + [c_double] + [c_void_p] * 7),
 }
 
 _lib = None
