@@ -698,7 +698,7 @@ int rtm3d_kitti_match(void* stream, int mode, int n_frames, int n_groups, int ca
  * this unless the caller does (no plan, engine file or record changes).  The rule below is the project's own and replaces
  * OpenCV's rasteriser, whose pixel values were never pinned here: everything is an integer, so the result is defined BIT FOR
  * BIT.  OUT OF SCOPE: text labels (there is no font in the library), anti-aliasing, clipping of boxes that cross the image
- * plane, the reference's heat-map overlays.
+ * plane, the reference's heat-map overlays.  (Text labels and track colours: rtm3d_records_draw_tracks, "drawing tracks" below.)
  *
  * FRAMES: h_imgs[B] HOST array of DEVICE pointers to uint8 (h, w, 3) frames, contiguous, h_hw[2B] their (h, w), as for
  * rtm3d_engine_detect_frames; painted IN PLACE.  The channel order is the caller's and colours are given in the same order.
@@ -871,6 +871,93 @@ int rtm3d_tracks_update(void* stream, int B, int topk, int T, const float* d_rec
 #define RTM3D_TRACK_ASSIGN_OPTIMAL 1
 int rtm3d_tracks_update_assign(void* stream, int B, int topk, int T, const float* d_rec, double dt, const double* d_ego /* or NULL */,
                                const rtm3d_track_params* params, int assign, double* d_state, int32_t* d_ids, void* d_ws);
+
+/* ------------------------------------------------------------------ drawing tracks (csrc/draw_tracks.hip)
+ * rtm3d_records_draw with what a tracker adds: a stable colour per track id, a text label per slot, and a bird's-eye panel painted
+ * from the track table - coasting tracks, the filtered box, the velocity.  Additive (still ABI 9): rtm3d_records_draw and its
+ * parameters are as they were, and nothing calls this unless the caller does.  Everything of "drawing" holds - frames, records,
+ * coordinates (COORD below = its rule: truncation toward zero; a value that is not finite or whose integer lies outside [-8192,
+ * 8192] is BAD), the thick segment, the layers, the panel mapping - and the rule below is complete with it: tests/draw_tracks_ref.py
+ * is written from the two sections.  All results are integers, defined bit for bit.
+ *
+ * d_ids [B][topk] int32: the ids of "tracking", step 6, for the same records (+id confirmed, -id tentative, 0 not tracked).
+ * COLOUR of a painted slot k of image b, in the frames and in the record-driven panel: id = d_ids[b][k];  id == 0: base.color[class]
+ * as in "drawing";  otherwise c = palette[(|id| - 1) % npal] (npal 1..32 RGB triples), and for a tentative track (id < 0) every
+ * channel (c + 1) >> 1.  Which slots are painted is decided as in "drawing" (flag >= min_flag, class inside [0, ncls) - also for a
+ * slot that takes an id colour).  With every id 0 and neither new layer set the call paints what rtm3d_records_draw paints, byte
+ * for byte.
+ * PAINTER'S ORDER in a frame: first the geometric layers of all slots, last slot first, as in "drawing"; then, with
+ * RTM3D_DRAW_LABEL, the labels of all slots, last slot first, per slot the background, then its glyphs left to right.  No label is
+ * covered by a box, and slot 0's label ends on top.
+ * FONT: 44 glyphs of 5 columns x 7 rows - space, 0-9, A-Z, # ? . % - : / in this order - in a cell of 6 x 8.  rtm3d_draw_font_rows
+ * (a HOST function, no device access) gives the seven rows of a character, top row first, 5 low bits per row, bit 4 the LEFT
+ * column; it returns non-zero (rows untouched) for a character outside the set - lower case included, which is folded only in
+ * names.  The bitmaps are the project's own and live in csrc/draw_font.h alone.  A glyph drawn at scale s = font_scale (1..4)
+ * with its top-left pixel at (gx, gy) covers pixel (x, y) iff x >= gx, y >= gy and, with c = (x - gx) / s, r = (y - gy) / s (integer
+ * division), c < 5, r < 7 and bit (4 - c) of row r is set: every glyph pixel is an s x s block.  A glyph is ONE primitive: it is
+ * not drawn if gx, gy, gx + 5 s - 1 or gy + 7 s - 1 lies outside [-8192, 8192].  The space paints nothing.
+ * LABEL TEXT of a slot (rtm3d_draw_label_text, a HOST function, composes the same text by the same code): the fields of the mask
+ * label_fields (0..15) in this order, joined by ONE space, an empty field left out with its space:
+ *   1  the id: '#' and the decimal digits of |id| % 10000000, '?' instead of '#' for a tentative track (id < 0); empty for id 0;
+ *   2  the class name: the bytes of names[class] before the first NUL, 7 at most, a - z drawn as A - Z, any byte outside the set
+ *      as '?'; empty for an empty name;
+ *   4  the score: two digits and '%': n = (int)((double)[1] * 100.0), 0 if that product is negative or NaN, 99 if it is >= 99;
+ *   8  the distance, for a slot with flag 2 only (empty otherwise): n = (int)((double)[29] * 10.0), 0 if the product is negative or
+ *      NaN, 9999 if it is >= 9999; the decimal digits of n / 10, '.', the digit n % 10, 'M'.
+ *   At most 27 characters.  The two products are single IEEE fp64 operations.  rtm3d_draw_label_text takes the slot as one of flag
+ *   2 (the text of another slot is that with bit 8 cleared); it writes the text and a NUL to out[32] and returns non-zero for a
+ *   NULL pointer, a label_fields outside 0..15 or a class outside [0, base.ncls).
+ * LABEL GEOMETRY (RTM3D_DRAW_LABEL; every painted slot with a text of n >= 1 characters): (x1, y1) = COORD of [20], [21]; if
+ * either is BAD the slot has no label.  s = font_scale.  The BACKGROUND is the filled rectangle of the columns x1 .. x1 +
+ * (6 n + 1) s - 1 and the 9 s rows top .. top + 9 s - 1, top = y1 - 9 s (above the box), or top = y1 (inside it) when y1 - 9 s < 0;
+ * in the slot's COLOUR, opaque.  Glyph i (0 ..) has its top-left pixel at (x1 + s + 6 s i, top + s): one s of padding on every
+ * side of the text, one s between the cells' glyphs.  GLYPH COLOUR: black (0, 0, 0) if 299 r + 587 g + 114 b >= 128000 for the
+ * background colour (r, g, b), else white (255, 255, 255).  The background and every glyph are separate primitives: the
+ * background is not drawn if one of its four extents lies outside [-8192, 8192], a glyph by the rule above, the others are.
+ * RTM3D_DRAW_TRACK_BEV: the panels d_bev as for RTM3D_DRAW_BEV (same sizes and mapping), painted from d_state instead of the
+ * records; setting both panel bits is refused.  d_state: the tables of "tracking" for B streams of T slots (1..256), stream b for
+ * panel b, READ ONLY; may be NULL without this bit.  A slot is drawn iff [0] is >= 1 (and < 2^31; id = (int)[0]): coasting slots -
+ * misses [4] > 0, no record of this frame - included.  A slot is TENTATIVE iff hits [3] < 1, that is, iff it was not matched in
+ * the frame the table was last updated with: min_hits is not in the table, so the confirmation of step 6 cannot be restated; a
+ * coasting track is tentative under step 6 as well (hits 0 < min_hits, once frame > min_hits), a matched one is drawn confirmed
+ * here even where step 6 still calls it tentative.  Colour: palette[(id - 1) % npal], halved as above while tentative.  Slots are
+ * painted FROM THE LAST TO THE FIRST, per slot in this order, all of thickness 1 and in that colour:
+ *   the footprint [7:14] = h w l X Y Z ry: corners, centre and +x midpoint from hl = l / 2, hw = w / 2, c = cos(ry), s = sin(ry)
+ *     by the mapping and the corner order of RTM3D_DRAW_BEV, all in fp64 (the table's own values): four outline segments;
+ *   the heading mark centre - midpoint;
+ *   with vel_horizon > 0 the velocity mark: the segment from the centre to the mapped point x = X + vx * vel_horizon, z = Z + vz *
+ *     vel_horizon ([14], [16]; the rounded product, then the rounded sum; u = trunc(bev_w / 2. + x / m), v = trunc(bev_h - z / m));
+ *   with label_fields & 1 the id text - '#' or '?' (tentative) and the digits, as field 1 of a label - as glyphs without a
+ *     background, glyph i with its top-left pixel at (cu + 6 s i, cv), (cu, cv) the mapped centre; none if the centre is BAD.
+ *   A primitive with a BAD coordinate (a state that is not finite) is not drawn, the others of the slot are.
+ * bev_fade (0..256): with a value < 256 and either panel layer set, every pixel channel of every panel becomes (px * bev_fade +
+ * 128) >> 8 before anything is painted - passing the same panels frame after frame leaves fading trails - and every panel tile
+ * is read and written; with 256 a tile nothing touches is neither read nor written, as in "drawing".
+ * rtm3d_draw_tracks_default_params: base = rtm3d_draw_default_params (no new layer), a palette of 32 colours of the project's own
+ * choosing, label_fields 3, font_scale 1, names "C0" .. "C15", bev_fade 256, vel_horizon 1.
+ * rtm3d_records_draw_tracks: one launch per 64 frames, the gather of rtm3d_records_draw (csrc/draw_tracks.hip); stream-ordered, no
+ * host synchronisation, no memset / memcpy node, no allocation.  REFUSED before anything is launched, non-zero with the field
+ * name in rtm3d_last_error(): everything rtm3d_records_draw refuses, in its words (layers: a mask of the seven bits; d_bev and the
+ * panel's size and scale are needed with either panel bit); both panel bits; npal outside 1..32; font_scale outside 1..4;
+ * label_fields outside 0..15; RTM3D_DRAW_LABEL with label_fields 0; bev_fade outside 0..256; vel_horizon negative or not finite;
+ * a NULL d_ids; with RTM3D_DRAW_TRACK_BEV a NULL d_state or T outside 1..256.                                            */
+#define RTM3D_DRAW_LABEL 32
+#define RTM3D_DRAW_TRACK_BEV 64
+typedef struct rtm3d_draw_tracks_params {
+    rtm3d_draw_params base;                         /* as for rtm3d_records_draw; layers may carry the two new bits */
+    int npal;
+    uint8_t palette[32][3];
+    int label_fields, font_scale;
+    char names[RTM3D_ENGINE_MAX_CLASSES][8];
+    int bev_fade;
+    double vel_horizon;
+} rtm3d_draw_tracks_params;
+int rtm3d_draw_tracks_default_params(rtm3d_draw_tracks_params* p);
+int rtm3d_records_draw_tracks(void* stream, int B, int topk, const float* d_rec, const int32_t* d_ids, int T,
+                              const double* d_state /* NULL unless RTM3D_DRAW_TRACK_BEV */, uint8_t* const* h_imgs, const int* h_hw,
+                              const double* d_K_camera, const rtm3d_draw_tracks_params* params, uint8_t* d_bev);
+int rtm3d_draw_font_rows(int ch, uint8_t rows[7]);
+int rtm3d_draw_label_text(const rtm3d_draw_tracks_params* p, int id, int cls, float score, float z, char out[32]);
 
 /* ------------------------------------------------------------------ tracking evaluation (csrc/mot_eval.hip)
  * The quality of a tracker on labelled sequences: HOTA and CLEAR-MOT over per-frame similarity matrices of whatever metric (3D

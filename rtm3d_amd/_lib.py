@@ -83,6 +83,12 @@ class DrawParamsC(ctypes.Structure):
                 ('ncls', c_int), ('color', (ctypes.c_uint8 * 3) * 16), ('bev_h', c_int), ('bev_w', c_int), ('bev_m_per_px', c_double)]
 
 
+class DrawTracksParamsC(ctypes.Structure):
+    """Mirror of struct rtm3d_draw_tracks_params (rtm3d_amd/draw.py)."""
+    _fields_ = [('base', DrawParamsC), ('npal', c_int), ('palette', (ctypes.c_uint8 * 3) * 32), ('label_fields', c_int), ('font_scale', c_int),
+                ('names', (ctypes.c_char * 8) * 16), ('bev_fade', c_int), ('vel_horizon', c_double)]
+
+
 class TrackParamsC(ctypes.Structure):
     """Mirror of struct rtm3d_track_params (rtm3d_amd/track.py)."""
     _fields_ = [('metric', c_int), ('class_aware', c_int), ('max_misses', c_int), ('min_hits', c_int),
@@ -191,6 +197,12 @@ SIGNATURES = {
     # drawing of records into frames and a bird's-eye panel (rtm3d_amd/draw.py)
     'rtm3d_draw_default_params': (c_int, [ctypes.POINTER(DrawParamsC)]),
     'rtm3d_records_draw': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(DrawParamsC), c_void_p]),
+    # the same with track ids: id colours, text labels, a panel painted from the track table (rtm3d_amd/draw.py)
+    'rtm3d_draw_tracks_default_params': (c_int, [ctypes.POINTER(DrawTracksParamsC)]),
+    'rtm3d_records_draw_tracks': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          ctypes.POINTER(DrawTracksParamsC), c_void_p]),
+    'rtm3d_draw_font_rows': (c_int, [c_int, ctypes.POINTER(ctypes.c_uint8 * 7)]),
+    'rtm3d_draw_label_text': (c_int, [ctypes.POINTER(DrawTracksParamsC), c_int, c_int, c_float, c_float, ctypes.c_char * 32]),
     # tracking of the kept boxes across frames (rtm3d_amd/track.py)
     'rtm3d_track_default_params': (c_int, [ctypes.POINTER(TrackParamsC)]),
     'rtm3d_tracks_state_bytes': (c_size_t, [c_int, c_int]),

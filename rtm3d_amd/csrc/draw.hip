@@ -19,65 +19,7 @@
 // v = p - P lies in [-8192, 16383].  d.d <= 2^29, v.d and v x d <= 2^29, |v|^2 < 2^29 (4|v|^2 in int64), 2 (v x d) <= 2^30 and its
 // square <= 2^60 (int64), t^2 (d.d) <= 2^16 * 2^29 (int64; t <= 128 = twice the largest radius).  Edge functions of the face:
 // (b - a) x (p - a) with factors <= 2^14, < 2^29.
-#include "common.h"
-#include "box_project.h"
-#include "../../include/rtm3d_hip.h"
-
-#define DRAW_MAX_BATCH 64
-#define DRAW_TW 64
-#define DRAW_TH 16
-#define DRAW_THREADS 256
-#define DRAW_PRIMS 18                  // per slot in a frame: face, 4 box sides, 12 edges, disc
-#define DRAW_BEV_PRIMS 5               // per slot in a panel: 4 outline segments, heading mark
-#define DRAW_MAX_SIDE 8192
-#define DRAW_MAX_RADIUS 64
-#define DRAW_FRAME_LAYERS (RTM3D_DRAW_FACE | RTM3D_DRAW_BOX2D | RTM3D_DRAW_WIREFRAME | RTM3D_DRAW_KEYPOINT)
-
-struct DrawBatch {
-    uint8_t* img[DRAW_MAX_BATCH];
-    int h[DRAW_MAX_BATCH], w[DRAW_MAX_BATCH];
-    int tile0[DRAW_MAX_BATCH + 1];     // first workgroup of frame i; [nb] = first workgroup of the panels
-};
-
-// truncation toward zero of a coordinate whose integer lies in [-8192, 8192]; false for anything else (NaN and infinities too)
-__device__ __forceinline__ bool draw_coord(double v, int& o) {
-    if (!(v > -(double)(DRAW_MAX_SIDE + 1) && v < (double)(DRAW_MAX_SIDE + 1))) return false;
-    o = (int)v;
-    return true;
-}
-
-// vertex vi of a slot: source 0 the regressed vertex, source 1 corner vi of the solved box through K
-__device__ __forceinline__ bool draw_vertex(const float* __restrict__ r, const double* __restrict__ xs, const double* __restrict__ k,
-                                            double sn, double cs, int source, int vi, int& x, int& y) {
-    double u, v;
-    if (source == 0) { u = (double)r[4 + 2 * vi]; v = (double)r[5 + 2 * vi]; }
-    else box_project_corner(xs, k, sn, cs, vi, u, v);
-    const bool a = draw_coord(u, x), b = draw_coord(v, y);
-    return a && b;
-}
-
-__device__ __forceinline__ bool seg_covers(int px, int py, int x0, int y0, int x1, int y1, int t2) {
-    const int dx = x1 - x0, dy = y1 - y0;
-    int vx = px - x0, vy = py - y0;
-    const int dd = dx * dx + dy * dy, k = vx * dx + vy * dy;
-    if (k <= 0 || k >= dd) {
-        if (k > 0) { vx = px - x1; vy = py - y1; }
-        return 4ll * (long long)(vx * vx + vy * vy) <= (long long)t2;
-    }
-    const long long cr = (long long)(2 * (vx * dy - vy * dx));
-    return cr * cr <= (long long)t2 * (long long)dd;
-}
-
-__device__ __forceinline__ bool tri_covers(int px, int py, int ax, int ay, int bx, int by, int cx, int cy) {
-    if ((bx - ax) * (cy - ay) - (by - ay) * (cx - ax) == 0) return false;
-    const int e0 = (bx - ax) * (py - ay) - (by - ay) * (px - ax);
-    const int e1 = (cx - bx) * (py - by) - (cy - by) * (px - bx);
-    const int e2 = (ax - cx) * (py - cy) - (ay - cy) * (px - cx);
-    return (e0 >= 0 && e1 >= 0 && e2 >= 0) || (e0 <= 0 && e1 <= 0 && e2 <= 0);
-}
-
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
+#include "draw_prims.h"                 // tile geometry, DrawBatch, draw_coord, the coverage tests (shared with draw_tracks.hip)
 
 __global__ __launch_bounds__(DRAW_THREADS) void records_draw_kernel(const DrawBatch fb, int nb, int topk, const float* __restrict__ rec,
                                                                    const double* __restrict__ K, const rtm3d_draw_params P,
@@ -314,12 +256,12 @@ extern "C" int rtm3d_draw_default_params(rtm3d_draw_params* p) {
     return 0;
 }
 
-extern "C" int rtm3d_records_draw(void* stream, int B, int topk, const float* d_rec, uint8_t* const* h_imgs, const int* h_hw,
-                                  const double* d_K_camera, const rtm3d_draw_params* params, uint8_t* d_bev) {
+int draw_check_args(int B, int topk, const float* d_rec, uint8_t* const* h_imgs, const int* h_hw, const double* d_K_camera,
+                    const rtm3d_draw_params* params, const uint8_t* d_bev, int max_layers, const char* layer_words, bool panels) {
     if (B < 1 || topk < 1 || topk > 65536) { rt_set_error("records_draw: bad sizes (B %d, topk %d)", B, topk); return 1; }
     if (!d_rec || !h_imgs || !h_hw || !params) { rt_set_error("records_draw: null pointer"); return 1; }
     const rtm3d_draw_params& P = *params;
-    if (P.layers < 1 || P.layers > (DRAW_FRAME_LAYERS | RTM3D_DRAW_BEV)) { rt_set_error("records_draw: layers %d is not a mask of the five layers", P.layers); return 1; }
+    if (P.layers < 1 || P.layers > max_layers) { rt_set_error("records_draw: layers %d is not a mask of the %s layers", P.layers, layer_words); return 1; }
     if (P.source != 0 && P.source != 1) { rt_set_error("records_draw: unknown source %d (0 regressed vertices, 1 solved box)", P.source); return 1; }
     if (P.min_flag != 1 && P.min_flag != 2) { rt_set_error("records_draw: min_flag %d (1 every detection, 2 3D-kept only)", P.min_flag); return 1; }
     if (P.thickness < 1 || P.thickness > 15) { rt_set_error("records_draw: thickness %d is outside 1..15", P.thickness); return 1; }
@@ -329,15 +271,12 @@ extern "C" int rtm3d_records_draw(void* stream, int B, int topk, const float* d_
         rt_set_error("records_draw: a colour table of %d classes (1..%d)", P.ncls, RTM3D_ENGINE_MAX_CLASSES); return 1;
     }
     if (P.source == 1 && !d_K_camera) { rt_set_error("records_draw: source 1 projects the solved boxes and needs d_K_camera"); return 1; }
-    const bool frames = (P.layers & DRAW_FRAME_LAYERS) != 0, panels = (P.layers & RTM3D_DRAW_BEV) != 0;
-    int bev_tiles = 0;
     if (panels) {
         if (!d_bev) { rt_set_error("records_draw: the bird's-eye layer is set and d_bev is NULL"); return 1; }
         if (P.bev_h < 1 || P.bev_w < 1 || P.bev_h > DRAW_MAX_SIDE || P.bev_w > DRAW_MAX_SIDE) {
             rt_set_error("records_draw: a bird's-eye panel of %d x %d (sides 1..%d)", P.bev_h, P.bev_w, DRAW_MAX_SIDE); return 1;
         }
         if (!(P.bev_m_per_px > 0.0) || !(P.bev_m_per_px < 1e300)) { rt_set_error("records_draw: bev_m_per_px %g is not a positive finite scale", P.bev_m_per_px); return 1; }
-        bev_tiles = ((P.bev_w + DRAW_TW - 1) / DRAW_TW) * ((P.bev_h + DRAW_TH - 1) / DRAW_TH);
     }
     for (int b = 0; b < B; ++b) {                                // the whole batch is checked before anything is painted
         const int h = h_hw[2 * b], w = h_hw[2 * b + 1];
@@ -346,6 +285,16 @@ extern "C" int rtm3d_records_draw(void* stream, int B, int topk, const float* d_
         }
         if (!h_imgs[b]) { rt_set_error("records_draw: frame %d is a NULL pointer", b); return 1; }
     }
+    return 0;
+}
+
+extern "C" int rtm3d_records_draw(void* stream, int B, int topk, const float* d_rec, uint8_t* const* h_imgs, const int* h_hw,
+                                  const double* d_K_camera, const rtm3d_draw_params* params, uint8_t* d_bev) {
+    const bool panels = params && (params->layers & RTM3D_DRAW_BEV) != 0;
+    if (draw_check_args(B, topk, d_rec, h_imgs, h_hw, d_K_camera, params, d_bev, DRAW_FRAME_LAYERS | RTM3D_DRAW_BEV, "five", panels)) return 1;
+    const rtm3d_draw_params& P = *params;
+    const bool frames = (P.layers & DRAW_FRAME_LAYERS) != 0;
+    const int bev_tiles = panels ? ((P.bev_w + DRAW_TW - 1) / DRAW_TW) * ((P.bev_h + DRAW_TH - 1) / DRAW_TH) : 0;
     for (int b0 = 0; b0 < B; b0 += DRAW_MAX_BATCH) {
         const int nb = B - b0 < DRAW_MAX_BATCH ? B - b0 : DRAW_MAX_BATCH;
         DrawBatch fb;

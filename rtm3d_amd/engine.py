@@ -435,7 +435,8 @@ class Engine(object):
         nms3d: as for detect; applied to the records and, with kitti=True, to the rows (a suppressed slot's row is zeroed).
         draw: None (nothing is painted, nothing is launched) or a draw.DrawParams: the records, after nms3d, are painted into
         ``images`` in place (draw.draw_records, one more launch behind the step; the frames must be contiguous); with the BEV
-        layer set the new (B, bev_h, bev_w, 3) panels are appended to what is returned.
+        layer set the new (B, bev_h, bev_w, 3) panels are appended to what is returned.  A draw.TrackDrawParams needs ``tracker``
+        (ValueError without one) and paints with the ids of this step and the tracker's table (draw.draw_tracks) instead.
         tracker: as for detect; it runs after nms3d and before draw, and the (B, topk) int32 ids are the last element of what is
         returned.  None launches nothing and returns what is returned without it."""
         import torch
@@ -455,6 +456,10 @@ class Engine(object):
         hw = (ctypes.c_int * (2 * B))(*[int(v) for i in imgs for v in i.shape[:2]])
         K = torch.as_tensor(K_camera, dtype=torch.float64, device=self.device).reshape(B, 9).contiguous()
         with torch.cuda.device(self.device):
+            if draw is not None and tracker is None:
+                from . import draw as _draw
+                if isinstance(draw, _draw.TrackDrawParams):
+                    raise ValueError('Engine.detect_frames: draw=TrackDrawParams paints track ids and needs tracker=')
             rec = torch.empty(B, topk, 32, dtype=torch.float32, device=self.device) if out is None else out
             rows = torch.empty(B, topk, 16, dtype=torch.float64, device=self.device) if kitti else None
             _lib.check(self.lib.rtm3d_engine_detect_frames(self.ctx, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
@@ -467,7 +472,10 @@ class Engine(object):
             panels = None
             if draw is not None:
                 from . import draw as _draw
-                panels = _draw.draw_records(list(images), rec, K, draw, check_classes=False)
+                if isinstance(draw, _draw.TrackDrawParams):
+                    panels = _draw.draw_tracks(list(images), rec, ids, K, draw, tracker=tracker, check_classes=False)
+                else:
+                    panels = _draw.draw_records(list(images), rec, K, draw, check_classes=False)
         res = (rec, rows) if kitti else (rec,)
         if panels is not None:
             res = res + (panels,)
