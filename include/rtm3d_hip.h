@@ -602,6 +602,98 @@ size_t rtm3d_engine_frames_workspace_bytes(rtm3d_ctx* ctx);
 int rtm3d_engine_detect_frames(rtm3d_ctx* ctx, void* stream, const uint8_t* const* h_imgs, const int* h_hw,
                                const double* d_K_camera, float* d_rec, double* d_kitti, void* d_workspace);
 
+/* ------------------------------------------------------------------ pixel formats (csrc/frames_convert.hip, csrc/engine.cpp)
+ * Camera frames as they reach a GPU - the video decoder's pitched NV12 / P010 surfaces, YUYV / UYVY of UVC and automotive
+ * cameras, I420 of software decoders, BGRA or pitched RGB rows of capture APIs - to the tightly packed uint8 (h, w, 3)
+ * frames that rtm3d_engine_detect_frames, rtm3d_preprocess_batch and rtm3d_records_draw read.  The conversion is its own
+ * launch (one per chunk of 32 frames, descriptors by value, no host synchronisation); the packed copy is what the drawing
+ * entry points paint into.  Added in ABI 9 without changing any existing declaration.
+ *
+ * THE RULE (integers only, int32, >> arithmetic; tests/pixfmt_ref.py restates it in numpy).
+ * Chroma of pixel (x, y): 4:2:0 formats (NV12, NV21, I420, P010) use the sample at (x >> 1, y >> 1); 4:2:2 formats (YUYV,
+ * UYVY) the chroma of the pixel's own pair on row y.  Nearest-sample replication is deliberate; siting-aware interpolation
+ * is out of scope.
+ * 8-bit samples: Y' = y - yo with yo = 16 (limited) or 0 (full), U = cb - 128, V = cr - 128, S = 16.
+ * P010: sample value = s >> 6 of the little-endian uint16 s; yo = 64 or 0, U = cb - 512, V = cr - 512, S = 18.
+ *   R = clamp((cy*Y' + crv*V         + (1 << (S-1))) >> S, 0, 255)
+ *   G = clamp((cy*Y' + cgu*U + cgv*V + (1 << (S-1))) >> S, 0, 255)
+ *   B = clamp((cy*Y' + cbu*U         + (1 << (S-1))) >> S, 0, 255)
+ * The coefficients are round(2^S * v), v the textbook value from (Kr, Kb) = (0.299, 0.114) for BT.601 and (0.2126, 0.0722)
+ * for BT.709: cy = sy, crv = 2 (1 - Kr) sc, cbu = 2 (1 - Kb) sc, cgu = -2 Kb (1 - Kb) / Kg sc, cgv = -2 Kr (1 - Kr) / Kg sc
+ * with Kg = 1 - Kr - Kb and the scales (sy, sc) = (255/219, 255/224) limited 8-bit, (1, 1) full 8-bit, (255/876, 255/896)
+ * limited 10-bit, (255/1023, 255/1023) full 10-bit.  [cy, crv, cgu, cgv, cbu]:
+ *   BT.601 limited, 8-bit S = 16 and 10-bit S = 18:  76309, 104597, -25675, -53279, 132201
+ *   BT.709 limited, 8-bit S = 16 and 10-bit S = 18:  76309, 117489, -13975, -34925, 138438
+ *   BT.601 full, 8-bit:                              65536,  91881, -22553, -46802, 116130
+ *   BT.709 full, 8-bit:                              65536, 103206, -12276, -30679, 121609
+ *   BT.601 full, 10-bit:                             65344,  91612, -22487, -46664, 115789
+ *   BT.709 full, 10-bit:                             65344, 102903, -12240, -30589, 121252
+ * (every intermediate is below 1.5e8 in magnitude).  RGB24 / BGR24 / RGBA32 / BGRA32 copy their three colour bytes, GRAY8
+ * writes the byte three times; matrix and range are ignored for them.  dst_order 0 writes R G B per pixel, 1 writes B G R -
+ * the channel order the checkpoint was trained on, which the library cannot know.
+ *
+ * REFUSALS, checked for the whole batch before the first launch (the message names the frame; a refused call has launched
+ * nothing): an unknown format, matrix or range, reserved != 0; a needed plane or a destination that is NULL; h or w < 1 or
+ * > 16384; a pitch below min_pitch; for P010 an odd plane address or an odd pitch.  There is NO other alignment requirement:
+ * plane bases, pitches and destinations may be any byte address.  Reads stay inside rows x row bytes of each plane (pitch
+ * padding need not exist behind the last row); exactly h * w * 3 bytes are written per frame.                             */
+#define RTM3D_PIX_RGB24 0   /* plane 0: R G B per pixel                                  */
+#define RTM3D_PIX_BGR24 1
+#define RTM3D_PIX_RGBA32 2  /* 4 bytes per pixel, the 4th ignored                         */
+#define RTM3D_PIX_BGRA32 3
+#define RTM3D_PIX_GRAY8 4   /* R = G = B = the byte (no range mapping)                    */
+#define RTM3D_PIX_NV12 5    /* plane 0: Y, w bytes x h rows; plane 1: Cb Cr interleaved, 2*cw bytes x ch rows */
+#define RTM3D_PIX_NV21 6    /* the same with Cr Cb                                        */
+#define RTM3D_PIX_I420 7    /* plane 0: Y; plane 1: Cb, plane 2: Cr, each cw bytes x ch rows */
+#define RTM3D_PIX_YUYV 8    /* plane 0: Y0 Cb Y1 Cr per pixel pair, 4*cw bytes x h rows   */
+#define RTM3D_PIX_UYVY 9    /* Cb Y0 Cr Y1                                                */
+#define RTM3D_PIX_P010 10   /* NV12 layout with little-endian uint16 samples, value = s >> 6 (10 bits) */
+/* cw = (w + 1) / 2, ch = (h + 1) / 2: odd sizes are legal, the last chroma sample serves one pixel / row */
+#define RTM3D_YUV_BT601 0
+#define RTM3D_YUV_BT709 1
+#define RTM3D_YUV_LIMITED 0
+#define RTM3D_YUV_FULL 1
+typedef struct rtm3d_frame_src {
+    const void* plane[3];   /* DEVICE pointers; unused planes NULL */
+    int pitch[3];           /* bytes from one row of the plane to the next, >= the row's own bytes */
+    int h, w;
+    int format, matrix, range, reserved;   /* matrix / range ignored for RGB* and GRAY8; reserved = 0 */
+} rtm3d_frame_src;
+
+/* HOST helpers (no device access).
+ * rtm3d_frame_src_layout: the planes of a format at a size - their number, the bytes of a row (the least pitch) and the rows
+ * of each; entries of unused planes are 0.
+ * rtm3d_yuv_coefficients: out[0:5] = the table row [cy, crv, cgu, cgv, cbu] the kernel uses for a YUV format, out[5] = yo,
+ * out[6] = the chroma offset (128 or 512), out[7] = S.
+ * rtm3d_frames_convert_plan: the schedule rtm3d_frames_convert gives a batch - the very numbers the launcher uses, it calls
+ * the same code; out[(B + 31) / 32] receives one entry per chunk.  A frame is cut into runs of px_per_thread pixels of
+ * rows_per_thread consecutive rows; thread t = block * threads + lane of grid row i (frame first + i) takes run
+ * t % runs_per_row of row group t / runs_per_row, runs_per_row = ceil(w / px_per_thread), and leaves when t >= the frame's
+ * own number of runs.  runs is the largest of the chunk, grid_x = ceil(runs / threads), grid_y = count.  The sources are
+ * validated as by rtm3d_frames_convert (destinations aside).
+ * rtm3d_frames_convert_check: every refusal of rtm3d_frames_convert, without a launch.                                */
+int rtm3d_frame_src_layout(int format, int h, int w, int* n_planes, int min_pitch[3], int rows[3]);
+int rtm3d_yuv_coefficients(int format, int matrix, int range, int out[8]);
+typedef struct rtm3d_convert_plan {
+    int first, count;                      /* frames first .. first + count - 1 */
+    int px_per_thread, rows_per_thread;    /* 8 pixels of 2 rows (one 4:2:0 chroma row) per thread */
+    int threads;                           /* per workgroup */
+    int runs;                              /* thread runs of the chunk's largest frame */
+    int grid_x, grid_y;
+} rtm3d_convert_plan;
+int rtm3d_frames_convert_plan(int B, const rtm3d_frame_src* h_src, rtm3d_convert_plan* out);
+int rtm3d_frames_convert_check(int B, const rtm3d_frame_src* h_src, uint8_t* const* h_dst, int dst_order);
+
+/* The conversion: h_src[B] and h_dst[B] are HOST arrays, h_dst[b] a DEVICE pointer to h * w * 3 packed bytes.  Stream-ordered. */
+int rtm3d_frames_convert(void* stream, int B, const rtm3d_frame_src* h_src, uint8_t* const* h_dst, int dst_order);
+
+/* One detect step of an engine fed by such sources: rtm3d_frames_convert into h_packed[B] (DEVICE buffers of h * w * 3 bytes,
+ * which hold the packed frames afterwards - the drawing entry points paint into them), then rtm3d_engine_detect_frames on
+ * h_packed with the (h, w) of the sources.  Same workspace, same rtm3d_engine_set_frame_params, stream-ordered with no host
+ * synchronisation; sources and frame geometry of the whole batch are validated before the first launch.                 */
+int rtm3d_engine_detect_frames_src(rtm3d_ctx* ctx, void* stream, const rtm3d_frame_src* h_src, uint8_t* const* h_packed,
+                                   int dst_order, const double* d_K_camera, float* d_rec, double* d_kitti, void* d_workspace);
+
 /* ------------------------------------------------------------------ box overlaps (csrc/box_overlap.hip)
  * Rotated-box overlaps in the ground plane and 3D non-maximum suppression of detection records.  Added in ABI 9 without
  * changing any existing declaration; nothing calls these unless the caller does (no plan, engine file or record changes).

@@ -104,6 +104,18 @@ class PreprocessPlan(ctypes.Structure):
                 ('grid_x', c_int), ('border_grid_x', c_int)]
 
 
+class FrameSrc(ctypes.Structure):
+    """Mirror of struct rtm3d_frame_src (rtm3d_amd/pixfmt.py)."""
+    _fields_ = [('plane', c_void_p * 3), ('pitch', c_int * 3), ('h', c_int), ('w', c_int),
+                ('format', c_int), ('matrix', c_int), ('range', c_int), ('reserved', c_int)]
+
+
+class ConvertPlan(ctypes.Structure):
+    """Mirror of struct rtm3d_convert_plan (one per chunk of 32 frames)."""
+    _fields_ = [('first', c_int), ('count', c_int), ('px_per_thread', c_int), ('rows_per_thread', c_int), ('threads', c_int),
+                ('runs', c_int), ('grid_x', c_int), ('grid_y', c_int)]
+
+
 # name -> (restype, argtypes); also the list of symbols include/rtm3d_hip.h declares
 SIGNATURES = {
     'rtm3d_last_error': (ctypes.c_char_p, []),
@@ -188,6 +200,14 @@ SIGNATURES = {
     'rtm3d_engine_set_frame_params': (c_int, [c_void_p, ctypes.POINTER(FrameParams)]),
     'rtm3d_engine_frames_workspace_bytes': (c_size_t, [c_void_p]),
     'rtm3d_engine_detect_frames': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # pixel formats: decoder / camera surfaces to packed frames (rtm3d_amd/pixfmt.py, rtm3d_amd/engine.py)
+    'rtm3d_frame_src_layout': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'rtm3d_yuv_coefficients': (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    'rtm3d_frames_convert_plan': (c_int, [c_int, ctypes.POINTER(FrameSrc), ctypes.POINTER(ConvertPlan)]),
+    'rtm3d_frames_convert_check': (c_int, [c_int, ctypes.POINTER(FrameSrc), c_void_p, c_int]),
+    'rtm3d_frames_convert': (c_int, [c_void_p, c_int, ctypes.POINTER(FrameSrc), c_void_p, c_int]),
+    'rtm3d_engine_detect_frames_src': (c_int, [c_void_p, c_void_p, ctypes.POINTER(FrameSrc), c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                               c_void_p]),
     # box overlaps / 3D NMS of records (rtm3d_amd/box_overlap.py)
     'rtm3d_box_overlaps': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'rtm3d_records_nms3d': (c_int, [c_void_p, c_int, c_int, c_void_p, c_double, c_int, c_int, c_void_p]),

@@ -483,6 +483,57 @@ class Engine(object):
             res = res + (ids,)
         return res if len(res) > 1 else res[0]
 
+    def detect_frames_src(self, sources, K_camera, order='rgb', packed=None, kitti=False, out=None, draw=None, tracker=None, nms3d=None):
+        """detect_frames fed by decoder / camera surfaces (rtm3d_engine_detect_frames_src): sources = list of B
+        pixfmt.FrameSource (NV12, P010, YUYV, I420, pitched RGB / BGRA ... of any sizes that fit the canvas after Resize).  One
+        more launch in front of the step converts them into ``packed`` - B contiguous uint8 (h, w, 3) CUDA tensors, allocated
+        when None and reachable afterwards as ``engine.last_packed`` - and the step reads those; nothing synchronises.
+        order: 'rgb' | 'bgr', the byte order of the packed pixels = the channel order the checkpoint was trained on; the
+        library cannot know it (the reference's loader hands the network B G R).
+        Every other keyword is detect_frames' and what is returned is what it returns; draw= paints into ``packed``."""
+        import torch
+        from . import box_overlap, pixfmt
+        nms3d = box_overlap.nms3d_options(nms3d)
+        B, topk = self.info['B'], self.info['topk']
+        if getattr(self, 'frames_workspace', None) is None:
+            raise RuntimeError('Engine.detect_frames_src: call set_frame_params(mean, std, resize_to) first')
+        sources = list(sources)
+        if len(sources) != B:
+            raise ValueError('this engine runs batches of %d frames, got %d' % (B, len(sources)))
+        src = pixfmt.c_sources(sources)
+        K = torch.as_tensor(K_camera, dtype=torch.float64, device=self.device).reshape(B, 9).contiguous()
+        with torch.cuda.device(self.device):
+            if draw is not None and tracker is None:
+                from . import draw as _draw
+                if isinstance(draw, _draw.TrackDrawParams):
+                    raise ValueError('Engine.detect_frames_src: draw=TrackDrawParams paints track ids and needs tracker=')
+            packed = pixfmt.packed_buffers(sources, packed)
+            ptrs = (ctypes.c_void_p * B)(*[p.data_ptr() for p in packed])
+            rec = torch.empty(B, topk, 32, dtype=torch.float32, device=self.device) if out is None else out
+            rows = torch.empty(B, topk, 16, dtype=torch.float64, device=self.device) if kitti else None
+            _lib.check(self.lib.rtm3d_engine_detect_frames_src(
+                self.ctx, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), src, ptrs,
+                pixfmt._lookup(pixfmt.ORDERS, order, 'order'), ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+                ctypes.c_void_p(rows.data_ptr()) if kitti else None, ctypes.c_void_p(self.frames_workspace.data_ptr())),
+                'engine_detect_frames_src')
+            self.last_packed = packed
+            if nms3d is not None:
+                box_overlap.nms3d_records(rec, kitti_rows=rows, **nms3d)
+            ids = None if tracker is None else tracker.update(rec, dt=tracker.dt, ego=tracker.ego)
+            panels = None
+            if draw is not None:
+                from . import draw as _draw
+                if isinstance(draw, _draw.TrackDrawParams):
+                    panels = _draw.draw_tracks(packed, rec, ids, K, draw, tracker=tracker, check_classes=False)
+                else:
+                    panels = _draw.draw_records(packed, rec, K, draw, check_classes=False)
+        res = (rec, rows) if kitti else (rec,)
+        if panels is not None:
+            res = res + (panels,)
+        if ids is not None:
+            res = res + (ids,)
+        return res if len(res) > 1 else res[0]
+
     def close(self):
         if self.ctx:
             self.lib.rtm3d_ctx_destroy(self.ctx)
