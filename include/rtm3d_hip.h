@@ -694,6 +694,115 @@ int rtm3d_frames_convert(void* stream, int B, const rtm3d_frame_src* h_src, uint
 int rtm3d_engine_detect_frames_src(rtm3d_ctx* ctx, void* stream, const rtm3d_frame_src* h_src, uint8_t* const* h_packed,
                                    int dst_order, const double* d_K_camera, float* d_rec, double* d_kitti, void* d_workspace);
 
+/* ------------------------------------------------------------------ lens undistortion (csrc/lens.hip, csrc/engine.cpp)
+ * Every other entry point takes a frame for a pinhole image described by a 3 x 3 K.  A frame of a real camera is one only
+ * after rectification: this section builds rectifying maps on the device and resamples packed frames through them, the stage
+ * between rtm3d_frames_convert and rtm3d_engine_detect_frames.  One launch per chunk of 32 frames, descriptors by value, no
+ * host synchronisation.  Added in ABI 9 without changing any existing declaration, plan, engine file, record or default.
+ *
+ * THE MAP is plain data: ho * wo * 2 int32 on the device, 4-byte aligned.  Entry 2 * (y * wo + x) is sx, the next one sy:
+ * the position in the SOURCE frame that destination pixel (x, y) is sampled from, in units of 1/32 pixel; integer
+ * coordinates are pixel centres.  sx == RTM3D_LENS_OUTSIDE (INT32_MIN) means "no source"; any other int32 pair is legal.
+ * A map may come from elsewhere (a table of another lens model, scaled by 32 and rounded): the remap asks nothing of it.
+ *
+ * THE REMAP RULE (integers only, int32, >> arithmetic; tests/lens_ref.py restates it in numpy).  Destination pixel (x, y),
+ * channel c, of a source of h x w pixels:
+ *   sx == INT32_MIN:  out = fill[c].  Otherwise
+ *   ix = sx >> 5, ax = sx & 31, iy = sy >> 5, ay = sy & 31,
+ *   S(i, j) = src[(j * w + i) * 3 + c] if 0 <= i < w and 0 <= j < h, else fill[c]   (decided per sample),
+ *   out = ((32-ax)*(32-ay)*S(ix,iy) + ax*(32-ay)*S(ix+1,iy) + (32-ax)*ay*S(ix,iy+1) + ax*ay*S(ix+1,iy+1) + 512) >> 10.
+ * The four weights sum to 1024, so out <= 255.  A sample of weight 0 need not be read; reads stay inside the h * w * 3 bytes of
+ * each source; exactly ho * wo * 3 bytes are written per frame; sources and destinations may be any byte address.
+ *
+ * REFUSALS of the remap, checked for the whole batch before the first launch (the message names the frame; a refused call has
+ * launched nothing): a NULL pointer (source, destination, map, fill), a side of the source or of the map < 1 or > 16384, a
+ * map address that is no multiple of 4, reserved != 0, a destination that overlaps its own source.
+ *
+ * THE MAP BUILDER (fp64, one fixed operation order, compiled without contraction; + - * / are IEEE, so the two polynomial
+ * models are defined bit for bit; sqrt and atan of the fisheye model are the device library's).  R (row-major) takes a ray
+ * of the RECTIFIED camera to a ray of the PHYSICAL camera - the transpose of the matrix OpenCV's initUndistortRectifyMap
+ * is given; the identity when there is no rectifying rotation.  Kr = the rectified camera's K.  Destination pixel (u, v),
+ * every line evaluated left to right as written:
+ *   a = ((double)u - Kr[2]) / Kr[0],  b = ((double)v - Kr[5]) / Kr[4]
+ *   X = R[0]*a + R[1]*b + R[2],  Y = R[3]*a + R[4]*b + R[5],  Wz = R[6]*a + R[7]*b + R[8]
+ *   !(Wz > 0): OUTSIDE.   x = X / Wz,  y = Y / Wz
+ * RTM3D_LENS_BROWN, dist = k1 k2 p1 p2 k3 k4 k5 k6 (the rational model; zeros give the 5-parameter one):
+ *   r2 = x*x + y*y,  num = 1 + r2*(k1 + r2*(k2 + r2*k3)),  den = 1 + r2*(k4 + r2*(k5 + r2*k6)),  cdist = num / den
+ *   xd = x*cdist + ((2*p1)*x*y + p2*(r2 + (2*x)*x)),  yd = y*cdist + (p1*(r2 + (2*y)*y) + (2*p2)*x*y)
+ * RTM3D_LENS_FISHEYE (Kannala-Brandt equidistant), dist = k1 k2 k3 k4 0 0 0 0:
+ *   r = sqrt(x*x + y*y),  t = atan(r),  t2 = t*t,  td = t*(1 + t2*(k1 + t2*(k2 + t2*(k3 + t2*k4))))
+ *   s = r > 1e-8 ? td / r : 1,  xd = x*s,  yd = y*s
+ * Both:  U = K[0]*xd + K[2],  V = K[4]*yd + K[5];  either not finite or above 2^20 in magnitude: OUTSIDE; otherwise
+ *   sx = (int32)floor(U*32.0 + 0.5),  sy = (int32)floor(V*32.0 + 0.5).
+ * An OUTSIDE entry is written as the pair (INT32_MIN, INT32_MIN).
+ * REFUSALS of the builder, before the first launch (the message names the map): an unknown kind; in K or Kr an entry [1], [3],
+ * [6] or [7] that is not 0, [8] that is not 1, fx or fy that is not > 0; a side of the lens or of the map < 1 or > 16384; a
+ * non-zero entry among the last four of a fisheye dist; a NULL or misaligned map.
+ *
+ * OUT OF SCOPE: choosing an "optimal" new camera matrix (callers pass Kr); filters other than this bilinear; fusing the remap
+ * into the pixel-format conversion; taking records back into the raw, distorted frame; parity with OpenCV's remap and
+ * initUndistortRectifyMap - the rules above restate the textbook models, OpenCV was not at hand to pin them against (as
+ * with the KITTI and TrackEval restatements): the fixed-point weights (5 bits here) and the rounding differ by design.    */
+#define RTM3D_LENS_OUTSIDE INT32_MIN
+#define RTM3D_LENS_BROWN 0
+#define RTM3D_LENS_FISHEYE 1
+typedef struct rtm3d_lens_map {
+    const int32_t* d_map;                  /* DEVICE pointer: ho * wo pairs (sx, sy) */
+    int ho, wo;                            /* the size of the frame the map makes */
+    int reserved;                          /* 0 */
+} rtm3d_lens_map;
+typedef struct rtm3d_lens_model {          /* the physical camera */
+    int kind;                              /* RTM3D_LENS_BROWN | RTM3D_LENS_FISHEYE */
+    int h, w;                              /* the size of its frames */
+    double K[9];                           /* row-major 3 x 3, no skew */
+    double dist[8];
+} rtm3d_lens_model;
+typedef struct rtm3d_lens_rect {           /* the pinhole image made */
+    int ho, wo;
+    double K[9];                           /* Kr */
+    double R[9];                           /* rectified ray -> physical ray */
+} rtm3d_lens_rect;
+
+/* rtm3d_frames_remap_plan: the schedule rtm3d_frames_remap gives a batch - the very numbers the launcher uses, it calls the
+ * same code; out[(B + 31) / 32] receives one entry per chunk.  A destination row is cut into runs of px_per_thread
+ * consecutive pixels; thread t = block * threads + lane of grid row i (frame first + i) takes run t % runs_per_row of row
+ * t / runs_per_row, runs_per_row = ceil(wo / px_per_thread), and leaves when t >= the frame's own number of runs.  runs is
+ * the largest of the chunk, grid_x = ceil(runs / threads), grid_y = count.  The maps are validated as by rtm3d_frames_remap.
+ * rtm3d_frames_remap_check: every refusal of rtm3d_frames_remap, without a launch.                                      */
+typedef struct rtm3d_remap_plan {
+    int first, count;                      /* frames first .. first + count - 1 */
+    int px_per_thread;                     /* 4 consecutive pixels of one row: 32 B of map, 12 B of output */
+    int threads;                           /* per workgroup */
+    int runs;                              /* thread runs of the chunk's largest destination */
+    int grid_x, grid_y;
+} rtm3d_remap_plan;
+int rtm3d_frames_remap_plan(int B, const rtm3d_lens_map* h_maps, rtm3d_remap_plan* out);
+int rtm3d_frames_remap_check(int B, const uint8_t* const* h_src, const int* h_hw, const rtm3d_lens_map* h_maps,
+                             uint8_t* const* h_dst, const uint8_t fill[3]);
+
+/* The remap: h_src[B] HOST array of DEVICE pointers to packed uint8 (h, w, 3) frames (the output of rtm3d_frames_convert, for
+ * one), h_hw[2B] their (h, w), h_maps[B] (frames may share a map), h_dst[b] a DEVICE pointer to ho * wo * 3 packed bytes.
+ * Stream-ordered.                                                                                                       */
+int rtm3d_frames_remap(void* stream, int B, const uint8_t* const* h_src, const int* h_hw, const rtm3d_lens_map* h_maps,
+                       uint8_t* const* h_dst, const uint8_t fill[3]);
+
+/* The builder: map i of n, h_maps[i] a DEVICE pointer to ho * wo * 2 int32, from lens h_models[i] and rectified camera
+ * h_rect[i] (all HOST arrays).  One launch per chunk of 8 maps, descriptors by value, stream-ordered.                   */
+int rtm3d_lens_map_build(void* stream, int n, const rtm3d_lens_model* h_models, const rtm3d_lens_rect* h_rect,
+                         int32_t* const* h_maps);
+
+/* One detect step of an engine fed by frames of a real lens: with h_src != NULL rtm3d_frames_convert into h_packed[B] (h_hw is
+ * ignored, the sizes are the sources'); with h_src == NULL h_packed[B] already holds the raw packed frames of sizes h_hw[2B].
+ * Then rtm3d_frames_remap of h_packed through h_maps[B] into h_rect[B] (DEVICE buffers of ho * wo * 3 bytes), then
+ * rtm3d_engine_detect_frames on h_rect with the maps' (ho, wo) and d_K_rect (B x 9 fp64, the RECTIFIED cameras' intrinsics).
+ * Records and KITTI rows are in the pixels and the camera of the rectified frames - the frames the drawing entry points
+ * then paint into.  Same workspace, same rtm3d_engine_set_frame_params, no host synchronisation; everything the three steps
+ * would refuse is refused before the first launch.                                                                      */
+int rtm3d_engine_detect_frames_lens(rtm3d_ctx* ctx, void* stream, const rtm3d_frame_src* h_src, uint8_t* const* h_packed,
+                                    const int* h_hw, int dst_order, const rtm3d_lens_map* h_maps, uint8_t* const* h_rect,
+                                    const uint8_t fill[3], const double* d_K_rect, float* d_rec, double* d_kitti,
+                                    void* d_workspace);
+
 /* ------------------------------------------------------------------ box overlaps (csrc/box_overlap.hip)
  * Rotated-box overlaps in the ground plane and 3D non-maximum suppression of detection records.  Added in ABI 9 without
  * changing any existing declaration; nothing calls these unless the caller does (no plan, engine file or record changes).

@@ -116,6 +116,27 @@ class ConvertPlan(ctypes.Structure):
                 ('runs', c_int), ('grid_x', c_int), ('grid_y', c_int)]
 
 
+class LensMapC(ctypes.Structure):
+    """Mirror of struct rtm3d_lens_map (rtm3d_amd/lens.py)."""
+    _fields_ = [('d_map', c_void_p), ('ho', c_int), ('wo', c_int), ('reserved', c_int)]
+
+
+class LensModelC(ctypes.Structure):
+    """Mirror of struct rtm3d_lens_model."""
+    _fields_ = [('kind', c_int), ('h', c_int), ('w', c_int), ('K', c_double * 9), ('dist', c_double * 8)]
+
+
+class LensRectC(ctypes.Structure):
+    """Mirror of struct rtm3d_lens_rect."""
+    _fields_ = [('ho', c_int), ('wo', c_int), ('K', c_double * 9), ('R', c_double * 9)]
+
+
+class RemapPlan(ctypes.Structure):
+    """Mirror of struct rtm3d_remap_plan (one per chunk of 32 frames)."""
+    _fields_ = [('first', c_int), ('count', c_int), ('px_per_thread', c_int), ('threads', c_int), ('runs', c_int), ('grid_x', c_int),
+                ('grid_y', c_int)]
+
+
 # name -> (restype, argtypes); also the list of symbols include/rtm3d_hip.h declares
 SIGNATURES = {
     'rtm3d_last_error': (ctypes.c_char_p, []),
@@ -208,6 +229,13 @@ SIGNATURES = {
     'rtm3d_frames_convert': (c_int, [c_void_p, c_int, ctypes.POINTER(FrameSrc), c_void_p, c_int]),
     'rtm3d_engine_detect_frames_src': (c_int, [c_void_p, c_void_p, ctypes.POINTER(FrameSrc), c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                                c_void_p]),
+    # lens undistortion: rectifying maps and the bilinear remap (rtm3d_amd/lens.py, rtm3d_amd/engine.py)
+    'rtm3d_frames_remap_plan': (c_int, [c_int, ctypes.POINTER(LensMapC), ctypes.POINTER(RemapPlan)]),
+    'rtm3d_frames_remap_check': (c_int, [c_int, c_void_p, c_void_p, ctypes.POINTER(LensMapC), c_void_p, c_void_p]),
+    'rtm3d_frames_remap': (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(LensMapC), c_void_p, c_void_p]),
+    'rtm3d_lens_map_build': (c_int, [c_void_p, c_int, ctypes.POINTER(LensModelC), ctypes.POINTER(LensRectC), c_void_p]),
+    'rtm3d_engine_detect_frames_lens': (c_int, [c_void_p, c_void_p, ctypes.POINTER(FrameSrc), c_void_p, c_void_p, c_int,
+                                                ctypes.POINTER(LensMapC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # box overlaps / 3D NMS of records (rtm3d_amd/box_overlap.py)
     'rtm3d_box_overlaps': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'rtm3d_records_nms3d': (c_int, [c_void_p, c_int, c_int, c_void_p, c_double, c_int, c_int, c_void_p]),

@@ -373,6 +373,7 @@ struct EngineState {
     std::vector<rtm3d_frame_geom> geom;
     std::vector<int> resized_hw;
     std::vector<int> src_hw;             // (h, w) of the sources of rtm3d_engine_detect_frames_src
+    std::vector<int> rect_hw;            // (ho, wo) of the maps of rtm3d_engine_detect_frames_lens
 };
 
 void free_state(void* p) { delete (EngineState*)p; }
@@ -565,4 +566,31 @@ extern "C" int rtm3d_engine_detect_frames_src(rtm3d_ctx* ctx, void* stream, cons
     if (rtm3d_frame_geometry(I.B, st->src_hw.data(), st->resize_to, I.H, I.W, st->geom.data())) return 1;
     if (rtm3d_frames_convert(stream, I.B, h_src, h_packed, dst_order)) return 1;
     return rtm3d_engine_detect_frames(ctx, stream, h_packed, st->src_hw.data(), d_K_camera, d_rec, d_kitti, d_workspace);
+}
+
+extern "C" int rtm3d_engine_detect_frames_lens(rtm3d_ctx* ctx, void* stream, const rtm3d_frame_src* h_src, uint8_t* const* h_packed,
+                                               const int* h_hw, int dst_order, const rtm3d_lens_map* h_maps, uint8_t* const* h_rect,
+                                               const uint8_t fill[3], const double* d_K_rect, float* d_rec, double* d_kitti,
+                                               void* d_workspace) {
+    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
+    if (!st) EFAIL("engine_detect_frames_lens: the context was not made by rtm3d_engine_load");
+    if (!h_packed || (!h_src && !h_hw) || !h_maps || !h_rect || !fill || !d_K_rect || !d_rec || !d_workspace)
+        EFAIL("engine_detect_frames_lens: null argument");
+    if (!st->frames) EFAIL("engine_detect_frames_lens: call rtm3d_engine_set_frame_params first");
+    const rtm3d_engine_info& I = st->info;
+    // everything the three steps would refuse, before the first launch: the sources, the maps and both sets of buffers, then
+    // the rectified frames' place on the canvas
+    if (h_src && rtm3d_frames_convert_check(I.B, h_src, h_packed, dst_order)) return 1;
+    st->src_hw.resize((size_t)I.B * 2);
+    st->rect_hw.resize((size_t)I.B * 2);
+    for (int b = 0; b < I.B; ++b) {
+        st->src_hw[2 * b] = h_src ? h_src[b].h : h_hw[2 * b];
+        st->src_hw[2 * b + 1] = h_src ? h_src[b].w : h_hw[2 * b + 1];
+    }
+    if (rtm3d_frames_remap_check(I.B, h_packed, st->src_hw.data(), h_maps, h_rect, fill)) return 1;
+    for (int b = 0; b < I.B; ++b) { st->rect_hw[2 * b] = h_maps[b].ho; st->rect_hw[2 * b + 1] = h_maps[b].wo; }
+    if (rtm3d_frame_geometry(I.B, st->rect_hw.data(), st->resize_to, I.H, I.W, st->geom.data())) return 1;
+    if (h_src && rtm3d_frames_convert(stream, I.B, h_src, h_packed, dst_order)) return 1;
+    if (rtm3d_frames_remap(stream, I.B, h_packed, st->src_hw.data(), h_maps, h_rect, fill)) return 1;
+    return rtm3d_engine_detect_frames(ctx, stream, h_rect, st->rect_hw.data(), d_K_rect, d_rec, d_kitti, d_workspace);
 }

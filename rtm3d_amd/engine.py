@@ -534,6 +534,74 @@ class Engine(object):
             res = res + (ids,)
         return res if len(res) > 1 else res[0]
 
+    def detect_frames_lens(self, frames_or_sources, maps, order='rgb', fill=(0, 0, 0), K_rect=None, packed=None, rect=None, kitti=False,
+                           out=None, draw=None, tracker=None, nms3d=None):
+        """detect_frames fed by frames of a real lens (rtm3d_engine_detect_frames_lens): frames_or_sources = list of B raw
+        frames, either all uint8 (h, w, 3) CUDA tensors or all pixfmt.FrameSource (converted into ``packed`` first, as by
+        detect_frames_src, in ``order``); maps = list of B lens.LensMap (frames may share one).  One more launch resamples the
+        raw frames through the maps into ``rect`` - B contiguous uint8 (ho, wo, 3) CUDA tensors, allocated when None - and the
+        step reads those with K_rect, the (B, 9) intrinsics of the RECTIFIED cameras (None: each map's own K_rect); nothing
+        synchronises.  Records and KITTI rows are in the pixels and the camera of the rectified frames; draw= paints into them.
+        fill: the bytes of a pixel without a source.  Every other keyword is detect_frames'.  Returns what detect_frames
+        returns, as a tuple, with the list of rectified frames appended: (records[, rows][, panels][, ids], rect)."""
+        import torch
+        from . import box_overlap, lens, pixfmt
+        nms3d = box_overlap.nms3d_options(nms3d)
+        B, topk = self.info['B'], self.info['topk']
+        if getattr(self, 'frames_workspace', None) is None:
+            raise RuntimeError('Engine.detect_frames_lens: call set_frame_params(mean, std, resize_to) first')
+        raw, maps = list(frames_or_sources), list(maps)
+        if len(raw) != B or len(maps) != B:
+            raise ValueError('this engine runs batches of %d frames, got %d frames and %d maps' % (B, len(raw), len(maps)))
+        cm = lens.c_maps(maps)
+        from_src = all(isinstance(r, pixfmt.FrameSource) for r in raw)
+        if not from_src and any(isinstance(r, pixfmt.FrameSource) for r in raw):
+            raise ValueError('Engine.detect_frames_lens: either all frames are FrameSource or none is')
+        if K_rect is None:
+            if any(m.K_rect is None for m in maps):
+                raise ValueError('Engine.detect_frames_lens: a map without K_rect needs K_rect=')
+            K_rect = np.stack([m.K_rect for m in maps])
+        K = torch.as_tensor(K_rect, dtype=torch.float64, device=self.device).reshape(B, 9).contiguous()
+        with torch.cuda.device(self.device):
+            if draw is not None and tracker is None:
+                from . import draw as _draw
+                if isinstance(draw, _draw.TrackDrawParams):
+                    raise ValueError('Engine.detect_frames_lens: draw=TrackDrawParams paints track ids and needs tracker=')
+            if from_src:
+                src, hw = pixfmt.c_sources(raw), None
+                packed = pixfmt.packed_buffers(raw, packed)
+            else:
+                src = None
+                packed = lens.packed_frames(raw)
+                hw = (ctypes.c_int * (2 * B))(*[int(v) for p in packed for v in p.shape[:2]])
+            rect = lens.rect_buffers(maps, rect)
+            pptr = (ctypes.c_void_p * B)(*[p.data_ptr() for p in packed])
+            rptr = (ctypes.c_void_p * B)(*[r.data_ptr() for r in rect])
+            rec = torch.empty(B, topk, 32, dtype=torch.float32, device=self.device) if out is None else out
+            rows = torch.empty(B, topk, 16, dtype=torch.float64, device=self.device) if kitti else None
+            _lib.check(self.lib.rtm3d_engine_detect_frames_lens(
+                self.ctx, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), src, pptr, hw,
+                pixfmt._lookup(pixfmt.ORDERS, order, 'order'), cm, rptr, lens.c_fill(fill), ctypes.c_void_p(K.data_ptr()),
+                ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(rows.data_ptr()) if kitti else None,
+                ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames_lens')
+            self.last_packed, self.last_rect = packed, rect
+            if nms3d is not None:
+                box_overlap.nms3d_records(rec, kitti_rows=rows, **nms3d)
+            ids = None if tracker is None else tracker.update(rec, dt=tracker.dt, ego=tracker.ego)
+            panels = None
+            if draw is not None:
+                from . import draw as _draw
+                if isinstance(draw, _draw.TrackDrawParams):
+                    panels = _draw.draw_tracks(rect, rec, ids, K, draw, tracker=tracker, check_classes=False)
+                else:
+                    panels = _draw.draw_records(rect, rec, K, draw, check_classes=False)
+        res = (rec, rows) if kitti else (rec,)
+        if panels is not None:
+            res = res + (panels,)
+        if ids is not None:
+            res = res + (ids,)
+        return res + (rect,)
+
     def close(self):
         if self.ctx:
             self.lib.rtm3d_ctx_destroy(self.ctx)
