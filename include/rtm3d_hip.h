@@ -1019,7 +1019,8 @@ int rtm3d_records_draw(void* stream, int B, int topk, const float* d_rec, uint8_
  *     Where several matchings attain the maximum, within the fp64 rounding of the sums, any one of them may be returned - the
  *     same one on every call with the same inputs: no result depends on the order in which lanes or atomics retire.  (The
  *     kernel runs shortest augmenting paths over the live slots that have a candidate, in slot order, taking the lowest record
- *     slot at equal slack: csrc/track.hip.)  thresh must be finite under this rule (the gains are differences from it).
+ *     slot at equal slack: the solver of csrc/assign_wave.h.)  thresh must be finite under this rule (the gains are differences
+ *     from it).
  * 4 UPDATE a matched slot with its detection z (zry = wrap(z ry)), everything on the right of one line from before that line:
  *     S = Ppp + r_pos;  Kp = Ppp / S;  Kv = Ppv / S
  *     per axis: y = zX - X;  X = X + Kp * y;  vx = vx + Kv * y
@@ -1183,8 +1184,8 @@ int rtm3d_draw_label_text(const rtm3d_draw_tracks_params* p, int id, int cls, fl
  * the largest sum of scores; unmatched rows and columns cost nothing; a non-candidate is never matched.  This is step 3b of
  * "tracking" with gain = w.  Where several matchings attain the maximum within the fp64 rounding of the sums, any one may be
  * returned, the same one on every call with the same inputs.  d_match [F][cap_g] int32: the tracker slot, or -1 (also beyond
- * ng).  One wavefront per frame runs shortest augmenting paths; a frame with ng, nt <= 64 with one column per lane, a larger one
- * with four - the frame's own size decides, not the caps.
+ * ng).  One wavefront per frame runs shortest augmenting paths (csrc/assign_wave.h, the solver step 3b runs); a frame with ng,
+ * nt <= 64 with one column per lane, a larger one with four - the frame's own size decides, not the caps.
  *
  * HOTA (rtm3d_mot_hota), per sequence:
  * 1 ALIGNMENT, for every frame in frame order: rowsum[g] = sum over t < nt of sim[g][t] in t order, colsum[t] = sum over g < ng

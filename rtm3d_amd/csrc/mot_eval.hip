@@ -12,38 +12,30 @@
 //   mot_clear_kernel       one wave per sequence, walking its frames with the carried identity state.  A frame's scores depend on
 //                          the previous frame's match, so the frames of a sequence are a chain: S waves are all the parallelism
 //                          CLEAR has.
-// ASSIGN is the shortest-augmenting-path solver of csrc/track.hip (step 3b of "tracking") restated for a frame of ng x nt with the
-// gain w: ONE wave runs the paths, lane L owns NC tracker slots with their duals and slacks in registers, row duals, the two owner
-// arrays and the predecessors are in LDS, "stay unmatched" is a zero-cost column private to every row kept as one scalar per path.
+// ASSIGN is the one-wave shortest-augmenting-path solver of assign_wave.h (the tracker's optimal match runs the same text) on a
+// frame of ng x nt with the gain w: every ground-truth slot 0 .. ng - 1 is a root, in slot order, and lane L owns NC tracker slots.
 // A frame with ng, nt <= 64 runs it with one column per lane (NC = 1), a larger one with four (NC = 4): the work follows the
-// frame's own size, never the caps.  Per step a wave minimum and a ballot pick the column of least slack - the lowest tracker slot
-// at equal slack, the private column at a tie with it - so nothing depends on the order in which lanes retire.
+// frame's own size, never the caps.  The tie rule - the lowest tracker slot at equal slack, "stay unmatched" at a tie with it -
+// is the solver's.
 #include "common.h"
 #include "../../include/rtm3d_hip.h"
+#include "assign_wave.h"
 
 #define MOT_MAX 256                 // ground truths and tracker boxes per frame, at most
 #define MOT_EPS 2.220446049250313e-16
 #define MOT_NALPHA RTM3D_MOT_ALPHAS
 #define MOT_INF (__builtin_inf())
 
-// a wave's LDS instructions execute in order: between lanes of ONE wave this is only a compiler / LDS ordering fence
-#define MOT_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 // global memory handed between lanes of one wave from one frame to the next (mot_clear_kernel)
 #define MOT_GSYNC() do { __threadfence(); __builtin_amdgcn_wave_barrier(); } while (0)
 
-struct MotLds {
+struct MotLds {                     // the solver's four arrays (assign_wave.h: AssignWave) and rowaux
     double row_dual[MOT_MAX];       // [ground-truth slot] dual of the row
     int row_col[MOT_MAX];           // ground-truth slot -> tracker slot it holds, -1 none
     int col_row[MOT_MAX];           // tracker slot -> ground-truth slot that holds it, -1 none
     int pred[MOT_MAX];              // tracker slot -> the row its slack came from, this path
     int rowaux[MOT_MAX];            // per row: its gid (HOTA) or the tracker id of its previous match (CLEAR), -1 none
 };
-
-__device__ __forceinline__ double mot_wave_min(double x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x = fmin(x, __shfl_xor(x, m, 64));
-    return x;
-}
 
 __device__ __forceinline__ int mot_wave_sum(int x) {
 #pragma unroll
@@ -74,93 +66,43 @@ struct MotWClear {                  // w = 1000 * (prev[gid] == tid) + sim, 0 wh
     }
 };
 
-// ASSIGN of one frame by one wave: L.rowaux is set by the caller; on return (after a wave sync) L.row_col holds the match
+// ASSIGN of one frame by one wave with NC columns per lane: L.rowaux is set by the caller, tids are the tracker ids of the frame's
+// columns or NULL; on return (after a wave sync) L.row_col holds the match
 template <int NC, class WF>
-__device__ __forceinline__ void mot_solve(int ng, int nt, const WF& wf, MotLds& L, const int (&ct)[NC], int wl) {
+__device__ __forceinline__ void mot_assign_frame(int ng, int nt, const WF& wf, MotLds& L, const int (&ct)[NC], int wl) {
     for (int q = wl; q < MOT_MAX; q += 64) { L.row_dual[q] = 0.0; L.row_col[q] = -1; L.col_row[q] = -1; }
-    MOT_WSYNC();
+    AW_WSYNC();
     uint32_t live = 0u;                                       // this lane's columns that exist
 #pragma unroll
     for (int c = 0; c < NC; ++c) if (NC * wl + c < nt) live |= 1u << c;
+    const AssignWave st{L.row_dual, L.row_col, L.col_row, L.pred};
     double v[NC];                                             // column duals
 #pragma unroll
     for (int c = 0; c < NC; ++c) v[c] = 0.0;
     for (int cur = 0; cur < ng; ++cur) {                      // one augmentation per row, in slot order
-        double sp[NC];                                        // slacks: shortest path costs
-#pragma unroll
-        for (int c = 0; c < NC; ++c) sp[c] = MOT_INF;
-        uint32_t sc = 0u;                                     // this lane's scanned columns
-        double minval = 0.0, dbest = MOT_INF;                 // dbest / drow: least slack of a scanned row's private column
-        int drow = -1, sink = -2;                             // sink: -2 none yet, -1 the private column of drow, else a tracker slot
-        int i = cur;
+        AwPath p = aw_path(cur);
         for (int step = 0; step <= nt; ++step) {              // every step scans another matched row or ends: at most nt + 1
-            const double ui = L.row_dual[i];
-            const int aux = L.rowaux[i];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                if (((live & ~sc) >> c) & 1u) {
-                    const double a = wf(i, aux, NC * wl + c, ct[c]);
-                    if (a > 0.0) {
-                        const double r = ((minval - a) - ui) - v[c];
-                        if (r < sp[c]) { sp[c] = r; L.pred[NC * wl + c] = i; }
-                    }
-                }
-            }
-            const double dv = minval - ui;
-            if (dv < dbest) { dbest = dv; drow = i; }
-            double lv = MOT_INF;
-            int lc = 0;
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-                if (!((sc >> c) & 1u) && sp[c] < lv) { lv = sp[c]; lc = c; }
-            const double m = mot_wave_min(lv);
-            const unsigned long long win = __ballot(lv == m);
-            if (!(m < dbest) || win == 0ull) { sink = -1; minval = dbest; break; }
-            const int wlane = __ffsll(win) - 1;               // lowest lane, and in it the lowest c: the lowest tracker slot
-            const int j = __builtin_amdgcn_readfirstlane(NC * wlane + __shfl(lc, wlane, 64));
-            minval = m;
-            if (wl == wlane) sc |= 1u << lc;
-            const int o = __builtin_amdgcn_readfirstlane(L.col_row[j]);
-            if (o < 0) { sink = j; break; }
-            i = o;
+            const int i = p.i, aux = L.rowaux[i];
+            const auto gain = [&](int c, double& g) {
+                g = wf(i, aux, NC * wl + c, ct[c]);
+                return g > 0.0;
+            };
+            aw_step<NC>(st, p, v, wl, live, gain);
+            if (p.sink != -2) break;
         }
-        if (sink != -2 && drow >= 0) {
-            // duals: scanned columns and the rows that hold them move by what the path still had to go; the root by all of it
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                if ((sc >> c) & 1u) {
-                    const double d = minval - sp[c];
-                    v[c] = v[c] - d;
-                    const int o = L.col_row[NC * wl + c];
-                    if (o >= 0) L.row_dual[o] = L.row_dual[o] + d;
-                }
-            }
-            if (wl == 0) L.row_dual[cur] = L.row_dual[cur] + minval;
-            MOT_WSYNC();
-            // augment back along the predecessors (every lane walks the same path and writes the same values)
-            int j = sink, r = -1;
-            if (sink == -1) { r = drow; j = L.row_col[r]; L.row_col[r] = -1; }
-            for (int g = 0; g <= nt && r != cur && j >= 0; ++g) {
-                r = L.pred[j];
-                L.col_row[j] = r;
-                const int t = L.row_col[r];
-                L.row_col[r] = j;
-                j = t;
-            }
-            MOT_WSYNC();
-        }
+        aw_finish<NC>(st, p, v, cur, nt, wl);
     }
-    MOT_WSYNC();
+    AW_WSYNC();
 }
 
-// the frame's own size picks the form; tids: the tracker ids of the frame's columns, or NULL
+// the frame's own size picks the form
 template <class WF>
 __device__ __forceinline__ void mot_run(int ng, int nt, const WF& wf, MotLds& L, const int32_t* __restrict__ tids, int n_tid, int wl) {
     if (ng <= 64 && nt <= 64) {
         int ct[1];
         ct[0] = -1;
         if (tids && wl < nt) { const int t = tids[wl]; ct[0] = t >= 0 && t < n_tid ? t : -1; }
-        mot_solve<1>(ng, nt, wf, L, ct, wl);
+        mot_assign_frame<1>(ng, nt, wf, L, ct, wl);
     } else {
         int ct[4];
 #pragma unroll
@@ -168,7 +110,7 @@ __device__ __forceinline__ void mot_run(int ng, int nt, const WF& wf, MotLds& L,
             ct[c] = -1;
             if (tids && 4 * wl + c < nt) { const int t = tids[4 * wl + c]; ct[c] = t >= 0 && t < n_tid ? t : -1; }
         }
-        mot_solve<4>(ng, nt, wf, L, ct, wl);
+        mot_assign_frame<4>(ng, nt, wf, L, ct, wl);
     }
 }
 

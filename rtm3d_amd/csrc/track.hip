@@ -13,18 +13,15 @@
 // pair of the whole order, so the rounds end.  Candidates are kept as two LDS bit matrices (rows, columns); the fp64 affinities
 // stay in the workspace and are read for set bits only.
 // The OPTIMAL match (step 3b; track_step_kernel<1>, reached only through rtm3d_tracks_update_assign) replaces the rounds by
-// shortest augmenting paths (Hungarian method in the Jonker-Volgenant form) over the same candidates, cost = -(affinity - thresh).
-// "Stay unmatched" is a zero-cost column private to every row, kept as one scalar per path (the smallest slack of the scanned
-// rows' private columns) instead of in memory: such a column is reachable from its own row only, is free whenever that row is
-// scanned, and a free column's dual is 0.  ONE wave runs the paths, so a path step has no block barrier: lane L owns the record
-// slots 4L .. 4L + 3 with their duals and slacks in registers; row duals, predecessors and the two owner arrays are in LDS.  Per
-// step every lane relaxes its unscanned candidate columns against the newly scanned row, a wave minimum and a ballot pick the
-// column of least slack - the lowest record slot at equal slack, the private column at a tie with it - and nothing depends on
-// the order in which lanes retire.  The rows are the live slots with a candidate, in slot order: at most T augmentations of at
-// most topk + 1 path steps each, both loops counted.
+// shortest augmenting paths over the same candidates, gain = affinity - thresh: the one-wave solver of assign_wave.h, which states
+// the method, the tie rule (the lowest record slot at equal slack, "stay unmatched" at a tie with it) and why nothing depends on
+// the order in which lanes retire.  Lane L owns the record slots 4L .. 4L + 3.  What is the tracker's own: the rows are the live
+// slots with a candidate, in slot order (at most T augmentations of at most topk + 1 path steps each), and a row's gains come from
+// the LDS candidate bits and the workspace, the next root's row fetched behind the current path.
 #include "common.h"
 #include "../../include/rtm3d_hip.h"
 #include "box_geom.h"
+#include "assign_wave.h"
 
 #define TRK_MAX 256                 // track slots per stream and record slots per image, at most
 #define TRK_HDR RTM3D_TRACK_HEADER_DOUBLES
@@ -58,15 +55,6 @@ __device__ __forceinline__ TrkPose trk_predict_pose(const double* __restrict__ s
     }
     p.ry = trk_wrap(p.ry);
     return p;
-}
-
-// a wave's LDS instructions execute in order: between lanes of ONE wave this is only a compiler / LDS ordering fence
-#define TRK_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-
-__device__ __forceinline__ double trk_wave_min(double x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x = fmin(x, __shfl_xor(x, m, 64));
-    return x;
 }
 
 __device__ __forceinline__ bool trk_is_detection(const float* __restrict__ r, double min_score) {
@@ -219,7 +207,7 @@ __global__ __launch_bounds__(BO_LANES) void track_step_kernel(int topk, int T, c
             if (!__syncthreads_or(rb >= 0 ? 1 : 0)) break;
         }
     } else {
-        // shortest augmenting paths, one wave; lane wl owns the record slots 4 * wl + c, c = 0 .. 3
+        // shortest augmenting paths by wave 0 (assign_wave.h); lane wl owns the record slots 4 * wl + c, c = 0 .. 3
         bool has = false;
 #pragma unroll
         for (int wd = 0; wd < TRK_MAX / 32; ++wd) has = has || rowmask[tid][wd] != 0u;
@@ -245,6 +233,7 @@ __global__ __launch_bounds__(BO_LANES) void track_step_kernel(int topk, int T, c
 #pragma unroll
                 for (int c = 0; c < 4; ++c) a[c] = (nib >> c) & 1u ? Ai[c] : 0.0;
             };
+            const AssignWave st{row_dual, trk_det, det_owner, pred};
             double v[4] = {0.0, 0.0, 0.0, 0.0};                   // column duals
             double an[4] = {0.0, 0.0, 0.0, 0.0};
             uint32_t nibn = 0u;
@@ -256,64 +245,15 @@ __global__ __launch_bounds__(BO_LANES) void track_step_kernel(int topk, int T, c
                 uint32_t nib = nibn;
                 next = pop_row();
                 if (next >= 0) load_row(next, an, nibn);          // the next root's row is fetched behind this path
-                double sp[4] = {__builtin_inf(), __builtin_inf(), __builtin_inf(), __builtin_inf()};   // slacks: shortest path costs
-                uint32_t sc = 0u;                                 // this lane's scanned columns
-                double minval = 0.0, dbest = __builtin_inf();     // dbest / drow: least slack of a scanned row's private column
-                int drow = -1, sink = -2;                         // sink: -2 none yet, -1 the private column of drow, else a record slot
-                int i = cur;
+                // a set bit of nib is a pair whose affinity is above thresh (track_affinity_kernel): a candidate, its gain > 0
+                const auto gain = [&](int c, double& g) { g = a[c] - P.thresh; return true; };
+                AwPath p = aw_path(cur);
                 for (int step = 0; step <= topk; ++step) {        // every step scans another matched row or ends: at most topk + 1
-                    const double ui = row_dual[i];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        if (((nib & ~sc) >> c) & 1u) {
-                            const double r = ((minval - (a[c] - P.thresh)) - ui) - v[c];
-                            if (r < sp[c]) { sp[c] = r; pred[4 * wl + c] = i; }
-                        }
-                    }
-                    const double dv = minval - ui;
-                    if (dv < dbest) { dbest = dv; drow = i; }
-                    double lv = __builtin_inf();
-                    int lc = 0;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (!((sc >> c) & 1u) && sp[c] < lv) { lv = sp[c]; lc = c; }
-                    const double m = trk_wave_min(lv);
-                    const unsigned long long win = __ballot(lv == m);
-                    if (!(m < dbest) || win == 0ull) { sink = -1; minval = dbest; break; }
-                    const int wlane = __ffsll(win) - 1;           // lowest lane, and in it the lowest c: the lowest record slot
-                    const int j = __builtin_amdgcn_readfirstlane(4 * wlane + __shfl(lc, wlane, 64));
-                    minval = m;
-                    if (wl == wlane) sc |= 1u << lc;
-                    const int o = __builtin_amdgcn_readfirstlane(det_owner[j]);
-                    if (o < 0) { sink = j; break; }
-                    i = o;
-                    load_row(i, a, nib);
+                    aw_step<4>(st, p, v, wl, nib, gain);
+                    if (p.sink != -2) break;
+                    load_row(p.i, a, nib);
                 }
-                if (sink != -2 && drow >= 0) {
-                    // duals: scanned columns and the rows that hold them move by what the path still had to go; the root by all of it
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        if ((sc >> c) & 1u) {
-                            const double d = minval - sp[c];
-                            v[c] = v[c] - d;
-                            const int o = det_owner[4 * wl + c];
-                            if (o >= 0) row_dual[o] = row_dual[o] + d;
-                        }
-                    }
-                    if (wl == 0) row_dual[cur] = row_dual[cur] + minval;
-                    TRK_WSYNC();
-                    // augment back along the predecessors (every lane walks the same path and writes the same values)
-                    int j = sink, r = -1;
-                    if (sink == -1) { r = drow; j = trk_det[r]; trk_det[r] = -1; }
-                    for (int g = 0; g <= topk && r != cur && j >= 0; ++g) {
-                        r = pred[j];
-                        det_owner[j] = r;
-                        const int t = trk_det[r];
-                        trk_det[r] = j;
-                        j = t;
-                    }
-                    TRK_WSYNC();
-                }
+                aw_finish<4>(st, p, v, cur, topk, wl);
             }
         }
         __syncthreads();

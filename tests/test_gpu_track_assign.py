@@ -2,8 +2,8 @@
 yardstick tests/track_assign_ref.py, frame by frame, by the comparison rule of tests/test_gpu_track.py: ids, classes, ages, hits,
 misses, scores, record slots and the three counters EQUAL, filtered states and covariances within 1e-9.  Every sequence's margin
 (threshold, heading and uniqueness of the optimum) is asserted first: >= 1e-6 in every frame, on the yardstick's own numbers.
-Then the chain the greedy rule gets wrong, exact ties, a frame without candidates, assign = 0 through the new entry point, and
-Engine.detect with an optimal tracker.
+Then the chain the greedy rule gets wrong, exact ties, a frame without candidates, assign = 0 through the new entry point, the
+evaluator's entry point on the tracker's own gains, and Engine.detect with an optimal tracker.
 
 Measured on an MI355X (the figure each case prints; copied to profiles/track.txt): 0 in dense_3d, overflow_bev,
 three_streams_classes and chain_dist, 1.78e-15 in crossing_dist_ego."""
@@ -16,7 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import rtm3d_amd                                     # noqa: E402
-from rtm3d_amd import _lib, weights, engine, track   # noqa: E402
+from rtm3d_amd import _lib, weights, engine, track, mot_eval   # noqa: E402
 from tests import track_ref as ref                   # noqa: E402
 from tests import track_cases as tc                  # noqa: E402
 from tests import track_assign_ref as ar             # noqa: E402
@@ -141,6 +141,38 @@ def test_assign_0_through_the_new_entry_is_tracks_update(dev):
         assert ids[0].cpu().numpy().tobytes() == ids[1].cpu().numpy().tobytes()
         assert states[0].cpu().numpy().tobytes() == states[1].cpu().numpy().tobytes()
     assert int(states[0][0, 0].item()) >= 4 and bool((ids[0] != 0).any())
+
+
+def test_the_evaluator_entry_gives_the_tracker_match_on_the_same_gains(dev):
+    """One solver text (csrc/assign_wave.h) behind both entry points: the match rtm3d_tracks_update_assign(assign = 1) stores equals
+    rtm3d_mot_assign on w = affinity - thresh read back from the tracker's own workspace, exact ties included; integers, exactly.
+    Both cases have T, topk <= 64, so the evaluator runs its one-column-per-lane form against the tracker's four-column one; the
+    evaluator's own four-column form is compared with scipy in tests/test_gpu_mot_eval.py, not with the tracker here."""
+    lib = _lib.load()
+    for name in ('exact_ties', 'chain_dist'):
+        case = ar.fixed(name)[0]
+        B, topk, T = case['frames'][0].shape[0], case['topk'], case['T']
+        p = track.TrackParams(**case['params']).to_c()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        state = torch.zeros(B, ref.HEADER + ref.SLOT * T, dtype=torch.float64, device=dev)
+        ids = torch.zeros(B, topk, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(lib.rtm3d_tracks_workspace_bytes(B, topk, T)), dtype=torch.uint8, device=dev)
+        assert len(case['frames']) == 2                                       # the births, then the frame that is matched
+        for rec in case['frames']:
+            before = state.cpu().numpy()[:, ref.HEADER:].reshape(B, T, ref.SLOT).copy()
+            d_rec = torch.from_numpy(rec).to(dev)
+            _lib.check(lib.rtm3d_tracks_update_assign(stream, B, topk, T, d_rec.data_ptr(), case['dt'], None, ctypes.byref(p), 1,
+                                                      state.data_ptr(), ids.data_ptr(), ws.data_ptr()), 'tracks_update_assign')
+            torch.cuda.synchronize()
+        aff = ws.view(torch.float64).reshape(B, T, topk)
+        w = torch.where(aff > -np.inf, aff - case['params']['thresh'], torch.zeros_like(aff))
+        match = mot_eval.assign(w, np.full(B, T), np.full(B, topk)).cpu().numpy()
+        after = state.cpu().numpy()[:, ref.HEADER:].reshape(B, T, ref.SLOT)
+        live = before[..., 0] != 0
+        assert live.sum() == {'exact_ties': 2, 'chain_dist': 2 * ar.CHAIN}[name] and int((w > 0).sum()) > live.sum()
+        assert np.array_equal(after[..., 0][live], before[..., 0][live])      # still the same tracks: field 6 is this frame's match
+        assert np.array_equal(match[live], after[..., 6][live].astype(np.int64)), name
+        assert (match[live] >= 0).all() and (match[~live] == -1).all()
 
 
 def test_engine_detect_with_an_optimal_tracker(dev, tmp_path, monkeypatch):
