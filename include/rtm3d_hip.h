@@ -1257,6 +1257,95 @@ int rtm3d_mot_clear(void* stream, int S, int F, int cap_g, int cap_t, int n_gid,
                     double thr, int32_t* d_match, int32_t* d_counts, double* d_simsum, int32_t* d_idcount, int32_t* d_matched,
                     int32_t* d_frag, void* d_ws);
 
+/* ------------------------------------------------------------------ rig fusion (csrc/rig.hip)
+ * The C cameras of one vehicle as ONE scene: every camera's kept 3D boxes taken to a common rig frame by the camera's
+ * extrinsics, the boxes that several cameras report for one object merged into one, and a map from every camera's record slot
+ * to the fused slot, so that a track id given to a fused box finds its way back to each camera's records.  Added in ABI 9
+ * without changing any existing declaration; nothing calls these unless the caller does (no plan, engine file or record
+ * changes).  The records are READ ONLY.  The rule below is complete: tests/rig_ref.py is written from it.  Everything is fp64,
+ * in the operation order written here, compiled without contraction; "a * b + c" means the rounded product, then the rounded
+ * sum, and sums associate left to right unless bracketed.  wrap, PI, TWO_PI are those of "tracking"; HALF_PI =
+ * 1.5707963267948966.
+ *
+ * SIZES: R rigs (or R time steps of one rig) of C cameras each.  d_rec [R * C][topk][32] fp32 records, the image of camera c
+ * of rig r at index r * C + c.  1 <= C <= 16, 1 <= topk <= 256, C * topk <= 2048, output capacity 1 <= cap <= 256, R >= 1;
+ * anything else is refused before a launch.
+ * EXTRINSICS: d_ext [R * C][12] fp64 device memory; e = d_ext + 12 * (r * C + c) is the row-major 3 x 4 [R | t] that takes a
+ * point of camera c's coordinates to the rig frame - the convention of the tracker's d_ego.
+ * RIG FRAME: camera-like, x right, y down, z forward (the frame of a camera whose extrinsic is the identity).  The fused records
+ * are therefore records like any camera's: rtm3d_box_overlaps, rtm3d_records_nms3d, rtm3d_tracks_update / _assign and the
+ * bird's-eye panels apply to them unchanged.  A caller whose vehicle frame is x forward / z up folds that fixed change of axes
+ * into the extrinsics.
+ *
+ * One call = one frame of every rig, in these steps.
+ * 1 CANDIDATES of rig r: the record slots (camera c, slot k) with flag [31] == 2 and (double)[1] >= min_score (a NaN score is
+ *   therefore no candidate); class [0], score [1].  The box (h, w, l) = (double)[24:27] is kept as it is.  With (x, y, z, ry) =
+ *   (double)[27:31] and the camera's e:
+ *     X' = ((e[0] * x + e[1] * y) + e[2] * z) + e[3]      (Y', Z' alike with e[4..7], e[8..11])
+ *     ry' = wrap(atan2(-(e[8] * c - e[10] * s), e[0] * c - e[2] * s)),  c = cos(ry), s = sin(ry)
+ *   - the heading vector (c, 0, -s) turned with R, as the tracker turns it with the ego motion.  With a pitched or rolled camera
+ *   this is an approximation: the box's vertical axis is taken as the rig's (h stays the extent along y), only the heading's
+ *   projection into the x-z plane is kept.
+ * 2 ORDER the candidates of a rig by score descending - the fp32 compare of [1], so -0 and +0 tie - then by lower camera index,
+ *   then by lower slot.
+ * 3 CLUSTERS.  linked(i, j) of two candidates holds iff  (cross_only == 0 or camera of i != camera of j)  and  (class_aware == 0
+ *   or class of i == class of j, compared as the fp32 values)  and  affinity(box a = the box of j, box b = the box of i) > thresh
+ *   (strict; never true for NaN).  The affinity is exactly step 2 of "tracking" on the boxes of step 1 here: metric 0 = BEV IoU,
+ *   1 = 3D IoU by the arithmetic of rtm3d_box_overlaps, criterion 0, with the reach shortcut - (ex, ey, ez) = centre a - centre
+ *   b, reach = 0.5 * sqrt(w_a * w_a + l_a * l_a) + 0.5 * sqrt(w_b * w_b + l_b * l_b), a pair with ex * ex + ez * ez > reach * reach
+ *   has affinity 0 - and metric 2 = -sqrt((ex * ex + ey * ey) + ez * ez).  A box that is not finite (or not positive in h, w, l)
+ *   has IoU 0 with everything and a NaN or infinite distance: it links to nothing unless thresh admits 0.
+ *   Walk the candidates in the order of step 2.  Candidate i joins the EARLIEST candidate j before it in that order that is a
+ *   representative and has linked(i, j); if there is none, i becomes a representative itself.  Members never attract other
+ *   candidates: with A-B linked, B-C linked and A-C not linked (A, B, C in this order), B joins A and C is its own
+ *   representative.  With cross_only, two boxes of ONE camera can still land in one cluster, each through its link to a
+ *   representative of another camera; cross_only only keeps two boxes of one camera from linking to each other.
+ * 4 MERGE of a cluster, members m = the representative first, then the other members in the order of step 2:
+ *   RTM3D_RIG_MERGE_BEST: the representative's box of step 1.
+ *   RTM3D_RIG_MERGE_MEAN: w_m = (double)score of m;  W = sum of w_m;  h, w, l, X, Y, Z each = (sum of w_m * v_m) / W (every sum
+ *     starts with the representative's term);  heading: d_m = wrap(ry_m - ry_rep); if d_m > HALF_PI: d_m = d_m - PI, otherwise if
+ *     d_m < -HALF_PI: d_m = d_m + PI (a box seen from the other end is the same box);  ry = wrap(ry_rep + (sum of w_m * d_m) / W).
+ *     A cluster of one goes through the same arithmetic ((w * v) / w, within a rounding of v), and a cluster whose scores sum to 0
+ *     has a box that is not a number: set min_score above 0 where scores of 0 occur.
+ *   Class and score of a cluster are the representative's, copied exactly.
+ * 5 OUTPUTS, all rewritten in full by every call (no memset is needed):
+ *   d_out [R][cap][32] fp32 records: slot s = the s-th representative in the order of step 2, so the output is score-descending
+ *     (what the tracker's births rely on).  [0] class  [1] score  [2:24] zero  [24:31] the fused box h w l X Y Z ry rounded to
+ *     fp32  [31] = 2.  Slots past the last cluster: 32 zeros.
+ *   d_box [R][cap][7] fp64, may be NULL: the fused box before that rounding, zeros in empty slots.
+ *   d_info [R][cap][4] int32: the representative's camera, its record slot, the member count (representative included), the bit
+ *     mask of the cameras in the cluster (bit c = camera c).  All zero in empty slots.
+ *   d_map [R * C][topk] int32, one per record slot: -1 not a candidate; s >= 0 the output slot of its cluster; -2 its cluster did
+ *     not fit in cap.
+ *   d_n [R][2] int32: clusters written, clusters dropped.  The dropped ones are the last in the order: the lowest scores.
+ *
+ * rtm3d_rig_default_params: metric 0, thresh 0.1, class_aware 1, cross_only 1, merge RTM3D_RIG_MERGE_MEAN, min_score 0.  There is
+ * no multi-camera recording behind these values: they are a choice (a loose BEV IoU, since two cameras' depth errors differ),
+ * not a tuning.
+ * rtm3d_rig_fuse: three launches - one workgroup per rig for steps 1 and 2 (the keys sorted in LDS), one lane per ordered pair
+ * for the linked bits, one workgroup per rig for the scan of step 3 and steps 4, 5 - through d_ws, rtm3d_rig_workspace_bytes(R,
+ * C, topk) bytes, whatever it holds before the call (0 for sizes the call refuses).  Stream-ordered: no host synchronisation, no
+ * memset / memcpy node, no allocation.  No result depends on the order in which lanes retire: two calls on the same inputs are
+ * bit-identical, and a call with R rigs equals R calls with one.  Refused before anything is launched, non-zero with the reason in
+ * rtm3d_last_error(): sizes outside the ranges above, a NULL d_rec / d_ext / params / d_out / d_info / d_map / d_n / d_ws, metric
+ * outside 0..2, merge outside 0..1, NaN thresh or min_score.
+ * rtm3d_rig_scatter_ids: d_ids_cam [R * C][topk] = d_map >= 0 ? d_ids_rig [r][d_map] : 0 with d_ids_rig [R][cap] - the ids the
+ * tracker returns for the fused records (B = R, topk = cap) taken back to each camera's slots, the array
+ * rtm3d_records_draw_tracks and the users of the per-camera records expect.  One launch; refused alike: sizes, a NULL pointer. */
+#define RTM3D_RIG_MERGE_BEST 0
+#define RTM3D_RIG_MERGE_MEAN 1
+typedef struct rtm3d_rig_params {
+    int metric, class_aware, cross_only, merge;
+    double thresh, min_score;
+} rtm3d_rig_params;
+int rtm3d_rig_default_params(rtm3d_rig_params* p);
+size_t rtm3d_rig_workspace_bytes(int R, int C, int topk);
+int rtm3d_rig_fuse(void* stream, int R, int C, int topk, int cap, const float* d_rec, const double* d_ext,
+                   const rtm3d_rig_params* params, float* d_out, double* d_box, int32_t* d_info, int32_t* d_map, int32_t* d_n,
+                   void* d_ws);
+int rtm3d_rig_scatter_ids(void* stream, int R, int C, int topk, int cap, const int32_t* d_map, const int32_t* d_ids_rig,
+                          int32_t* d_ids_cam);
+
 #ifdef __cplusplus
 }
 #endif

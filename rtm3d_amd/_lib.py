@@ -98,6 +98,12 @@ class TrackParamsC(ctypes.Structure):
                 ('r_pos', c_double), ('r_ry', c_double), ('r_dim', c_double)]
 
 
+class RigParamsC(ctypes.Structure):
+    """Mirror of struct rtm3d_rig_params (rtm3d_amd/rig.py)."""
+    _fields_ = [('metric', c_int), ('class_aware', c_int), ('cross_only', c_int), ('merge', c_int),
+                ('thresh', c_double), ('min_score', c_double)]
+
+
 class PreprocessPlan(ctypes.Structure):
     """Mirror of struct rtm3d_preprocess_plan (one per sub-batch of 64 images)."""
     _fields_ = [('first', c_int), ('count', c_int), ('col_bytes', c_int), ('stage_bytes', c_int), ('band_rows', c_int), ('bands', c_int),
@@ -264,6 +270,12 @@ SIGNATURES = {
     'rtm3d_mot_assign': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rtm3d_mot_hota': (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 18),
     'rtm3d_mot_clear': (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 6 + [c_double] + [c_void_p] * 7),
+    # rig fusion: the cameras of one vehicle as one scene (rtm3d_amd/rig.py)
+    'rtm3d_rig_default_params': (c_int, [ctypes.POINTER(RigParamsC)]),
+    'rtm3d_rig_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'rtm3d_rig_fuse': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(RigParamsC), c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rtm3d_rig_scatter_ids': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

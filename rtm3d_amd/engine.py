@@ -483,6 +483,34 @@ class Engine(object):
             res = res + (ids,)
         return res if len(res) > 1 else res[0]
 
+    def detect_frames_rig(self, images, K_camera, rig, kitti=False, nms3d=None, tracker=None, out=None):
+        """detect_frames on the R * C frames of a rig.Rig (frame r * C + c = camera c of rig r; the engine's batch is R * C), then
+        the fusion of the cameras' records into the rig frame (rig.fuse, three more launches).  nms3d: as for detect_frames, per
+        camera, before the fusion.  tracker: None or a track.Tracker of R streams: ONE update on the fused records - an object
+        keeps its id from one camera's view into the next - then the ids taken back to every camera's record slots
+        (rig.camera_ids).  Returns (records[, rows], fused) and, with a tracker, (..., ids_rig (R, cap), ids_cam (R * C, topk)):
+        records / rows per camera as detect_frames returns them, fused a rig.Fused.  Nothing synchronises; wrong sizes raise
+        before anything is launched."""
+        B, topk = self.info['B'], self.info['topk']
+        if rig.R * rig.C != B:
+            raise ValueError('Engine.detect_frames_rig: the rig holds %d x %d cameras, this engine runs batches of %d' % (rig.R, rig.C, B))
+        if rig.device != self.device:
+            raise ValueError('Engine.detect_frames_rig: the rig lives on %s, the engine on %s' % (rig.device, self.device))
+        cap = rig.check_sizes(topk)
+        if tracker is not None and tracker.B != rig.R:
+            raise ValueError('Engine.detect_frames_rig: the tracker follows %d streams, the rig has %d (one stream per rig)' % (tracker.B, rig.R))
+        res = self.detect_frames(images, K_camera, kitti=kitti, out=out, nms3d=nms3d)
+        rec = res[0] if kitti else res
+        import torch
+        with torch.cuda.device(self.device):
+            fused = rig.fuse(rec)
+            assert fused.records.shape[1] == cap
+            res = (res if kitti else (rec,)) + (fused,)
+            if tracker is not None:
+                ids_rig = tracker.update(fused.records, dt=tracker.dt, ego=tracker.ego)
+                res = res + (ids_rig, rig.camera_ids(ids_rig, fused))
+        return res
+
     def detect_frames_src(self, sources, K_camera, order='rgb', packed=None, kitti=False, out=None, draw=None, tracker=None, nms3d=None):
         """detect_frames fed by decoder / camera surfaces (rtm3d_engine_detect_frames_src): sources = list of B
         pixfmt.FrameSource (NV12, P010, YUYV, I420, pitched RGB / BGRA ... of any sizes that fit the canvas after Resize).  One
