@@ -4,7 +4,7 @@
 //
 // Three launches:
 //   A  (grid over all B*K*H*W elements) sigmoid of the heat-map logits -> workspace (L2 resident)
-//   B  (same grid) 3x3 max with -inf border, keep s == max (all members of a plateau survive, like
+//   B  (same grid) 3x3 NaN-propagating max with -inf border, keep s == max (all members of a plateau survive, like
 //      the reference), append survivors with s > thresh as unique 64-bit keys
 //      (score bits << 32 | ~flat_index) to the image's candidate list (global atomic counter)
 //   C+D (one 1024-thread workgroup per image) exact radix select (8 passes x 8 bits) of the top-k-th
@@ -15,7 +15,16 @@
 // Bit-exactness: the fp32 sigmoid reproduces what PyTorch-CPU computes: the vectorised path is
 // Sleef's expf_u10 polynomial (fma form) followed by an IEEE divide; elements that fall in the
 // scalar tail of ATen's vectorised loop (last n % 32 elements of a < 32768-element tensor on an
-// AVX-512 host) use a correctly rounded expf instead.  Verified against torch.sigmoid on 16M values.
+// AVX-512 host) use the host libm's expf instead (expf_libm below: not always the correctly rounded
+// value).  Every regime of this file is pinned per case in tests/decode2d_cases.py.
+// At or above 32768 elements every element is called "vector".  That is what torch does when the size is a multiple of 32
+// (every stride-4 map of a 32-aligned input).  Otherwise torch.sigmoid splits the tensor among its threads and each part ends
+// in a scalar tail of its own, whose position changes with the thread count: the reference is not defined bit for bit there,
+// and all this kernel promises is that every score is one of the two forms of its logit (same peaks, classes and counts as
+// long as the scores are more than an ulp apart).
+//
+// NaN: the 3x3 maximum and the vertex min / max propagate NaN like max_pool2d and min / max(dim) of the reference: a NaN heat
+// cell is no peak and neither is any cell of its 3x3 neighbourhood; a NaN vertex coordinate gives a NaN box entry.
 #include "common.h"
 #include "../../include/rtm3d_hip.h"
 
@@ -46,13 +55,53 @@ __device__ __forceinline__ float expf_sleef_u10(float d) {
     return u;
 }
 
+// expf as the host's libm computes it (glibc >= 2.27, the algorithm of ARM's optimized routines): exp(x) = 2^(k/32) * p(r) in
+// double, k = round(x * 32 / ln 2), 2^(i/32) from a table, p of degree 3, ONE rounding to float at the end.  Its error bound is
+// 0.502 ulp: near a rounding midpoint it is not the correctly rounded value (x = -1.2257744 gives 0x1.2c9336p-2, the exact
+// value 0x1.2c9334ffde9p-2 rounds to 0x1.2c9334p-2; 67 of a million arguments in [-20, 20]), and the scalar tail of ATen's
+// sigmoid is this expf.  Checked on the host against libm's expf on every eighth float of [-20, 20] (275M values): identical.
+__constant__ unsigned long long EXP2F_TAB[32] = {
+    0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull,
+    0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull,
+    0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull,
+    0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull, 0x3feea47eb03a5585ull,
+    0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
+    0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull,
+    0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull,
+    0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull,
+};
+
+__device__ __forceinline__ float expf_libm(float x) {
+    if (!(fabsf(x) < 88.0f)) {
+        if (x != x) return x;
+        if (x > 0x1.62e42ep6f) return INFINITY;
+        if (x < -0x1.9fe368p6f) return 0.0f;
+    }
+    const double N = 32.0, InvLn2N = 0x1.71547652b82fep+0 * N, SHIFT = 0x1.8p52;
+    const double C0 = 0x1.c6af84b912394p-5 / N / N / N, C1 = 0x1.ebfce50fac4f3p-3 / N / N, C2 = 0x1.62e42ff0c52d6p-1 / N;
+    const double z = InvLn2N * (double)x;
+    double kd = z + SHIFT;
+    const unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
+    kd -= SHIFT;
+    const double r = z - kd;
+    const double s = __longlong_as_double((long long)(EXP2F_TAB[ki & 31ull] + (ki << 47)));
+    const double p = C0 * r + C1, r2 = r * r;
+    double y = C2 * r + 1.0;
+    y = p * r2 + y;
+    return (float)(y * s);
+}
+
 // vector == true : ATen Vectorized<float> path;  false : scalar tail (1/(1+std::exp(-x)))
 __device__ __forceinline__ float sigmoid_aten(float x, bool vector) {
     float e;
     if (vector) e = expf_sleef_u10(0.0f - x);
-    else e = (float)exp((double)(-x));
+    else e = expf_libm(0.0f - x);
     return __fdiv_rn(1.0f, 1.0f + e);
 }
+
+// NaN-propagating max / min (fmaxf / fminf drop a NaN operand); identical to them on other operands
+__device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }
+__device__ __forceinline__ float min_nan(float m, float v) { return (v < m || v != v) ? v : m; }
 
 #define D2_THREADS 1024
 #define D2_MAXK 256
@@ -85,7 +134,7 @@ __global__ __launch_bounds__(256) void d2_nms_kernel(const float* __restrict__ s
         for (int dx = -1; dx <= 1; ++dx) {
             const int xx = x + dx;
             if (xx < 0 || xx >= W) continue;
-            mx = fmaxf(mx, pl[yy * W + xx]);
+            mx = max_nan(mx, pl[yy * W + xx]);
         }
     }
     const bool keep = mx == s && s > thresh;
@@ -206,8 +255,8 @@ __global__ __launch_bounds__(D2_THREADS) void decode2d_kernel(
             const float vy = down * (of[(size_t)(2 * k + 1) * HW] + yf);
             out_verts[row * 16 + 2 * k] = vx;
             out_verts[row * 16 + 2 * k + 1] = vy;
-            minx = fminf(minx, vx); miny = fminf(miny, vy);
-            maxx = fmaxf(maxx, vx); maxy = fmaxf(maxy, vy);
+            minx = min_nan(minx, vx); miny = min_nan(miny, vy);
+            maxx = max_nan(maxx, vx); maxy = max_nan(maxy, vy);
         }
         out_bbox[row * 4 + 0] = minx; out_bbox[row * 4 + 1] = miny;
         out_bbox[row * 4 + 2] = maxx; out_bbox[row * 4 + 3] = maxy;
@@ -272,8 +321,8 @@ __global__ __launch_bounds__(256) void decode2d_finish_kernel(int B, int topk, c
         const float vy = down * (of[2 * k + 1] + yf);
         verts[(size_t)i * 16 + 2 * k] = vx;
         verts[(size_t)i * 16 + 2 * k + 1] = vy;
-        minx = fminf(minx, vx); miny = fminf(miny, vy);
-        maxx = fmaxf(maxx, vx); maxy = fmaxf(maxy, vy);
+        minx = min_nan(minx, vx); miny = min_nan(miny, vy);
+        maxx = max_nan(maxx, vx); maxy = max_nan(maxy, vy);
     }
     bbox[(size_t)i * 4 + 0] = minx; bbox[(size_t)i * 4 + 1] = miny;
     bbox[(size_t)i * 4 + 2] = maxx; bbox[(size_t)i * 4 + 3] = maxy;

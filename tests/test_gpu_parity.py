@@ -933,7 +933,8 @@ def test_nonfinite_logits_through_decode2d_decode3d_pack(dev):
     assert n == len(d_ref[0][0]) and n in (n0, n0 + 1, n0 - 1)
     # detections: same classes and cells; finite fields bit-exact, non-finite ones non-finite in the same places
     assert torch.equal(det.cls[:n].cpu(), d_ref[0][0])
-    for got, ref in ((det.score[:n], d_ref[1][0]), (det.mproj[:n], d_ref[2][0]), (det.verts[:n], d_ref[3][0])):
+    for got, ref in ((det.score[:n], d_ref[1][0]), (det.mproj[:n], d_ref[2][0]), (det.verts[:n], d_ref[3][0]),
+                     (det.bbox[:n], d_ref[4][0])):
         got, ref = got.cpu().numpy(), ref.numpy()
         np.testing.assert_array_equal(np.isfinite(got), np.isfinite(ref))
         np.testing.assert_array_equal(got[np.isfinite(ref)], ref[np.isfinite(ref)])
