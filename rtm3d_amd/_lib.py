@@ -308,3 +308,20 @@ def check(rc, what=''):
     if rc != 0:
         msg = load().rtm3d_last_error()
         raise RuntimeError('rtm3d_hip %s failed: %s' % (what, msg.decode() if msg else 'unknown error'))
+
+
+# what the camera-frame wrappers (engine, draw, lens, pixfmt, preprocess) hand to the library
+def stream_ptr(device):
+    """The current stream of ``device`` as the `void* stream` of an entry point."""
+    import torch
+    return c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr_array(tensors):
+    """The device addresses of ``tensors`` as a host array of pointers."""
+    return (c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def hw_array(tensors):
+    """(h, w) of every (h, w, ...) tensor as the host array h0, w0, h1, w1 ..."""
+    return (c_int * (2 * len(tensors)))(*[int(v) for t in tensors for v in t.shape[:2]])

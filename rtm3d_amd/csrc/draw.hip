@@ -298,15 +298,7 @@ extern "C" int rtm3d_records_draw(void* stream, int B, int topk, const float* d_
     for (int b0 = 0; b0 < B; b0 += DRAW_MAX_BATCH) {
         const int nb = B - b0 < DRAW_MAX_BATCH ? B - b0 : DRAW_MAX_BATCH;
         DrawBatch fb;
-        int tiles = 0;
-        for (int i = 0; i < nb; ++i) {
-            fb.img[i] = h_imgs[b0 + i]; fb.h[i] = h_hw[2 * (b0 + i)]; fb.w[i] = h_hw[2 * (b0 + i) + 1];
-            fb.tile0[i] = tiles;
-            if (frames) tiles += ((fb.w[i] + DRAW_TW - 1) / DRAW_TW) * ((fb.h[i] + DRAW_TH - 1) / DRAW_TH);
-        }
-        for (int i = nb; i < DRAW_MAX_BATCH; ++i) { fb.img[i] = nullptr; fb.h[i] = 0; fb.w[i] = 0; fb.tile0[i] = tiles; }
-        fb.tile0[nb] = tiles;
-        fb.tile0[DRAW_MAX_BATCH] = tiles;
+        const int tiles = draw_fill_batch(fb, h_imgs, h_hw, b0, nb, frames);
         const int grid = tiles + nb * bev_tiles;                   // <= 64 * 65536 * 2
         hipLaunchKernelGGL(records_draw_kernel, dim3((unsigned)grid), dim3(DRAW_THREADS), 0, (hipStream_t)stream, fb, nb, topk,
                            d_rec + (size_t)b0 * topk * 32, d_K_camera ? d_K_camera + (size_t)b0 * 9 : nullptr, P,

@@ -1,6 +1,6 @@
 // Device helpers shared by the two drawing kernels (draw.hip: records_draw_kernel; draw_tracks.hip: draw_tracks_kernel): the
-// tile geometry, the batch descriptor, the coordinate rule and the exact integer coverage tests of include/rtm3d_hip.h,
-// "drawing".  Integer ranges: draw.hip.
+// tile geometry, the batch descriptor with the host function that fills it (draw_fill_batch), the coordinate rule and the exact
+// integer coverage tests of include/rtm3d_hip.h, "drawing".  Integer ranges: draw.hip.
 #pragma once
 #include "common.h"
 #include "box_project.h"
@@ -21,6 +21,21 @@ struct DrawBatch {
     int h[DRAW_MAX_BATCH], w[DRAW_MAX_BATCH];
     int tile0[DRAW_MAX_BATCH + 1];     // first workgroup of frame i; [nb] = first workgroup of the panels
 };
+
+// host: the descriptor of the nb frames from b0 on (unused entries empty); `frames` = a frame layer is set, so the frames get
+// workgroups.  Returns the workgroups of the frames = the first workgroup of the panels.
+static inline int draw_fill_batch(DrawBatch& fb, uint8_t* const* h_imgs, const int* h_hw, int b0, int nb, bool frames) {
+    int tiles = 0;
+    for (int i = 0; i < nb; ++i) {
+        fb.img[i] = h_imgs[b0 + i]; fb.h[i] = h_hw[2 * (b0 + i)]; fb.w[i] = h_hw[2 * (b0 + i) + 1];
+        fb.tile0[i] = tiles;
+        if (frames) tiles += ((fb.w[i] + DRAW_TW - 1) / DRAW_TW) * ((fb.h[i] + DRAW_TH - 1) / DRAW_TH);
+    }
+    for (int i = nb; i < DRAW_MAX_BATCH; ++i) { fb.img[i] = nullptr; fb.h[i] = 0; fb.w[i] = 0; fb.tile0[i] = tiles; }
+    fb.tile0[nb] = tiles;
+    fb.tile0[DRAW_MAX_BATCH] = tiles;
+    return tiles;
+}
 
 // truncation toward zero of a coordinate whose integer lies in [-8192, 8192]; false for anything else (NaN and infinities too)
 __device__ __forceinline__ bool draw_coord(double v, int& o) {

@@ -415,15 +415,7 @@ extern "C" int rtm3d_records_draw_tracks(void* stream, int B, int topk, const fl
     for (int b0 = 0; b0 < B; b0 += DRAW_MAX_BATCH) {
         const int nb = B - b0 < DRAW_MAX_BATCH ? B - b0 : DRAW_MAX_BATCH;
         DrawBatch fb;
-        int tiles = 0;
-        for (int i = 0; i < nb; ++i) {
-            fb.img[i] = h_imgs[b0 + i]; fb.h[i] = h_hw[2 * (b0 + i)]; fb.w[i] = h_hw[2 * (b0 + i) + 1];
-            fb.tile0[i] = tiles;
-            if (frames) tiles += ((fb.w[i] + DRAW_TW - 1) / DRAW_TW) * ((fb.h[i] + DRAW_TH - 1) / DRAW_TH);
-        }
-        for (int i = nb; i < DRAW_MAX_BATCH; ++i) { fb.img[i] = nullptr; fb.h[i] = 0; fb.w[i] = 0; fb.tile0[i] = tiles; }
-        fb.tile0[nb] = tiles;
-        fb.tile0[DRAW_MAX_BATCH] = tiles;
+        const int tiles = draw_fill_batch(fb, h_imgs, h_hw, b0, nb, frames);
         const int grid = tiles + nb * bev_tiles;                   // <= 64 * 65536 * 2
         hipLaunchKernelGGL(draw_tracks_kernel, dim3((unsigned)grid), dim3(DRAW_THREADS), 0, (hipStream_t)stream, fb, nb, topk,
                            d_rec + (size_t)b0 * topk * 32, d_ids + (size_t)b0 * topk, T, tpanel ? d_state + (size_t)b0 * stream_doubles : nullptr,

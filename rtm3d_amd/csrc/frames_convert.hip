@@ -9,12 +9,14 @@
 //
 // Any byte address is legal.  A run is read with 8- or 4-byte loads when its first byte is so aligned and the whole run lies
 // inside the row's own bytes, byte by byte otherwise (row tails, odd pitches, odd bases): no read leaves rows x row bytes of
-// a plane.  The 24 output bytes of a full run leave as aligned dwords - shifted by the destination's misalignment, with a
-// byte-wise head and tail - and a partial run (the row's last) byte by byte: exactly h * w * 3 bytes are written.
+// a plane.  The 24 output bytes of a full run leave through store_rgb_run<8> (rgb_runs.h, shared with lens.hip): as aligned
+// dwords - shifted by the destination's misalignment, with a byte-wise head and tail - and a partial run (the row's last)
+// byte by byte: exactly h * w * 3 bytes are written.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/rtm3d_hip.h"
+#include "rgb_runs.h"
 
 #define CONV_PX 8
 #define CONV_ROWS 2
@@ -74,39 +76,6 @@ __device__ __forceinline__ uint32_t load_run4(const uint8_t* p, int n) {
 }
 #define BYTE_OF(v, k) (int)(((v)[(k) >> 2] >> (8 * ((k) & 3))) & 255u)
 #define HALF_OF(v, k) (int)(((v)[(k) >> 1] >> (16 * ((k) & 1))) & 65535u)
-
-// ---- the run's 24 output bytes (n pixels of them valid) to q
-__device__ __forceinline__ void store_run(uint8_t* q, const uint32_t (&px)[CONV_PX], int n) {
-    uint32_t v[6];
-    v[0] = px[0] | (px[1] << 24); v[1] = (px[1] >> 8) | (px[2] << 16); v[2] = (px[2] >> 16) | (px[3] << 8);
-    v[3] = px[4] | (px[5] << 24); v[4] = (px[5] >> 8) | (px[6] << 16); v[5] = (px[6] >> 16) | (px[7] << 8);
-    const int a = (int)((uintptr_t)q & 3);
-    if (n == CONV_PX && a == 0) {
-        if (((uintptr_t)q & 7) == 0) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) ((uint2*)q)[i] = make_uint2(v[2 * i], v[2 * i + 1]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) ((uint32_t*)q)[i] = v[i];
-        }
-    } else if (n == CONV_PX) {
-        const int hb = 4 - a, lo = 8 * hb, hi = 8 * a;          // hb = 1..3 head bytes reach the next dword boundary
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (i < hb) q[i] = (uint8_t)(v[0] >> (8 * i));
-        uint32_t* d = (uint32_t*)(q + hb);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) d[i] = (v[i] >> lo) | (v[i + 1] << hi);
-        const uint32_t t = v[5] >> lo;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (i < a) q[hb + 20 + i] = (uint8_t)(t >> (8 * i));
-    } else {
-#pragma unroll
-        for (int i = 0; i < 3 * CONV_PX; ++i)
-            if (i < 3 * n) q[i] = (uint8_t)(v[i >> 2] >> (8 * (i & 3)));
-    }
-}
 
 __device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
 
@@ -213,7 +182,7 @@ __device__ __forceinline__ void convert_run(const ConvFrame& f, int x0, int y0) 
                 px[2 * i + 1] = pixel_of<S>(BYTE_OF(v, 4 * i + 2 + YB), q, c[0], yo, swap);
             }
         }
-        store_run(f.dst + ((size_t)y * f.w + x0) * 3, px, n);
+        store_rgb_run<CONV_PX>(f.dst + ((size_t)y * f.w + x0) * 3, px, n);
     }
 }
 

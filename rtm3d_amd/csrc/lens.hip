@@ -11,9 +11,10 @@
 // 16-byte aligned map), dword loads otherwise.  A pixel whose four samples all lie inside the source reads each of its two
 // source rows as the six consecutive bytes of two neighbouring pixels (a 4- and a 2-byte load at the bytes' own address: the
 // device reads global memory at any alignment) - exactly those bytes, so no read leaves the source; a pixel at the border
-// reads the samples that are inside and have a weight, byte by byte.  The 12 output bytes of a full run leave as aligned
-// dwords - shifted by the destination's misalignment, with a byte-wise head and tail - and a partial run (the row's last)
-// byte by byte: exactly ho * wo * 3 bytes are written.
+// reads the samples that are inside and have a weight, byte by byte.  The 12 output bytes of a full run leave through
+// store_rgb_run<4> (rgb_runs.h, shared with frames_convert.hip): as aligned dwords - shifted by the destination's
+// misalignment, with a byte-wise head and tail - and a partial run (the row's last) byte by byte: exactly ho * wo * 3 bytes
+// are written.
 //
 // Builder: one thread per destination pixel, fp64 in the header's operation order (this file is compiled with
 // -ffp-contract=off).
@@ -23,6 +24,7 @@
 #include <string.h>
 
 #include "../../include/rtm3d_hip.h"
+#include "rgb_runs.h"
 
 #define LENS_PX 4
 #define LENS_THREADS 256
@@ -80,33 +82,6 @@ __device__ __forceinline__ uint32_t remap_pixel(const LensFrame& f, int sx, int 
     return out;
 }
 
-// ---- the run's 12 output bytes (n pixels of them valid) to q
-__device__ __forceinline__ void store_run(uint8_t* q, const uint32_t (&px)[LENS_PX], int n) {
-    uint32_t v[3];
-    v[0] = px[0] | (px[1] << 24); v[1] = (px[1] >> 8) | (px[2] << 16); v[2] = (px[2] >> 16) | (px[3] << 8);
-    const int a = (int)((uintptr_t)q & 3);
-    if (n == LENS_PX && a == 0) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) ((uint32_t*)q)[i] = v[i];
-    } else if (n == LENS_PX) {
-        const int hb = 4 - a, lo = 8 * hb, hi = 8 * a;                    // hb = 1..3 head bytes reach the next dword boundary
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (i < hb) q[i] = (uint8_t)(v[0] >> (8 * i));
-        uint32_t* d = (uint32_t*)(q + hb);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) d[i] = (v[i] >> lo) | (v[i + 1] << hi);
-        const uint32_t t = v[2] >> lo;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (i < a) q[hb + 8 + i] = (uint8_t)(t >> (8 * i));
-    } else {
-#pragma unroll
-        for (int i = 0; i < 3 * LENS_PX; ++i)
-            if (i < 3 * n) q[i] = (uint8_t)(v[i >> 2] >> (8 * (i & 3)));
-    }
-}
-
 __global__ __launch_bounds__(LENS_THREADS) void frames_remap_kernel(LensBatch fb) {
     const LensFrame& f = fb.f[blockIdx.y];
     const unsigned per_row = (unsigned)(f.wo + LENS_PX - 1) / LENS_PX;
@@ -128,7 +103,7 @@ __global__ __launch_bounds__(LENS_THREADS) void frames_remap_kernel(LensBatch fb
     uint32_t px[LENS_PX];
 #pragma unroll
     for (int i = 0; i < LENS_PX; ++i) px[i] = i < n ? remap_pixel(f, s[2 * i], s[2 * i + 1], fb.fill) : 0u;
-    store_run(f.dst + first * 3, px, n);
+    store_rgb_run<LENS_PX>(f.dst + first * 3, px, n);
 }
 
 // ---------------------------------------------------------------------------------------------------- the map builder

@@ -81,9 +81,7 @@ def draw_records(images, rec, K_camera=None, params=None, bev=None, check_classe
                 raise ValueError('draw_records: bev must be a contiguous uint8 tensor %s on %s' % (shape, dev))
             else:
                 panels = bev
-        ptrs = (ctypes.c_void_p * B)(*[i.data_ptr() for i in images])
-        hw = (ctypes.c_int * (2 * B))(*[int(v) for i in images for v in i.shape[:2]])
-        _lib.check(_lib.load().rtm3d_records_draw(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), B, topk, rec.data_ptr(), ptrs, hw,
+        _lib.check(_lib.load().rtm3d_records_draw(_lib.stream_ptr(dev), B, topk, rec.data_ptr(), _lib.ptr_array(images), _lib.hw_array(images),
                                                   K.data_ptr() if K is not None else None, ctypes.byref(p),
                                                   panels.data_ptr() if panels is not None else None), 'records_draw')
     return panels
@@ -177,11 +175,9 @@ def draw_tracks(images, rec, ids, K_camera=None, params=None, tracker=None, bev=
                 raise ValueError('draw_tracks: bev must be a contiguous uint8 tensor %s on %s' % (shape, dev))
             else:
                 panels = bev
-        ptrs = (ctypes.c_void_p * B)(*[i.data_ptr() for i in images])
-        hw = (ctypes.c_int * (2 * B))(*[int(v) for i in images for v in i.shape[:2]])
-        _lib.check(_lib.load().rtm3d_records_draw_tracks(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), B, topk, rec.data_ptr(),
-                                                         ids.data_ptr(), T, state.data_ptr() if state is not None else None, ptrs, hw,
-                                                         K.data_ptr() if K is not None else None, ctypes.byref(q),
+        _lib.check(_lib.load().rtm3d_records_draw_tracks(_lib.stream_ptr(dev), B, topk, rec.data_ptr(), ids.data_ptr(), T,
+                                                         state.data_ptr() if state is not None else None, _lib.ptr_array(images),
+                                                         _lib.hw_array(images), K.data_ptr() if K is not None else None, ctypes.byref(q),
                                                          panels.data_ptr() if panels is not None else None), 'records_draw_tracks')
     return panels
 

@@ -387,9 +387,64 @@ class Engine(object):
         with torch.cuda.device(self.device):
             outs = [torch.empty(sh, dtype=torch.float32, device=self.device) for sh in self.shapes] if out is None else list(out)
             ptrs = (ctypes.c_void_p * 4)(*([o.data_ptr() for o in outs] + [0] * (4 - len(outs))))
-            _lib.check(self.lib.rtm3d_forward(self.ctx, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
-                                              ctypes.c_void_p(x.data_ptr()), ptrs), 'forward')
+            _lib.check(self.lib.rtm3d_forward(self.ctx, _lib.stream_ptr(self.device), ctypes.c_void_p(x.data_ptr()), ptrs), 'forward')
         return tuple(outs)
+
+    # ---- what detect and the three detect_frames* share: the refusals in front of the step, its outputs, and what follows it
+    def _frames_ready(self, who, frames, *maps):
+        """Engine.<who> has its workspace and a full batch of frames (and of maps, where it takes them); returns them as lists."""
+        B = self.info['B']
+        if getattr(self, 'frames_workspace', None) is None:
+            raise RuntimeError('Engine.%s: call set_frame_params(mean, std, resize_to) first' % who)
+        batches = [list(b) for b in (frames,) + maps]
+        if any(len(b) != B for b in batches):
+            got = ('%d frames and %d maps' if maps else '%d') % tuple(len(b) for b in batches)
+            raise ValueError('this engine runs batches of %d frames, got %s' % (B, got))
+        return batches if maps else batches[0]
+
+    @staticmethod
+    def _check_draw(who, draw, tracker):
+        """Before anything is launched: a TrackDrawParams paints the ids only a tracker hands out."""
+        if draw is not None and tracker is None:
+            from . import draw as _draw
+            if isinstance(draw, _draw.TrackDrawParams):
+                raise ValueError('Engine.%s: draw=TrackDrawParams paints track ids and needs tracker=' % who)
+
+    def _intrinsics(self, K):
+        import torch
+        return torch.as_tensor(K, dtype=torch.float64, device=self.device).reshape(self.info['B'], 9).contiguous()
+
+    def _outputs(self, out, kitti=False):
+        """(records, KITTI rows or None) of one step; out: the caller's records."""
+        import torch
+        B, topk = self.info['B'], self.info['topk']
+        rec = torch.empty(B, topk, 32, dtype=torch.float32, device=self.device) if out is None else out
+        return rec, torch.empty(B, topk, 16, dtype=torch.float64, device=self.device) if kitti else None
+
+    @staticmethod
+    def _after_step(rec, rows, K, paint, draw, tracker, nms3d):
+        """Behind a step, in this order: nms3d on the records (and rows), one more frame for the tracker, the drawing into the
+        frames ``paint``.  Returns (panels, ids), None where there are none."""
+        if nms3d is not None:
+            from . import box_overlap
+            box_overlap.nms3d_records(rec, kitti_rows=rows, **nms3d)
+        ids = None if tracker is None else tracker.update(rec, dt=tracker.dt, ego=tracker.ego)
+        panels = None
+        if draw is not None:
+            from . import draw as _draw
+            if isinstance(draw, _draw.TrackDrawParams):
+                panels = _draw.draw_tracks(paint, rec, ids, K, draw, tracker=tracker, check_classes=False)
+            else:
+                panels = _draw.draw_records(paint, rec, K, draw, check_classes=False)
+        return panels, ids
+
+    @staticmethod
+    def _result(rec, rows, panels, ids, extra=None):
+        """(records[, rows][, panels][, ids]): alone, the records themselves; with ``extra`` appended, always a tuple."""
+        res = tuple(v for v in (rec, rows, panels, ids) if v is not None)
+        if extra is not None:
+            return res + extra
+        return res if len(res) > 1 else res[0]
 
     # (nms3d stays the LAST parameter of detect and detect_frames - tests/test_box_overlap_cpu.py pins it - so tracker, which runs
     # after nms3d, stands before it in the signatures; pass both by keyword)
@@ -403,19 +458,14 @@ class Engine(object):
         nms3d = box_overlap.nms3d_options(nms3d)
         import torch
         x = self._input(x)
-        B, topk = self.info['B'], self.info['topk']
-        K = torch.as_tensor(K_per_image, dtype=torch.float64, device=self.device).reshape(B, 9).contiguous()
+        K = self._intrinsics(K_per_image)
         with torch.cuda.device(self.device):
-            rec = torch.empty(B, topk, 32, dtype=torch.float32, device=self.device) if out is None else out
-            _lib.check(self.lib.rtm3d_engine_detect(self.ctx, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
-                                                    ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(K.data_ptr()),
-                                                    ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(self.workspace.data_ptr())),
-                       'engine_detect')
-            if nms3d is not None:
-                box_overlap.nms3d_records(rec, **nms3d)
-            if tracker is not None:
-                return rec, tracker.update(rec, dt=tracker.dt, ego=tracker.ego)
-        return rec
+            rec, _ = self._outputs(out)
+            _lib.check(self.lib.rtm3d_engine_detect(self.ctx, _lib.stream_ptr(self.device), ctypes.c_void_p(x.data_ptr()),
+                                                    ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+                                                    ctypes.c_void_p(self.workspace.data_ptr())), 'engine_detect')
+            _, ids = self._after_step(rec, None, K, None, None, tracker, nms3d)
+        return self._result(rec, None, None, ids)
 
     def set_frame_params(self, mean, std, resize_to=None):
         """Once, before detect_frames (rtm3d_engine_set_frame_params): the Normalize mean / std of the frames (cfg.DATASET.MEAN /
@@ -442,46 +492,23 @@ class Engine(object):
         import torch
         from . import box_overlap
         nms3d = box_overlap.nms3d_options(nms3d)
-        B, topk = self.info['B'], self.info['topk']
-        if getattr(self, 'frames_workspace', None) is None:
-            raise RuntimeError('Engine.detect_frames: call set_frame_params(mean, std, resize_to) first')
-        if len(images) != B:
-            raise ValueError('this engine runs batches of %d frames, got %d' % (B, len(images)))
+        images = self._frames_ready('detect_frames', images)
         imgs = []
         for img in images:
             if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_cuda:
                 raise ValueError('expected uint8 (h, w, 3) CUDA frames')
             imgs.append(img.contiguous())
-        ptrs = (ctypes.c_void_p * B)(*[i.data_ptr() for i in imgs])
-        hw = (ctypes.c_int * (2 * B))(*[int(v) for i in imgs for v in i.shape[:2]])
-        K = torch.as_tensor(K_camera, dtype=torch.float64, device=self.device).reshape(B, 9).contiguous()
+        K = self._intrinsics(K_camera)
         with torch.cuda.device(self.device):
-            if draw is not None and tracker is None:
-                from . import draw as _draw
-                if isinstance(draw, _draw.TrackDrawParams):
-                    raise ValueError('Engine.detect_frames: draw=TrackDrawParams paints track ids and needs tracker=')
-            rec = torch.empty(B, topk, 32, dtype=torch.float32, device=self.device) if out is None else out
-            rows = torch.empty(B, topk, 16, dtype=torch.float64, device=self.device) if kitti else None
-            _lib.check(self.lib.rtm3d_engine_detect_frames(self.ctx, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
-                                                           ptrs, hw, ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+            self._check_draw('detect_frames', draw, tracker)
+            rec, rows = self._outputs(out, kitti)
+            _lib.check(self.lib.rtm3d_engine_detect_frames(self.ctx, _lib.stream_ptr(self.device), _lib.ptr_array(imgs), _lib.hw_array(imgs),
+                                                           ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
                                                            ctypes.c_void_p(rows.data_ptr()) if kitti else None,
                                                            ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames')
-            if nms3d is not None:
-                box_overlap.nms3d_records(rec, kitti_rows=rows, **nms3d)
-            ids = None if tracker is None else tracker.update(rec, dt=tracker.dt, ego=tracker.ego)
-            panels = None
-            if draw is not None:
-                from . import draw as _draw
-                if isinstance(draw, _draw.TrackDrawParams):
-                    panels = _draw.draw_tracks(list(images), rec, ids, K, draw, tracker=tracker, check_classes=False)
-                else:
-                    panels = _draw.draw_records(list(images), rec, K, draw, check_classes=False)
-        res = (rec, rows) if kitti else (rec,)
-        if panels is not None:
-            res = res + (panels,)
-        if ids is not None:
-            res = res + (ids,)
-        return res if len(res) > 1 else res[0]
+            # (the caller's tensors, not their contiguous copies: the drawing refuses a frame it could not paint in place)
+            panels, ids = self._after_step(rec, rows, K, images, draw, tracker, nms3d)
+        return self._result(rec, rows, panels, ids)
 
     def detect_frames_rig(self, images, K_camera, rig, kitti=False, nms3d=None, tracker=None, out=None):
         """detect_frames on the R * C frames of a rig.Rig (frame r * C + c = camera c of rig r; the engine's batch is R * C), then
@@ -522,45 +549,20 @@ class Engine(object):
         import torch
         from . import box_overlap, pixfmt
         nms3d = box_overlap.nms3d_options(nms3d)
-        B, topk = self.info['B'], self.info['topk']
-        if getattr(self, 'frames_workspace', None) is None:
-            raise RuntimeError('Engine.detect_frames_src: call set_frame_params(mean, std, resize_to) first')
-        sources = list(sources)
-        if len(sources) != B:
-            raise ValueError('this engine runs batches of %d frames, got %d' % (B, len(sources)))
+        sources = self._frames_ready('detect_frames_src', sources)
         src = pixfmt.c_sources(sources)
-        K = torch.as_tensor(K_camera, dtype=torch.float64, device=self.device).reshape(B, 9).contiguous()
+        K = self._intrinsics(K_camera)
         with torch.cuda.device(self.device):
-            if draw is not None and tracker is None:
-                from . import draw as _draw
-                if isinstance(draw, _draw.TrackDrawParams):
-                    raise ValueError('Engine.detect_frames_src: draw=TrackDrawParams paints track ids and needs tracker=')
+            self._check_draw('detect_frames_src', draw, tracker)
             packed = pixfmt.packed_buffers(sources, packed)
-            ptrs = (ctypes.c_void_p * B)(*[p.data_ptr() for p in packed])
-            rec = torch.empty(B, topk, 32, dtype=torch.float32, device=self.device) if out is None else out
-            rows = torch.empty(B, topk, 16, dtype=torch.float64, device=self.device) if kitti else None
+            rec, rows = self._outputs(out, kitti)
             _lib.check(self.lib.rtm3d_engine_detect_frames_src(
-                self.ctx, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), src, ptrs,
-                pixfmt._lookup(pixfmt.ORDERS, order, 'order'), ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
-                ctypes.c_void_p(rows.data_ptr()) if kitti else None, ctypes.c_void_p(self.frames_workspace.data_ptr())),
-                'engine_detect_frames_src')
+                self.ctx, _lib.stream_ptr(self.device), src, _lib.ptr_array(packed), pixfmt._lookup(pixfmt.ORDERS, order, 'order'),
+                ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(rows.data_ptr()) if kitti else None,
+                ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames_src')
             self.last_packed = packed
-            if nms3d is not None:
-                box_overlap.nms3d_records(rec, kitti_rows=rows, **nms3d)
-            ids = None if tracker is None else tracker.update(rec, dt=tracker.dt, ego=tracker.ego)
-            panels = None
-            if draw is not None:
-                from . import draw as _draw
-                if isinstance(draw, _draw.TrackDrawParams):
-                    panels = _draw.draw_tracks(packed, rec, ids, K, draw, tracker=tracker, check_classes=False)
-                else:
-                    panels = _draw.draw_records(packed, rec, K, draw, check_classes=False)
-        res = (rec, rows) if kitti else (rec,)
-        if panels is not None:
-            res = res + (panels,)
-        if ids is not None:
-            res = res + (ids,)
-        return res if len(res) > 1 else res[0]
+            panels, ids = self._after_step(rec, rows, K, packed, draw, tracker, nms3d)
+        return self._result(rec, rows, panels, ids)
 
     def detect_frames_lens(self, frames_or_sources, maps, order='rgb', fill=(0, 0, 0), K_rect=None, packed=None, rect=None, kitti=False,
                            out=None, draw=None, tracker=None, nms3d=None):
@@ -575,12 +577,7 @@ class Engine(object):
         import torch
         from . import box_overlap, lens, pixfmt
         nms3d = box_overlap.nms3d_options(nms3d)
-        B, topk = self.info['B'], self.info['topk']
-        if getattr(self, 'frames_workspace', None) is None:
-            raise RuntimeError('Engine.detect_frames_lens: call set_frame_params(mean, std, resize_to) first')
-        raw, maps = list(frames_or_sources), list(maps)
-        if len(raw) != B or len(maps) != B:
-            raise ValueError('this engine runs batches of %d frames, got %d frames and %d maps' % (B, len(raw), len(maps)))
+        raw, maps = self._frames_ready('detect_frames_lens', frames_or_sources, maps)
         cm = lens.c_maps(maps)
         from_src = all(isinstance(r, pixfmt.FrameSource) for r in raw)
         if not from_src and any(isinstance(r, pixfmt.FrameSource) for r in raw):
@@ -589,46 +586,26 @@ class Engine(object):
             if any(m.K_rect is None for m in maps):
                 raise ValueError('Engine.detect_frames_lens: a map without K_rect needs K_rect=')
             K_rect = np.stack([m.K_rect for m in maps])
-        K = torch.as_tensor(K_rect, dtype=torch.float64, device=self.device).reshape(B, 9).contiguous()
+        K = self._intrinsics(K_rect)
         with torch.cuda.device(self.device):
-            if draw is not None and tracker is None:
-                from . import draw as _draw
-                if isinstance(draw, _draw.TrackDrawParams):
-                    raise ValueError('Engine.detect_frames_lens: draw=TrackDrawParams paints track ids and needs tracker=')
+            self._check_draw('detect_frames_lens', draw, tracker)
             if from_src:
                 src, hw = pixfmt.c_sources(raw), None
                 packed = pixfmt.packed_buffers(raw, packed)
             else:
                 src = None
                 packed = lens.packed_frames(raw)
-                hw = (ctypes.c_int * (2 * B))(*[int(v) for p in packed for v in p.shape[:2]])
+                hw = _lib.hw_array(packed)
             rect = lens.rect_buffers(maps, rect)
-            pptr = (ctypes.c_void_p * B)(*[p.data_ptr() for p in packed])
-            rptr = (ctypes.c_void_p * B)(*[r.data_ptr() for r in rect])
-            rec = torch.empty(B, topk, 32, dtype=torch.float32, device=self.device) if out is None else out
-            rows = torch.empty(B, topk, 16, dtype=torch.float64, device=self.device) if kitti else None
+            rec, rows = self._outputs(out, kitti)
             _lib.check(self.lib.rtm3d_engine_detect_frames_lens(
-                self.ctx, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), src, pptr, hw,
-                pixfmt._lookup(pixfmt.ORDERS, order, 'order'), cm, rptr, lens.c_fill(fill), ctypes.c_void_p(K.data_ptr()),
-                ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(rows.data_ptr()) if kitti else None,
-                ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames_lens')
+                self.ctx, _lib.stream_ptr(self.device), src, _lib.ptr_array(packed), hw, pixfmt._lookup(pixfmt.ORDERS, order, 'order'), cm,
+                _lib.ptr_array(rect), lens.c_fill(fill), ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+                ctypes.c_void_p(rows.data_ptr()) if kitti else None, ctypes.c_void_p(self.frames_workspace.data_ptr())),
+                'engine_detect_frames_lens')
             self.last_packed, self.last_rect = packed, rect
-            if nms3d is not None:
-                box_overlap.nms3d_records(rec, kitti_rows=rows, **nms3d)
-            ids = None if tracker is None else tracker.update(rec, dt=tracker.dt, ego=tracker.ego)
-            panels = None
-            if draw is not None:
-                from . import draw as _draw
-                if isinstance(draw, _draw.TrackDrawParams):
-                    panels = _draw.draw_tracks(rect, rec, ids, K, draw, tracker=tracker, check_classes=False)
-                else:
-                    panels = _draw.draw_records(rect, rec, K, draw, check_classes=False)
-        res = (rec, rows) if kitti else (rec,)
-        if panels is not None:
-            res = res + (panels,)
-        if ids is not None:
-            res = res + (ids,)
-        return res + (rect,)
+            panels, ids = self._after_step(rec, rows, K, rect, draw, tracker, nms3d)
+        return self._result(rec, rows, panels, ids, extra=(rect,))
 
     def close(self):
         if self.ctx:

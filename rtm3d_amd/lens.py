@@ -129,8 +129,7 @@ def build_maps(models, K_rect=None, R=None, out_size=None, device='cuda'):
             if not (1 <= ho <= 16384 and 1 <= wo <= 16384):
                 raise ValueError('map %d: a map of %d x %d; a side must lie in 1..16384' % (i, ho, wo))
             maps.append(LensMap(torch.empty(ho, wo, 2, dtype=torch.int32, device=dev), K))
-        ptrs = (ctypes.c_void_p * n)(*[m.tensor.data_ptr() for m in maps])
-        _lib.check(_lib.load().rtm3d_lens_map_build(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), n, cm, cr, ptrs),
+        _lib.check(_lib.load().rtm3d_lens_map_build(_lib.stream_ptr(dev), n, cm, cr, _lib.ptr_array([m.tensor for m in maps])),
                    'lens_map_build')
     return maps
 
@@ -201,10 +200,6 @@ def remap(frames, maps, fill=(0, 0, 0), out=None):
     dev = frames[0].device
     with torch.cuda.device(dev):
         out = rect_buffers(maps, out)
-        n = len(frames)
-        src = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
-        dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
-        hw = (ctypes.c_int * (2 * n))(*[int(v) for f in frames for v in f.shape[:2]])
-        _lib.check(_lib.load().rtm3d_frames_remap(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), n, src, hw, cm, dst,
-                                                  c_fill(fill)), 'frames_remap')
+        _lib.check(_lib.load().rtm3d_frames_remap(_lib.stream_ptr(dev), len(frames), _lib.ptr_array(frames), _lib.hw_array(frames), cm,
+                                                  _lib.ptr_array(out), c_fill(fill)), 'frames_remap')
     return out

@@ -210,7 +210,6 @@ def convert(sources, order='rgb', out=None):
     dev = sources[0].device
     with torch.cuda.device(dev):
         out = packed_buffers(sources, out)
-        dst = (ctypes.c_void_p * len(out))(*[o.data_ptr() for o in out])
-        _lib.check(_lib.load().rtm3d_frames_convert(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), len(out), src, dst,
+        _lib.check(_lib.load().rtm3d_frames_convert(_lib.stream_ptr(dev), len(out), src, _lib.ptr_array(out),
                                                     _lookup(ORDERS, order, 'order')), 'frames_convert')
     return out

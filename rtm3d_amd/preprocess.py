@@ -64,7 +64,7 @@ def letterbox_normalize(images, size, mean, std, out=None):
         lut = torch.as_tensor(normalize_lut(mean, std), device=dev)
         sums = torch.zeros(B, 3, dtype=torch.int64, device=dev)
         pads = []
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream_ptr(dev)
         for b, img in enumerate(images):
             if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
                 raise ValueError('expected uint8 (h, w, 3) images')
@@ -126,11 +126,11 @@ def preprocess_batch(images, size, mean, std, resize_to=None, out=None, model=No
     rhw = np.array([resized_size(h, w, resize_to) if resize_to else (h, w) for h, w in hw], np.int32)
     if (rhw[:, 0] > H).any() or (rhw[:, 1] > W).any() or (rhw < 1).any():
         raise ValueError('a resized image does not fit the %dx%d canvas: %s' % (H, W, rhw.tolist()))
-    ptrs = (ctypes.c_void_p * B)(*[i.data_ptr() for i in imgs])
+    ptrs = _lib.ptr_array(imgs)
     d_lut, d_lut16 = device_luts(mean, std, dev)
     with torch.cuda.device(dev):
         sums = torch.zeros(B, 3, dtype=torch.int64, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream_ptr(dev)
         if model is not None:
             base, border = model.input_tensor(B, H, W, dev, heads, head_precision)
             mode, dst, ret = 1, base, None
@@ -173,7 +173,7 @@ def adjust_K_device(K_camera, geom, out=None):
             out = torch.empty(B, 9, dtype=torch.float64, device=dev)
         if out.dtype != torch.float64 or out.numel() != B * 9 or not out.is_contiguous() or out.device != dev:
             raise ValueError('out must be a contiguous float64 tensor of %d x 9 on %s' % (B, dev))
-        _lib.check(lib.rtm3d_frames_adjust_k(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), B, geom, K_camera.data_ptr(),
+        _lib.check(lib.rtm3d_frames_adjust_k(_lib.stream_ptr(dev), B, geom, K_camera.data_ptr(),
                                              out.data_ptr()), 'frames_adjust_K')
     return out
 
@@ -202,6 +202,6 @@ def records_to_camera(rec, geom, K_camera=None, boxes=None, kitti=False):
     with torch.cuda.device(dev):
         if kitti:
             rows = torch.empty(B, topk, 16, dtype=torch.float64, device=dev)
-        _lib.check(lib.rtm3d_records_to_camera(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), B, topk, geom, rec.data_ptr(),
+        _lib.check(lib.rtm3d_records_to_camera(_lib.stream_ptr(dev), B, topk, geom, rec.data_ptr(),
                                                *args, float(FUN_ACCEPT), rows.data_ptr() if kitti else None), 'records_to_camera')
     return (rec, rows) if kitti else rec

@@ -19,6 +19,11 @@ BLOCK_EDGES = [(2, G * T - G), (2, G * T), (2, G * T + 1), (2 * T - 2, G), (2 * 
 # rows whose every run is whole and aligned at base offset 0 (the wide loads and stores), next to one that is not
 WIDE = [(4, 16), (3, 24), (5, 40), (7, 33)]
 SIZES = SMALL + RUN_EDGES + BLOCK_EDGES
+# the store of a run (csrc/rgb_runs.h) at the destination addresses base_offsets() leaves to the luck of an odd width: a row of
+# three whole runs is 72 bytes, so every run keeps the base's alignment - 2 modulo 4 (the shifted store), 4 modulo 8 (dword
+# but not 8-byte stores) - and a row of 21 pixels ends in a partial run and walks the addresses through every residue
+STORE_SIZES = [(3, 24), (3, 21)]
+STORE_OFFSETS = (2, 4)
 
 MATRIX_RANGE = [(m, r) for m in ('bt601', 'bt709') for r in ('limited', 'full')]
 

@@ -107,10 +107,12 @@ def test_map_kinds_over_every_size(dev, kind):
 
 # ---------------------------------------------------------------------------------------------------- 2. addresses
 def test_address_sweep(dev):
-    """Source and destination bases at byte offsets 0..3 into their allocations: the same bytes come out wherever they lie."""
+    """Source and destination bases at byte offsets 0..3 into their allocations: the same bytes come out wherever they lie.
+    (3 x 8 and 3 x 7: rows of two whole runs, which keep the base's alignment, and rows that end in a partial run - every
+    branch of the run store, csrc/rgb_runs.h, at every address modulo 4.)"""
     rng = np.random.Generator(np.random.PCG64(20))
     jobs = []
-    for (h, w), dsts in (((37, 53), [(48, 64), (33, 65), (3, 5), (1, 7)]), ((5, 4), [(2, 9), (3, 4), (1, 1)])):
+    for (h, w), dsts in (((37, 53), [(48, 64), (33, 65), (3, 5), (1, 7)]), ((5, 4), [(2, 9), (3, 4), (1, 1), (3, 8), (3, 7)])):
         f = cases.frames_for(h, w, rng)[0]
         jobs += [(f, cases.make_map(kind, h, w, ho, wo, rng)) for ho, wo in dsts for kind in ('random', 'fractions')]
     first = None

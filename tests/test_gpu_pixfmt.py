@@ -121,7 +121,7 @@ def test_pitch_sweep(dev, fmt):
 @pytest.mark.parametrize('fmt', ref.FORMATS)
 def test_address_sweep(dev, fmt):
     """Plane and destination bases at byte offsets 0, 1, 3 (P010 planes: 0, 2) into their allocations, at the least pitch and
-    one byte (P010: two) above it: the same bytes come out wherever they lie."""
+    one byte (P010: two) above it: the same bytes come out wherever they lie.  Then the destination alone at offsets 2 and 4."""
     rng = np.random.Generator(np.random.PCG64(200 + ref.FORMAT_ID[fmt]))
     m, r = cases.variants(fmt)[0]
     srcs = [cases.build_source(fmt, h, w, rng, extra, m, r) for extra in cases.pitch_steps(fmt)[:2]
@@ -132,6 +132,11 @@ def test_address_sweep(dev, fmt):
             got = [t.cpu() for t in run_and_compare(srcs, dev, 'bgr', so, do)]
             first = first or got
             assert all(torch.equal(a, b) for a, b in zip(first, got))
+    # destination bases 2 modulo 4 and 4 modulo 8, on rows of whole runs and rows that end in a partial one (cases.STORE_SIZES)
+    srcs = [cases.build_source(fmt, h, w, rng, 0, m, r) for (h, w) in cases.STORE_SIZES]
+    first = [t.cpu() for t in run_and_compare(srcs, dev, 'bgr')]
+    for do in cases.STORE_OFFSETS:
+        assert all(torch.equal(a, b.cpu()) for a, b in zip(first, run_and_compare(srcs, dev, 'bgr', 0, do)))
 
 
 # ---------------------------------------------------------------------------------------------------- 4. batches
