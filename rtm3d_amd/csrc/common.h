@@ -232,6 +232,8 @@ hipError_t launch_conv_mfma256(const ConvKArgs& a, int groups, unsigned int* til
 // workgroup (conv_mfma256_kernel), the generic persistent kernel, the halo-tile kernel, the dilation row-sub-lattice kernel
 enum Conv256Route { C256_ONE_TILE, C256_PERSISTENT, C256_HALO, C256_LATTICE };
 Conv256Route conv_mfma256_route(const ConvKArgs& a, int groups, HaloTaps* ht);
+// the row order the 256 x 256 kernels read their packed weights in (conv_mfma256.hip, "Store layout"); host code
+void conv_mfma256_permute_weights(const f16* src, f16* dst, size_t n_ktiles);
 bool conv64_halo_supported(const ConvKArgs& a, int groups);
 hipError_t launch_conv64_halo(const ConvKArgs& a, int cu_count, unsigned int* ticket_ctr, hipStream_t s);
 hipError_t launch_conv64_root(const ConvKArgs& a, const RootKArgs& r, int cu_count, unsigned int* ticket_ctr, hipStream_t s);

@@ -16,10 +16,42 @@
 //   * raw s_barrier twice per phase (after the load segment, after the MFMA segment); waves 4-7
 //     run one barrier behind waves 0-3, so on every SIMD one wave issues MFMAs while its partner
 //     issues LDS reads / DMA / waits (the two co-resident waves of a SIMD share one matrix pipe).
+//
+// Store layout (all four 256 x 256 kernels: this file's two, conv_mfma256_halo.hip, conv_mfma256_lattice.hip).  The PIXEL fragment
+// is the MFMA's A operand and the weight fragment its B operand, so in a 16 x 16 accumulator tile lane (fk, frow) holds pixels
+// fk * 4 + {0..3} of ONE channel column frow.  A wave's four channel tiles (W half j, tile c) are made four CONSECUTIVE channels
+// of the wave's 64-channel run - column frow of tile t = j * 2 + c is channel wc * 64 + frow * 4 + t - so a lane packs the same
+// register of its four tiles into 8 bytes, and one global_store_dwordx2 writes four pixels' 128 contiguous bytes each (lanes
+// 16 k .. 16 k + 15 = one pixel): 32 stores per lane and tile, no v_permlane16_swap; the residual loads (RES) have the same shape.
+// Before: weights as A, the pixel on frow, 16 stores of 16 pixels x 64 B each, the four 16-B pieces of a run from lanes 16 apart.
+// Measured on the epilogue alone (tools/microbench/store_patterns.hip, profiles/store_patterns.txt: 128 KB per workgroup from
+// registers, all CUs together): 8.6k cycles per burst before, 5.2-5.4k in this shape at 256 and at 1024 channels per pixel; the
+// 16-byte form of it (64-pixel x 128-channel wave tiles) 3.2-3.4k - not built: it changes the wave tile, i.e. the K loop's operand
+// reads; today's loads of the residual (16 pixels x 32 B per instruction) 17k against 5-7k.
+// The LDS image, the operand reads, the DMA schedule and the counted waits of the K loop are unchanged (the first K-tile of a
+// tile counts 32 stores of the tile before instead of 16): the kernels read a COPY of the op's packed weights in which row
+// j * 128 + wc * 32 + c * 16 + frow of every 256-row K-tile holds channel wc * 64 + frow * 4 + j * 2 + c, re-swizzled for its new
+// row (conv_mfma256_permute_weights; made once per op by rtm3d_op_conv's admission - the weights are constant for the life of a
+// plan).  Reading the permuted rows from the unpermuted image instead would put the 16 lanes of a fragment on two swizzle keys.
+#include <string.h>
 #include "common.h"
 
 #define LDS_AS __attribute__((address_space(3)))
 #define GLB_AS __attribute__((address_space(1)))
+
+// dst = src with the 256 rows of each of the n_ktiles K-tiles ([256 rows][8 chunks][8 halves], chunk ^= row & 7 baked in) in the
+// order of the store layout above.  Host code.
+void conv_mfma256_permute_weights(const f16* src, f16* dst, size_t n_ktiles) {
+    for (size_t k = 0; k < n_ktiles; ++k)
+        for (int rd = 0; rd < 256; ++rd) {
+            const int j = rd >> 7, wc = (rd >> 5) & 3, c = (rd >> 4) & 1, frow = rd & 15;
+            const int rs = wc * 64 + frow * 4 + j * 2 + c;
+            for (int pos = 0; pos < 8; ++pos) {
+                const int chunk = pos ^ (rd & 7);                  // the logical 8-channel chunk at position pos of row rd
+                memcpy(dst + (k * 256 + rd) * 64 + pos * 8, src + (k * 256 + rs) * 64 + (chunk ^ (rs & 7)) * 8, 16);
+            }
+        }
+}
 
 #define HALF_ELEMS (128 * 64)            // one half-tile: 128 rows x 64 halves = 16 KB
 #define BUF_ELEMS (4 * HALF_ELEMS)       // XA XB WA WB
@@ -27,6 +59,13 @@
 #define SLOT_XB 1
 #define SLOT_WA 2
 #define SLOT_WB 3
+
+// the pixel after (n, y, x) in iteration order (row-major over the Hm x Wm map, image after image); `live` false: stay (rows past M)
+__device__ __forceinline__ void c256_next_pixel(int& n, int& y, int& x, bool live, int Wm, int Hm) {
+    const bool wx = x + 1 == Wm, wy = wx && y + 1 == Hm;
+    const int x1 = wx ? 0 : x + 1, y1 = wy ? 0 : (wx ? y + 1 : y), n1 = wy ? n + 1 : n;
+    x = live ? x1 : x; y = live ? y1 : y; n = live ? n1 : n;
+}
 
 template <int RES>
 __global__ __launch_bounds__(512) void conv_mfma256_kernel(const ConvKArgs a) {
@@ -133,7 +172,7 @@ __global__ __launch_bounds__(512) void conv_mfma256_kernel(const ConvKArgs a) {
     _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                        \
         _Pragma("unroll") for (int c = 0; c < 2; ++c)                                       \
             _Pragma("unroll") for (int p = 0; p < 4; ++p)                                   \
-                acc[i][j][c][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfrag[c][kk], xf[p][kk], acc[i][j][c][p], 0, 0, 0); \
+                acc[i][j][c][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[p][kk], wfrag[c][kk], acc[i][j][c][p], 0, 0, 0); \
     __builtin_amdgcn_s_setprio(0);                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                      \
     __builtin_amdgcn_s_barrier();                                                           \
@@ -168,50 +207,46 @@ __global__ __launch_bounds__(512) void conv_mfma256_kernel(const ConvKArgs a) {
     // All loads (bias, residual) are issued before the first store and the stores form one
     // dependency-free run: a load between two stores would make the compiler wait vmcnt(0), i.e. for
     // the previous store's acknowledgement as well, and serialise 32 round trips per thread.
-    f32x4 bv[2][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-            bv[j][c] = *(const f32x4*)(a.bias + g.bias_off + ntile * 256 + j * 128 + wc * 32 + c * 16 + fk * 4);
+    // Store layout: see the header.  A lane's four tiles (j, c) are the channels wc * 64 + frow * 4 + j * 2 + c, its four registers
+    // of a tile the pixels fk * 4 + e of the fragment: 8 bytes per lane and store, 128 contiguous bytes per pixel.
+    const f32x4 bv = *(const f32x4*)(a.bias + g.bias_off + ntile * 256 + wc * 64 + frow * 4);
     const float lo = a.relu ? 0.f : -__builtin_inff();
-    const int cbase = ntile * 256 + wc * 32 + fk * 4;
+    const int cbase = ntile * 256 + wc * 64 + frow * 4;
+    const int Hm = a.HmWm / a.Wm;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        size_t opix[4];
-        f16x4 rv[4][2][2];
+        size_t opix[4][4];
+        f16x4 rv[4][4];
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             // rows past M were staged from pixel M-1 (see xoff), so they hold its result: storing them
             // to its address again is a same-value write and keeps the epilogue branch-free
-            int m = mtile * 256 + i * 128 + wp * 64 + p * 16 + frow;
-            m = m < a.M ? m : a.M - 1;
-            const int n = m / a.HmWm, rem = m - n * a.HmWm;
-            const int y = rem / a.Wm, x = rem - y * a.Wm;
-            const int oy = y * a.out_scale + g.out_oy, ox = x * a.out_scale + g.out_ox;
-            opix[p] = ((size_t)(n * a.out_Hp + oy + a.out_P) * a.out_Wp + ox + a.out_P) * a.out_C + g.out_coff + cbase;
-            if (RES) {
-                const f16* rp = a.res + ((size_t)(n * a.res_Hp + oy + a.res_P) * a.res_Wp + ox + a.res_P) * a.res_C + g.res_coff + cbase;
+            const int m0 = mtile * 256 + i * 128 + wp * 64 + p * 16 + fk * 4;
+            const int m = m0 < a.M ? m0 : a.M - 1;
+            int n = m / a.HmWm;
+            const int rem = m - n * a.HmWm;
+            int y = rem / a.Wm, x = rem - y * a.Wm;
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) rv[p][j][c] = *(const f16x4*)(rp + j * 128 + c * 16);
+            for (int e = 0; e < 4; ++e) {
+                if (e) c256_next_pixel(n, y, x, m0 + e < a.M, a.Wm, Hm);
+                const int oy = y * a.out_scale + g.out_oy, ox = x * a.out_scale + g.out_ox;
+                opix[p][e] = ((size_t)(n * a.out_Hp + oy + a.out_P) * a.out_Wp + ox + a.out_P) * a.out_C + g.out_coff + cbase;
+                if (RES) rv[p][e] = *(const f16x4*)(a.res + ((size_t)(n * a.res_Hp + oy + a.res_P) * a.res_Wp + ox + a.res_P) * a.res_C + g.res_coff + cbase);
             }
         }
 #pragma unroll
         for (int p = 0; p < 4; ++p)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    f32x4 v = acc[i][j][c][p] + bv[j][c];
-                    if (RES) {
-                        const f16x4 r = rv[p][j][c];
-                        v[0] += (float)r[0]; v[1] += (float)r[1]; v[2] += (float)r[2]; v[3] += (float)r[3];
-                    }
-                    const f16x4 h = {(f16)fmaxf(v[0], lo), (f16)fmaxf(v[1], lo), (f16)fmaxf(v[2], lo), (f16)fmaxf(v[3], lo)};
-                    *(f16x4*)((f16*)a.out + opix[p] + j * 128 + c * 16) = h;
+            for (int e = 0; e < 4; ++e) {
+                f32x4 v = {acc[i][0][0][p][e], acc[i][0][1][p][e], acc[i][1][0][p][e], acc[i][1][1][p][e]};
+                v += bv;
+                if (RES) {
+                    const f16x4 r = rv[p][e];
+                    v[0] += (float)r[0]; v[1] += (float)r[1]; v[2] += (float)r[2]; v[3] += (float)r[3];
                 }
+                const f16x4 h = {(f16)fmaxf(v[0], lo), (f16)fmaxf(v[1], lo), (f16)fmaxf(v[2], lo), (f16)fmaxf(v[3], lo)};
+                *(f16x4*)((f16*)a.out + opix[p][e]) = h;
+            }
     }
 }
 
@@ -222,10 +257,9 @@ __global__ __launch_bounds__(512) void conv_mfma256_kernel(const ConvKArgs a) {
 //     tile already stage the first two of the next one (descriptor "n"), so there is no prologue,
 //     no drain and no workgroup launch between tiles;
 //   * the bias vector sits in LDS (a VMEM load in the epilogue would make the compiler drain vmcnt);
-//     the epilogue is 16 global_store_dwordx4
-//     per thread (v_permlane16_swap pairs the two 16-channel MFMA tiles so a lane owns 8 consecutive
-//     channels) with no wait behind them: the first K-tile of the next tile runs its four phases
-//     with s_waitcnt vmcnt(8+16) (the 16 stores are younger than the DMA it needs);
+//     the epilogue is 32 global_store_dwordx2 per thread (header, "Store layout": a lane owns 4 consecutive
+//     channels of 16 pixels) with no wait behind them: the first K-tile of the next tile runs its four phases
+//     with s_waitcnt vmcnt(8+32) (the 32 stores are younger than the DMA it needs);
 //   * pixel -> (image, row, column) uses a float-estimate division (quotients are tiny).
 // Measured (in-kernel stamps, bs=32): the one-tile kernel spends 1.8 us in its prologue, 5.4 us in
 // its epilogue and ~3.8 us between workgroups per tile.  That is 16 % of a 36-K-tile head tile but
@@ -276,7 +310,7 @@ __global__ __launch_bounds__(512) void conv_mfma256_kernel(const ConvKArgs a) {
     _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                        \
         _Pragma("unroll") for (int c = 0; c < 2; ++c)                                       \
             _Pragma("unroll") for (int p = 0; p < 4; ++p)                                   \
-                acc[i][j][c][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfrag[c][kk], xf[p][kk], acc[i][j][c][p], 0, 0, 0); \
+                acc[i][j][c][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[p][kk], wfrag[c][kk], acc[i][j][c][p], 0, 0, 0); \
     __builtin_amdgcn_s_setprio(0);                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                      \
     if (TAILBAR) __builtin_amdgcn_s_barrier();                                              \
@@ -324,7 +358,7 @@ __global__ __launch_bounds__(512) void conv_mfma256_kernel(const ConvKArgs a) {
     _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                        \
         _Pragma("unroll") for (int c = 0; c < 2; ++c)                                       \
             _Pragma("unroll") for (int p = 0; p < 4; ++p)                                   \
-                acc[i][j][c][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfrag[c][kk], xf[p][kk], acc[i][j][c][p], 0, 0, 0); \
+                acc[i][j][c][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[p][kk], wfrag[c][kk], acc[i][j][c][p], 0, 0, 0); \
     __builtin_amdgcn_s_setprio(0);                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                      \
     STAMP((K0) + 3)                                                                         \
@@ -353,13 +387,13 @@ __global__ __launch_bounds__(512) void conv_mfma256_kernel(const ConvKArgs a) {
 #define STAGE_WB_P2 stage_w1(SLOT_WB, 1, t + 1, sp ^ 1);
 #define STAGE_WB_P4
 #define VM1_8 5
-#define VM1_24 21
+#define VM1_40 37
 #else
 #define STAGE_WB_P1
 #define STAGE_WB_P2
 #define STAGE_WB_P4 stage(SLOT_WB, t + 2, sp, 0);
 #define VM1_8 8
-#define VM1_24 24
+#define VM1_40 40
 #endif
 #define OPA_SET(SP)                                                                         \
     {                                                                                       \
@@ -551,8 +585,7 @@ __global__ __launch_bounds__(512) void conv_mfma256_persistent_kernel(const Conv
     // LDS byte addresses (within a K-tile buffer) of this lane's operand rows, k-halves 0 and 1
     const uint32_t xrow_b0 = (uint32_t)(((wp * 64 + frow) * 64 + sw0) * 2), xrow_b1 = (uint32_t)(((wp * 64 + frow) * 64 + sw1) * 2);
     const uint32_t wrow_b0 = (uint32_t)(((wc * 32 + frow) * 64 + sw0) * 2), wrow_b1 = (uint32_t)(((wc * 32 + frow) * 64 + sw1) * 2);
-    // after the permlane swap a lane stores channels [so, so+8) of its wave's 32-channel run
-    const int so = (fk & 1) * 16 + (fk >> 1) * 8;
+    const int Hm = a.HmWm / a.Wm;
     const f16 lo = a.relu ? (f16)0.f : (f16)(-__builtin_inff());
     const f16x4 lo4 = {lo, lo, lo, lo};
 
@@ -600,23 +633,24 @@ __global__ __launch_bounds__(512) void conv_mfma256_persistent_kernel(const Conv
         // the accumulators start at the bias (fp32, from LDS) instead of at zero: the epilogue then has no add (64 packed adds per
         // lane and tile less, in the one part of a tile that no MFMA overlaps)
         {
-            const float* bp = lds_bias + a.g[gi_c].bias_off + nt_c * 256 + wc * 32 + fk * 4;
+            f32x4 b4 = *(const f32x4*)__builtin_assume_aligned(lds_bias + a.g[gi_c].bias_off + nt_c * 256 + wc * 64 + frow * 4, 16);
+            asm volatile("" : "+v"(b4));      // (bias_off is a multiple of 256.)  ONE ds_read_b128: taken apart it becomes two ds_read2_b32, which conflict (32 banks)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    const f32x4 b4 = *(const f32x4*)(bp + j * 128 + c * 16);
+                    const float b = b4[j * 2 + c];
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int p = 0; p < 4; ++p) acc[i][j][c][p] = b4;
+                        for (int p = 0; p < 4; ++p) acc[i][j][c][p] = (f32x4){b, b, b, b};
                 }
         }
         int t = 0;
         TSTAMP(0)
-        // The first K-tile's waits count the previous tile's 16 stores as well.  The workgroup's FIRST tile has none before it: with
+        // The first K-tile's waits count the previous tile's 32 stores as well.  The workgroup's FIRST tile has none before it: with
         // the same count its waits would let the prologue's K-tile-1 half-tiles stay in flight past their first read.
-        if (first_tile) STEP_N(8, VM1_8, 1, 0) else STEP_N(24, VM1_24, 1, 0)
+        if (first_tile) STEP_N(8, VM1_8, 1, 0) else STEP_N(40, VM1_40, 1, 0)
         first_tile = false;
         if (wave == 0) {
             asm volatile("s_waitcnt vmcnt(8)" : "+v"(ticket) : : "memory");
@@ -636,53 +670,42 @@ __global__ __launch_bounds__(512) void conv_mfma256_persistent_kernel(const Conv
         if (wave < 4) __builtin_amdgcn_s_barrier();
         TSTAMP(1)
 
-        // ---- epilogue of the current tile: no loads, 16 independent 16-byte stores
+        // ---- epilogue of the current tile: 32 independent 8-byte stores (behind the half's residual loads, RES)
         {
             const ConvGroupArgs& g = a.g[gi_c];
-            const int cbase = g.out_coff + nt_c * 256 + wc * 32 + so;
+            const int cbase = nt_c * 256 + wc * 64 + frow * 4;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                size_t opix[4];
-                f16x4 rv[4][2][2];       // residual (RES): loaded for the whole half before its first store
+                size_t opix[4][4];
+                f16x4 rv[4][4];          // residual (RES): loaded for the whole half before its first store
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     // rows past M were staged from pixel M-1 and hold its result: a same-value write
-                    int m = mt_c * 256 + i * 128 + wp * 64 + p * 16 + frow;
-                    m = m < a.M ? m : a.M - 1;
-                    const int n = div_small_q(m, a.HmWm, rcp_hw), rem = m - n * a.HmWm;
-                    const int y = div_small_q(rem, a.Wm, rcp_w), x = rem - y * a.Wm;
-                    const int oy = y * a.out_scale + g.out_oy, ox = x * a.out_scale + g.out_ox;
-                    opix[p] = ((size_t)(n * a.out_Hp + oy + a.out_P) * a.out_Wp + ox + a.out_P) * a.out_C + cbase;
-                    if (RES) {
-                        const f16* rp = a.res + ((size_t)(n * a.res_Hp + oy + a.res_P) * a.res_Wp + ox + a.res_P) * a.res_C
-                                        + g.res_coff + nt_c * 256 + wc * 32 + fk * 4;
+                    const int m0 = mt_c * 256 + i * 128 + wp * 64 + p * 16 + fk * 4;
+                    const int m = m0 < a.M ? m0 : a.M - 1;
+                    int n = div_small_q(m, a.HmWm, rcp_hw);
+                    const int rem = m - n * a.HmWm;
+                    int y = div_small_q(rem, a.Wm, rcp_w), x = rem - y * a.Wm;
 #pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int c = 0; c < 2; ++c) rv[p][j][c] = *(const f16x4*)(rp + j * 128 + c * 16);
+                    for (int e = 0; e < 4; ++e) {
+                        if (e) c256_next_pixel(n, y, x, m0 + e < a.M, a.Wm, Hm);
+                        const int oy = y * a.out_scale + g.out_oy, ox = x * a.out_scale + g.out_ox;
+                        opix[p][e] = ((size_t)(n * a.out_Hp + oy + a.out_P) * a.out_Wp + ox + a.out_P) * a.out_C + g.out_coff + cbase;
+                        if (RES) rv[p][e] = *(const f16x4*)(a.res + ((size_t)(n * a.res_Hp + oy + a.res_P) * a.res_Wp + ox + a.res_P) * a.res_C + g.res_coff + cbase);
                     }
                 }
 #pragma unroll
                 for (int p = 0; p < 4; ++p)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        uint32_t u[2][2];
-#pragma unroll
-                        for (int c = 0; c < 2; ++c) {
-                            f32x4 vv = acc[i][j][c][p];                  // (bias: the accumulators started at it)
-                            if (RES) {
-                                const f16x4 r = rv[p][j][c];
-                                vv[0] += (float)r[0]; vv[1] += (float)r[1]; vv[2] += (float)r[2]; vv[3] += (float)r[3];
-                            }
-                            f16x4 h = {(f16)vv[0], (f16)vv[1], (f16)vv[2], (f16)vv[3]};
-                            h = __builtin_elementwise_max(h, lo4);       // ReLU (or -inf) on packed halves
-                            __builtin_memcpy(u[c], &h, 8);
+                    for (int e = 0; e < 4; ++e) {
+                        f32x4 vv = {acc[i][0][0][p][e], acc[i][0][1][p][e], acc[i][1][0][p][e], acc[i][1][1][p][e]};   // (bias: the accumulators started at it)
+                        if (RES) {
+                            const f16x4 r = rv[p][e];
+                            vv[0] += (float)r[0]; vv[1] += (float)r[1]; vv[2] += (float)r[2]; vv[3] += (float)r[3];
                         }
-                        // rows (16-lane groups) 1,3 of the c=0 registers <-> rows 0,2 of the c=1 registers
-                        const auto s0 = __builtin_amdgcn_permlane16_swap(u[0][0], u[1][0], false, false);
-                        const auto s1 = __builtin_amdgcn_permlane16_swap(u[0][1], u[1][1], false, false);
-                        const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
-                        *(u32x4*)((f16*)a.out + opix[p] + j * 128) = o;
+                        f16x4 h = {(f16)vv[0], (f16)vv[1], (f16)vv[2], (f16)vv[3]};
+                        h = __builtin_elementwise_max(h, lo4);       // ReLU (or -inf) on packed halves
+                        *(f16x4*)((f16*)a.out + opix[p][e]) = h;
                     }
             }
         }

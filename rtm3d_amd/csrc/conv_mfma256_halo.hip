@@ -12,7 +12,10 @@
 // (kt = chunk * ntaps + tap) over the same packed weights (K-tile index tap * cpt + chunk).
 //   pixel operand DMA per 64-channel chunk: 43.5 KB instead of 9 x 32 KB; weights unchanged (9 x 32 KB).
 //
-// Schedule, tickets, bias-in-LDS, 16-byte swapped stores: as the persistent kernel of conv_mfma256.hip.
+// Schedule, tickets, bias-in-LDS, store layout (pixels as the MFMA's A operand, 8-byte stores of whole 128-byte lines, the weights
+// read from the op's row-permuted copy): as the persistent kernel of conv_mfma256.hip.  Same box, parent -> this layout: the 96 x 320
+// transposed convs 0.446 / 0.445 / 0.456 -> 0.406 / 0.420 / 0.430 ms, heads.conv_d1 3.253 -> 3.034 (profiles/store_layout_ab.txt); the
+// softmax partials now fold over a lane's 32 registers per channel and two lane exchanges instead of sixteen row rotations per tile.
 // Differences: the weight ring holds only WA/WB half-tiles (64 KB); the halo of the NEXT chunk (or of the
 // next tile's first chunk) is staged one halo ROW per DMA instruction (34 lanes of every wave, the row a running cursor in SGPRs),
 // two rows per K-tile with nine taps, three with four, so that every K-tile issues the same 0+2+2+2 (0+2+2+3) DMA instructions -
@@ -181,7 +184,6 @@ __global__ __launch_bounds__(512) void conv_mfma256_halo_kernel(const ConvKArgs 
     // (the k-half 1 slot and an odd halo row are each the same slot ^ 64 bytes)
     const uint32_t ck_m = (uint32_t)((((frow + 0) ^ fk) & 7) << 4), ck_0 = (uint32_t)((((frow + 1) ^ fk) & 7) << 4),
                    ck_p = (uint32_t)((((frow + 2) ^ fk) & 7) << 4);
-    const int so_ch = (fk & 1) * 16 + (fk >> 1) * 8;
     const f16 lo = a.relu ? (f16)0.f : (f16)(-__builtin_inff());
     const f16x4 lo4 = {lo, lo, lo, lo};
 
@@ -244,7 +246,7 @@ __global__ __launch_bounds__(512) void conv_mfma256_halo_kernel(const ConvKArgs 
     _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                            \
         _Pragma("unroll") for (int cc = 0; cc < 2; ++cc)                                        \
             _Pragma("unroll") for (int p = 0; p < 4; ++p)                                       \
-                acc[i][j][cc][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfrag[cc][kk], xf[p][kk], acc[i][j][cc][p], 0, 0, 0); \
+                acc[i][j][cc][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[p][kk], wfrag[cc][kk], acc[i][j][cc][p], 0, 0, 0); \
     PIN                                                                                         \
     __builtin_amdgcn_s_setprio(0);                                                              \
     __builtin_amdgcn_sched_barrier(0);                                                          \
@@ -372,22 +374,25 @@ __global__ __launch_bounds__(512) void conv_mfma256_halo_kernel(const ConvKArgs 
         // the accumulators start at the bias (fp32, from LDS) instead of at zero: the epilogue then has no add (64 packed adds per
         // lane and tile less, in the one part of a tile that no MFMA overlaps)
         {
-            const float* bp = lds_bias + a.g[gi_c].bias_off + nt_c * 256 + wc * 32 + fk * 4;
+            // (pixels are the MFMA's A operand: a lane's four registers of a tile are four PIXELS of one channel, and its four
+            // tiles (j, cc) are the four consecutive channels wc * 64 + frow * 4 + j * 2 + cc - conv_mfma256.hip, "Store layout")
+            f32x4 b4 = *(const f32x4*)__builtin_assume_aligned(lds_bias + a.g[gi_c].bias_off + nt_c * 256 + wc * 64 + frow * 4, 16);
+            asm volatile("" : "+v"(b4));      // (bias_off is a multiple of 256.)  ONE ds_read_b128: taken apart it becomes two ds_read2_b32, which conflict (32 banks)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int cc = 0; cc < 2; ++cc) {
-                    const f32x4 b4 = *(const f32x4*)(bp + j * 128 + cc * 16);
+                    const float b = b4[j * 2 + cc];
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int p = 0; p < 4; ++p) acc[i][j][cc][p] = b4;
+                        for (int p = 0; p < 4; ++p) acc[i][j][cc][p] = (f32x4){b, b, b, b};
                 }
         }
         const unsigned long long tapword = ht.taps[gi_c], tapword_n = ht.taps[gi_n];     // (both in SGPRs for the whole tile: no load, no branch in the K loop)
         int ch = 0, tap = 0;
         // (the counted waits are immediates: 6 DMA instructions per K-tile with nine taps, 7 with four)
-        if constexpr (NTAP == 9) STEP_H(22, 1, 0) else STEP_H(23, 1, 0)                    // + the previous tile's 16 stores
+        if constexpr (NTAP == 9) STEP_H(38, 1, 0) else STEP_H(39, 1, 0)                    // + the previous tile's 32 stores
         if (wave == 0) {
             if constexpr (NTAP == 9) asm volatile("s_waitcnt vmcnt(6)" : "+v"(ticket) : : "memory");   // the atomic is older than this K-tile's DMAs
             else asm volatile("s_waitcnt vmcnt(7)" : "+v"(ticket) : : "memory");
@@ -401,96 +406,95 @@ __global__ __launch_bounds__(512) void conv_mfma256_halo_kernel(const ConvKArgs 
         // last MFMA segment had no trailing barrier: waves 0-3 take it before their epilogue, waves 4-7 after
         if (wave < 4) __builtin_amdgcn_s_barrier();
 
-        // ---- epilogue: 16 independent 16-byte stores, no loads from global memory
+        // ---- epilogue: 32 independent 8-byte stores, no loads from global memory.  A store instruction writes four pixels' 128
+        // contiguous bytes each (lanes 16 k .. 16 k + 15 = pixel fk * 4 + e of the fragment, the wave's 64 channels)
         {
             const ConvGroupArgs& g = a.g[gi_c];
-            const int cbase = g.out_coff + nt_c * 256 + wc * 32 + so_ch;
-            f16x4 hq[2][4][2][2];          // fp16 results [pixel half][pixel tile][channel half][channel tile]
+            const int cbase = g.out_coff + nt_c * 256 + wc * 64 + frow * 4;
+            const int pstep = a.out_scale * a.out_C;                   // to the next pixel of the fragment's row
+            f16x4 hq[2][4][4];             // fp16 results [pixel half][pixel tile][pixel of the lane]: four consecutive channels each
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 size_t opix[4];
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     const int oy = (ty_c * 8 + i * 4 + wp * 2 + (p >> 1)) * a.out_scale + g.out_oy;
-                    const int ox = (tx_c * 32 + (p & 1) * 16 + frow) * a.out_scale + g.out_ox;
+                    const int ox = (tx_c * 32 + (p & 1) * 16 + fk * 4) * a.out_scale + g.out_ox;
                     opix[p] = ((size_t)(n_c * a.out_Hp + oy + a.out_P) * a.out_Wp + ox + a.out_P) * a.out_C + cbase;
                 }
 #pragma unroll
                 for (int p = 0; p < 4; ++p)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        uint32_t u[2][2];
-#pragma unroll
-                        for (int cc = 0; cc < 2; ++cc) {
-                            const f32x4 vv = acc[i][j][cc][p];                      // (bias: the accumulators started at it)
-                            f16x4 h = {(f16)vv[0], (f16)vv[1], (f16)vv[2], (f16)vv[3]};
-                            h = __builtin_elementwise_max(h, lo4);
-                            if (STATS) hq[i][p][j][cc] = h;
-                            __builtin_memcpy(u[cc], &h, 8);
-                        }
-                        const auto s0 = __builtin_amdgcn_permlane16_swap(u[0][0], u[1][0], false, false);
-                        const auto s1 = __builtin_amdgcn_permlane16_swap(u[0][1], u[1][1], false, false);
-                        const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+                    for (int e = 0; e < 4; ++e) {
+                        // (bias: the accumulators started at it)
+                        f16x4 h = {(f16)acc[i][0][0][p][e], (f16)acc[i][0][1][p][e], (f16)acc[i][1][0][p][e], (f16)acc[i][1][1][p][e]};
+                        h = __builtin_elementwise_max(h, lo4);
+                        if (STATS) hq[i][p][e] = h;
 #ifdef HALO_T_NOSTORE
-                        if (a.relu == 12345)        // (timing only: the epilogue without its 16 stores per lane.  Round 5, same box: heads.conv_d1
+                        if (a.relu == 12345)        // (timing only: the epilogue without its stores.  Round 5, same box, 16-byte swapped stores: heads.conv_d1
                                                     //  3.76 -> 3.62 ms (2 GB written), the 96 x 320 transposed convs 0.523 -> 0.510: what hiding the stores could buy)
 #endif
-                        *(u32x4*)((f16*)a.out + opix[p] + j * 128) = o;
+                        *(f16x4*)((f16*)a.out + opix[p] + e * pstep) = h;
                     }
             }
             if (STATS) {
                 // Spatial-softmax partials of this wave's 128 pixels x 64 channels (keypoint_fpn_fusion.py:67: the
                 // fusion then needs no pass over the map to find them): per channel the max and sum exp(v - max)
-                // of the STORED fp16 values.  Lane (frow, fk) holds pixels (i, p, frow) x channels (j, cc, fk*4+e):
-                // reduce over (i, p) in the lane, over frow with row rotations (DPP); lanes frow == 0 write.
+                // of the STORED fp16 values.  Lane (frow, fk) holds pixels (i, p, fk * 4 + e) x channels frow * 4 + {0..3}:
+                // reduce over (i, p, e) in the lane, over fk with two lane exchanges (16 and 32 lanes apart); lanes fk == 0 write.
                 // Layout [image][chunk = (group * tiles_per_image + tile) * 2 + wp][256 channels][max, sum].
-#define ROW_ROR_MAX(N)                                                                                           \
-    {                                                                                                            \
-        const uint32_t o_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mu[d], 0x120 + (N), 0xf, 0xf, false);  \
-        f16x2 a_, b_;                                                                                            \
-        __builtin_memcpy(&a_, &mu[d], 4); __builtin_memcpy(&b_, &o_, 4);                                         \
-        a_ = __builtin_elementwise_max(a_, b_);                                                                  \
-        __builtin_memcpy(&mu[d], &a_, 4);                                                                        \
-    }
-#define ROW_ROR_ADD(N) S[e] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, S[e]), 0x120 + (N), 0xf, 0xf, false));
+                // The partner lanes are 16 and 32 lanes away, i.e. in other DPP rows: ds_bpermute (the LDS pipe's crossbar, no memory
+                // access; twelve per lane and tile) instead of row rotations.  Not v_permlane32_swap / row_bcast: they move half-waves
+                // or one lane per row, and would need the values re-packed first.  On scalars only: update_dpp on the elements of an
+                // ext-vector was miscompiled here (the sixteen-lane fold this replaces kept its sums in scalars for that reason).
+#define FK_XCHG(V, D) __builtin_amdgcn_ds_bpermute((lane ^ (D)) << 2, (int)(V))
                 const size_t chunk = (size_t)(gi_c * tpi + ty_c * tiles_x + tx_c) * 2 + wp;
-                float* const srow = stat_out + (((size_t)n_c * (groups * tpi * 2) + chunk) * 256 + wc * 32 + fk * 4) * 2;
+                float* const srow = stat_out + (((size_t)n_c * (groups * tpi * 2) + chunk) * 256 + wc * 64 + frow * 4) * 2;
+                f16x4 mx = hq[0][0][0];
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int cc = 0; cc < 2; ++cc) {
-                        f16x4 mx = hq[0][0][j][cc];
+                    for (int p = 0; p < 4; ++p)
 #pragma unroll
-                        for (int i = 0; i < 2; ++i)
+                        for (int e = 0; e < 4; ++e) mx = __builtin_elementwise_max(mx, hq[i][p][e]);
+                uint32_t mu[2];
+                __builtin_memcpy(mu, &mx, 8);
 #pragma unroll
-                            for (int p = 0; p < 4; ++p) mx = __builtin_elementwise_max(mx, hq[i][p][j][cc]);
-                        uint32_t mu[2];
-                        __builtin_memcpy(mu, &mx, 8);
+                for (int x = 16; x <= 32; x += 16)
 #pragma unroll
-                        for (int d = 0; d < 2; ++d) { ROW_ROR_MAX(8) ROW_ROR_MAX(4) ROW_ROR_MAX(2) ROW_ROR_MAX(1) }
-                        __builtin_memcpy(&mx, mu, 8);
-                        const f32x4 M = {(float)mx[0], (float)mx[1], (float)mx[2], (float)mx[3]};
-                        // exp(h - M) = exp2(h * log2(e) - M * log2(e)): one mixed-precision fma (fp16 source, fp32 result: no separate
-                        // conversion) + v_exp_f32 + the add per element instead of cvt, sub, mul, exp, add
-                        const float L2E = 1.4426950408889634f;
-                        const f32x4 nMl = {-M[0] * L2E, -M[1] * L2E, -M[2] * L2E, -M[3] * L2E};
-                        float S[4] = {0.f, 0.f, 0.f, 0.f};     // (scalars: update_dpp on ext-vector elements was miscompiled)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-#pragma unroll
-                            for (int p = 0; p < 4; ++p) {
-                                const f16x4 h = hq[i][p][j][cc];
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) S[e] += __builtin_amdgcn_exp2f(__builtin_fmaf((float)h[e], L2E, nMl[e]));
-                            }
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { ROW_ROR_ADD(8) ROW_ROR_ADD(4) ROW_ROR_ADD(2) ROW_ROR_ADD(1) }
-                        if (frow == 0) {
-                            float* o = srow + (j * 128 + cc * 16) * 2;
-                            *(f32x4*)o = (f32x4){M[0], S[0], M[1], S[1]};
-                            *(f32x4*)(o + 4) = (f32x4){M[2], S[2], M[3], S[3]};
-                        }
+                    for (int d = 0; d < 2; ++d) {
+                        const uint32_t o_ = (uint32_t)FK_XCHG(mu[d], x);
+                        f16x2 a_, b_;
+                        __builtin_memcpy(&a_, &mu[d], 4); __builtin_memcpy(&b_, &o_, 4);
+                        a_ = __builtin_elementwise_max(a_, b_);
+                        __builtin_memcpy(&mu[d], &a_, 4);
                     }
+                __builtin_memcpy(&mx, mu, 8);
+                const f32x4 M = {(float)mx[0], (float)mx[1], (float)mx[2], (float)mx[3]};
+                // exp(h - M) = exp2(h * log2(e) - M * log2(e)): one mixed-precision fma (fp16 source, fp32 result: no separate
+                // conversion) + v_exp_f32 + the add per element instead of cvt, sub, mul, exp, add
+                const float L2E = 1.4426950408889634f;
+                const f32x4 nMl = {-M[0] * L2E, -M[1] * L2E, -M[2] * L2E, -M[3] * L2E};
+                float S[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int p = 0; p < 4; ++p)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const f16x4 h = hq[i][p][e];
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) S[c] += __builtin_amdgcn_exp2f(__builtin_fmaf((float)h[c], L2E, nMl[c]));
+                        }
+#pragma unroll
+                for (int x = 16; x <= 32; x += 16)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) S[c] += __builtin_bit_cast(float, FK_XCHG(__builtin_bit_cast(int, S[c]), x));
+                if (fk == 0) {
+                    *(f32x4*)srow = (f32x4){M[0], S[0], M[1], S[1]};
+                    *(f32x4*)(srow + 4) = (f32x4){M[2], S[2], M[3], S[3]};
+                }
+#undef FK_XCHG
             }
         }
         if (wave >= 4) __builtin_amdgcn_s_barrier();

@@ -16,10 +16,10 @@
 // one DMA instruction per wave, as in the halo kernel, two per K-tile (phases 2 and 3):
 //   tap     0          1          2          3          4        5       6       7        8
 //   P2 / P3 c.8 / c.9  n.0 / n.1  n.2 / n.3  n.4 / n.5  n.6 / =  = / =   = / =   n.7 / =  = / =        ("=": the last row again)
-// so every K-tile issues the halo kernel's 0 + 2 + 2 + 2 DMA instructions and the counted waits are its immediates (vmcnt(6), 22 in a
+// so every K-tile issues the halo kernel's 0 + 2 + 2 + 2 DMA instructions and the counted waits are its immediates (vmcnt(6), 38 = 6 + the 32 stores of the tile before in a
 // tile's first K-tile).  Everything new is issued at least one whole K-tile before its first read (n.7: tap 7 -> read in phase 3 of
 // the next chunk's tap 0) and at least two K-tiles after the last read of the row it replaces.
-// Weights, K order (chunk-major over the packed K-tiles tap * cpt + chunk), tickets, bias-in-LDS, 16-byte swapped stores: the halo
+// Weights, K order (chunk-major over the packed K-tiles tap * cpt + chunk), tickets, bias-in-LDS, store layout (8-byte stores of whole 128-byte lines; heads.conv_d6 3.512 -> 3.413 ms, profiles/store_layout_ab.txt): the halo
 // kernel's.  The operand addresses of a K-tile are four wave-uniform row-slot addresses (the ring wraps) added to one per-lane
 // column offset, computed a K-tile ahead in phase 4's load segment.
 #include "common.h"
@@ -150,7 +150,6 @@ __global__ __launch_bounds__(512) void conv_mfma256_lattice_kernel(const ConvKAr
     uint32_t xl[3];
 #pragma unroll
     for (int dxi = 0; dxi < 3; ++dxi) xl[dxi] = (uint32_t)((frow + dxi * D) * 128 + ((((frow + dxi * D) ^ fk) & 7) << 4));
-    const int so_ch = (fk & 1) * 16 + (fk >> 1) * 8;
     const f16 lo = a.relu ? (f16)0.f : (f16)(-__builtin_inff());
     const f16x4 lo4 = {lo, lo, lo, lo};
 
@@ -198,7 +197,7 @@ __global__ __launch_bounds__(512) void conv_mfma256_lattice_kernel(const ConvKAr
     _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                            \
         _Pragma("unroll") for (int cc = 0; cc < 2; ++cc)                                        \
             _Pragma("unroll") for (int p = 0; p < 4; ++p)                                       \
-                acc[i][j][cc][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfrag[cc][kk], xf[p][kk], acc[i][j][cc][p], 0, 0, 0); \
+                acc[i][j][cc][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[p][kk], wfrag[cc][kk], acc[i][j][cc][p], 0, 0, 0); \
     __builtin_amdgcn_s_setprio(0);                                                              \
     __builtin_amdgcn_sched_barrier(0);                                                          \
     if (TAILBAR) __builtin_amdgcn_s_barrier();                                                  \
@@ -310,21 +309,24 @@ __global__ __launch_bounds__(512) void conv_mfma256_lattice_kernel(const ConvKAr
         if (live_n) locate(vnext, xb_n, wb_n, gi_n, nt_n, n_n, y0_n, tx_n);
         // the accumulators start at the bias (fp32, from LDS): the epilogue has no add
         {
-            const float* bp = lds_bias + a.g[gi_c].bias_off + nt_c * 256 + wc * 32 + fk * 4;
+            // (a lane's four tiles (j, cc) are the four consecutive channels wc * 64 + frow * 4 + j * 2 + cc, its four registers of
+            // a tile four pixels - conv_mfma256.hip, "Store layout")
+            f32x4 b4 = *(const f32x4*)__builtin_assume_aligned(lds_bias + a.g[gi_c].bias_off + nt_c * 256 + wc * 64 + frow * 4, 16);
+            asm volatile("" : "+v"(b4));      // (bias_off is a multiple of 256.)  ONE ds_read_b128: taken apart it becomes two ds_read2_b32, which conflict (32 banks)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int cc = 0; cc < 2; ++cc) {
-                    const f32x4 b4 = *(const f32x4*)(bp + j * 128 + cc * 16);
+                    const float b = b4[j * 2 + cc];
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int p = 0; p < 4; ++p) acc[i][j][cc][p] = b4;
+                        for (int p = 0; p < 4; ++p) acc[i][j][cc][p] = (f32x4){b, b, b, b};
                 }
         }
         int ch = 0, tap = 0;
         LT_ORG_SET(0)
-        LT_STEP(22, 0)                                         // 6 DMA instructions per K-tile + the previous tile's 16 stores
+        LT_STEP(38, 0)                                         // 6 DMA instructions per K-tile + the previous tile's 32 stores
         if (wave == 0) {
             asm volatile("s_waitcnt vmcnt(6)" : "+v"(ticket) : : "memory");      // the atomic is older than this K-tile's DMAs
             if (lane == 0) {
@@ -337,7 +339,7 @@ __global__ __launch_bounds__(512) void conv_mfma256_lattice_kernel(const ConvKAr
         // last MFMA segment had no trailing barrier: waves 0-3 take it before their epilogue, waves 4-7 after
         if (wave < 4) __builtin_amdgcn_s_barrier();
 
-        // ---- epilogue: 16 independent 16-byte stores, no loads from global memory
+        // ---- epilogue: 32 independent 8-byte stores (four pixels' 128 contiguous bytes per instruction), no loads from global memory
         // (Round 6, same box: the epilogue of the three accumulator quadrants that are complete after phases 1-3 of the LAST K-tile
         // issued in that K-tile's load segments - ~45 vector instructions + 4 stores each, behind the segment's DMA, counted waits
         // 6 | 10 | 14 | 18 and 22 | 18 | 14 | 6 in the next tile's first K-tile - so that three quarters of the stores drain under
@@ -345,32 +347,23 @@ __global__ __launch_bounds__(512) void conv_mfma256_lattice_kernel(const ConvKAr
         // cap the tile boundary is not what this kernel waits for.  Removed.)
         {
             const ConvGroupArgs& g = a.g[gi_c];
-            const int cbase = g.out_coff + nt_c * 256 + wc * 32 + so_ch;
+            const int cbase = g.out_coff + nt_c * 256 + wc * 64 + frow * 4;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 size_t opix[4];
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     const int oy = y0_c + (i * 4 + wp * 2 + (p >> 1)) * D;
-                    const int ox = tx_c * 32 + (p & 1) * 16 + frow;
+                    const int ox = tx_c * 32 + (p & 1) * 16 + fk * 4;
                     opix[p] = ((size_t)(n_c * a.out_Hp + oy + a.out_P) * a.out_Wp + ox + a.out_P) * a.out_C + cbase;
                 }
 #pragma unroll
                 for (int p = 0; p < 4; ++p)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        uint32_t u[2][2];
-#pragma unroll
-                        for (int cc = 0; cc < 2; ++cc) {
-                            const f32x4 vv = acc[i][j][cc][p];
-                            f16x4 h = {(f16)vv[0], (f16)vv[1], (f16)vv[2], (f16)vv[3]};
-                            h = __builtin_elementwise_max(h, lo4);
-                            __builtin_memcpy(u[cc], &h, 8);
-                        }
-                        const auto s0 = __builtin_amdgcn_permlane16_swap(u[0][0], u[1][0], false, false);
-                        const auto s1 = __builtin_amdgcn_permlane16_swap(u[0][1], u[1][1], false, false);
-                        const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
-                        *(u32x4*)((f16*)a.out + opix[p] + j * 128) = o;
+                    for (int e = 0; e < 4; ++e) {
+                        f16x4 h = {(f16)acc[i][0][0][p][e], (f16)acc[i][0][1][p][e], (f16)acc[i][1][0][p][e], (f16)acc[i][1][1][p][e]};
+                        h = __builtin_elementwise_max(h, lo4);
+                        *(f16x4*)((f16*)a.out + opix[p] + (size_t)e * a.out_C) = h;
                     }
             }
         }

@@ -326,6 +326,21 @@ static int admit_mfma256(rtm3d_ctx* ctx, const rtm3d_conv_desc* d, size_t wbytes
     for (int g = 0; g < d->groups; ++g) { a.g[g].w_off = (uint32_t)(per_group * g); a.g[g].bias_off = d->cout * g; }
     op.kind = OP_CONV_MFMA256; op.bn_tile = 256;
     if (ensure_tile_ctr(ctx)) return 1;
+    // The 256 x 256 kernels read the packed weights with the rows of every K-tile in the order of their store layout
+    // (conv_mfma256.hip): a device copy of the op's own, made here once - the blob stays as the caller packed it, resident and
+    // unread, so these ops hold their weights twice (the DLA-34 plan at bs = 32: 38 MB more).  The copy goes through the host (one read-back and one
+    // upload per op at plan or engine build, both synchronous like blob_create's upload) and has a blob's 256 bytes of zeroed slack.
+    {
+        std::vector<f16> h_src(wbytes / sizeof(f16)), h_dst(wbytes / sizeof(f16));
+        RT_HIP(hipMemcpy(h_src.data(), a.wgt, wbytes, hipMemcpyDeviceToHost));
+        conv_mfma256_permute_weights(h_src.data(), h_dst.data(), wbytes / (256 * 64 * sizeof(f16)));
+        f16* w_perm = nullptr;
+        RT_HIP(hipMalloc((void**)&w_perm, wbytes + 256));
+        ctx->extra.push_back(w_perm);
+        RT_HIP(hipMemset(w_perm, 0, wbytes + 256));
+        RT_HIP(hipMemcpy(w_perm, h_dst.data(), wbytes, hipMemcpyHostToDevice));
+        a.wgt = w_perm;
+    }
     // the name says which kernel launch_conv_mfma256 will run it on (the generic persistent one keeps the bare name)
     static const char* const suffix[] = {"_1tile", "", "_halo", "_lattice"};
     op.name = d->ntaps == 1 ? "conv1x1_mfma256" : (d->ntaps == 4 ? "deconv4x4_phase_mfma256" : "conv3x3_mfma256");
