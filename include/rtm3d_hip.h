@@ -694,6 +694,112 @@ int rtm3d_frames_convert(void* stream, int B, const rtm3d_frame_src* h_src, uint
 int rtm3d_engine_detect_frames_src(rtm3d_ctx* ctx, void* stream, const rtm3d_frame_src* h_src, uint8_t* const* h_packed,
                                    int dst_order, const double* d_K_camera, float* d_rec, double* d_kitti, void* d_workspace);
 
+/* ------------------------------------------------------------------ raw sensor frames (csrc/demosaic.hip, csrc/engine.cpp)
+ * GMSL / CSI-2 automotive and machine-vision sensors deliver the colour-filter mosaic itself: one 8 / 10 / 12 / 14 / 16-bit
+ * sample per pixel in an RGGB-family Bayer pattern, often MIPI-packed.  This section turns such frames into the tightly packed
+ * uint8 (h, w, 3) frames that rtm3d_engine_detect_frames, rtm3d_frames_remap, rtm3d_preprocess_batch and the drawing entry
+ * points read: black level, white balance, demosaic, colour matrix and tone table in one launch per chunk of 32 frames,
+ * descriptors by value, no host synchronisation.  Added in ABI 9 without changing any existing declaration, struct, plan,
+ * engine file or default; a raw frame is NOT an RTM3D_PIX_* format (it needs parameters rtm3d_frame_src has no room for).
+ *
+ * SAMPLE LAYOUTS (layout, bits).  A frame is one plane, pitch bytes from one row to the next; s(x, y) is the sample value.
+ *   RTM3D_RAW_U8       the byte                                                     row bytes w              bits 8
+ *   RTM3D_RAW_U16      min(u, 2^bits - 1), u a little-endian uint16                  row bytes 2 w            bits 10 12 14 16
+ *   RTM3D_RAW_U16_MSB  u >> (16 - bits)                                              row bytes 2 w            bits 10 12 14 16
+ *   RTM3D_RAW_MIPI10   group g = x >> 2 of 5 bytes b0..b4, j = x & 3:
+ *                      (b[j] << 2) | ((b4 >> (2 j)) & 3)                             row bytes 5 ceil(w / 4)  bits 10
+ *   RTM3D_RAW_MIPI12   group g = x >> 1 of 3 bytes b0..b2, j = x & 1:
+ *                      (b[j] << 4) | ((b2 >> (4 j)) & 15)                            row bytes 3 ceil(w / 2)  bits 12
+ * The two uint16 layouts need an even plane address and an even pitch; the byte layouts accept any byte address and any pitch
+ * at or above the row bytes.  Any w is legal: the last MIPI group of a row is complete in memory.  Reads stay inside h rows
+ * of "row bytes" each (pitch padding need not exist behind the last row).
+ *
+ * PATTERNS.  k = (y & 1) * 2 + (x & 1) is the cell of pixel (x, y); the colours of cells k = 0, 1, 2, 3 are
+ *   RTM3D_CFA_RGGB: R G G B    RTM3D_CFA_BGGR: B G G R    RTM3D_CFA_GRBG: G R B G    RTM3D_CFA_GBRG: G B R G.
+ *
+ * THE RULE (integers only, int32, >> arithmetic; tests/raw_ref.py restates it in numpy).  M = 2^bits - 1.
+ * 1. Black level: l = max(s - black[k], 0).
+ * 2. White balance on the mosaic: m(x, y) = min((l * gain[k] + 512) >> 10, M); gain is Q10, 1024 is 1.0.
+ * 3. Demosaic.  m is read at (fold(x + dx, w), fold(y + dy, h)) with fold(i, n): p = 2 (n - 1), i = i mod p (non-negative),
+ *    i >= n gives p - i - reflection without repeating the edge.  p is even, so a folded position has the CFA colour of the
+ *    position it stands for; h, w >= 2 is enough.  C = m(x, y); ax1 = the sum of the two horizontal neighbours at distance 1,
+ *    ay1 of the two vertical ones, d of the four diagonal ones; ax2, ay2 = the sums of the two neighbours at distance 2 along
+ *    each axis.
+ *    RTM3D_DEMOSAIC_MHC (Malvar-He-Cutler in sixteenths).  At an R or B pixel - own colour C, the other of R / B called O:
+ *      G = (8 C + 4 (ax1 + ay1) - 2 (ax2 + ay2) + 8) >> 4        O = (12 C + 4 d - 3 (ax2 + ay2) + 8) >> 4
+ *    At a G pixel - H the colour of its horizontal neighbours, V the colour of its vertical ones:
+ *      H = (10 C + 8 ax1 - 2 d - 2 ax2 + ay2 + 8) >> 4           V = (10 C + 8 ay1 - 2 d - 2 ay2 + ax2 + 8) >> 4
+ *    Each interpolated value is clamped to [0, M]; the pixel's own colour is C.
+ *    RTM3D_DEMOSAIC_BILINEAR:  G = (ax1 + ay1 + 2) >> 2,  O = (d + 2) >> 2,  H = (ax1 + 1) >> 1,  V = (ay1 + 1) >> 1.
+ * 4. Colour matrix, Q10, signed, row-major:  c_i = clamp((ccm[3i] R + ccm[3i+1] G + ccm[3i+2] B + 512) >> 10, 0, M).
+ *    The identity (1024 on the diagonal) gives (R, G, B) back.
+ * 5. Tone: t = c >> (bits - 12) when bits >= 12, else c << (12 - bits); the byte is d_tone[t], d_tone a table of 4096 bytes
+ *    on the device and plain data (any byte address); with d_tone == NULL the byte is t >> 4.
+ * 6. The three bytes are written R G B (dst_order 0) or B G R (1).  Exactly h * w * 3 bytes are written per frame; the
+ *    destination may be any byte address.
+ * With the bounds below every intermediate stays below 2^31 (65535 * 16384 + 512 and 3 * 65535 * 8192 + 512).
+ *
+ * REFUSALS, checked for the whole batch before the first launch (the message names the frame; a refused call has launched
+ * nothing): an unknown layout, pattern, method or dst_order; bits not legal for the layout; reserved or pad != 0; a NULL plane
+ * or destination; h or w < 2 or > 16384; a pitch below the row bytes; for a uint16 layout an odd address or an odd pitch;
+ * black[k] > M; gain[k] > 16384; |ccm[i]| > 8192.
+ *
+ * OUT OF SCOPE: auto white balance and exposure, lens shading, defect pixels, denoising; decompanding of piecewise-linear HDR
+ * sensors (the tone table acts after the demosaic); RCCB, RCCC, quad-Bayer, X-Trans; fusing the demosaic into the lens remap
+ * or the preprocess; parity with OpenCV's cvtColor of COLOR_Bayer* - the rule restates the published filters, OpenCV was not
+ * at hand to pin them against (as with the lens and evaluation restatements).                                            */
+#define RTM3D_RAW_U8 0
+#define RTM3D_RAW_U16 1
+#define RTM3D_RAW_U16_MSB 2
+#define RTM3D_RAW_MIPI10 3
+#define RTM3D_RAW_MIPI12 4
+#define RTM3D_CFA_RGGB 0
+#define RTM3D_CFA_BGGR 1
+#define RTM3D_CFA_GRBG 2
+#define RTM3D_CFA_GBRG 3
+#define RTM3D_DEMOSAIC_MHC 0
+#define RTM3D_DEMOSAIC_BILINEAR 1
+typedef struct rtm3d_raw_src {             /* 80 bytes */
+    const void* plane;                     /* DEVICE */
+    const uint8_t* d_tone;                 /* DEVICE, 4096 bytes, or NULL */
+    int pitch, h, w;
+    int layout, bits, pattern, reserved;   /* reserved = 0 */
+    uint16_t black[4], gain[4];            /* per cell k */
+    int16_t ccm[9], pad;                   /* pad = 0 */
+} rtm3d_raw_src;
+
+/* HOST helpers (no device access).
+ * rtm3d_raw_src_layout: the bytes of a row (the least pitch) and the rows of the plane of a layout at a size.
+ * rtm3d_frames_demosaic_plan: the schedule rtm3d_frames_demosaic gives a batch - the very numbers the launcher uses, it calls
+ * the same code; out[(B + 31) / 32] receives one entry per chunk.  A frame is cut into tiles of tile_w x tile_h pixels; a
+ * workgroup of `threads` stages its tile with `halo` more samples on every side (after steps 1-2, folded) and then every
+ * thread writes 8 pixels of 2 consecutive rows.  Workgroup t of grid row i (frame first + i) takes tile t % tiles_x of tile
+ * row t / tiles_x, tiles_x = ceil(w / tile_w), and leaves when t >= the frame's own number of tiles.  tiles is the largest of
+ * the chunk, grid_x = tiles, grid_y = count.  The sources are validated as by rtm3d_frames_demosaic (destinations aside).
+ * rtm3d_frames_demosaic_check: every refusal of rtm3d_frames_demosaic, without a launch.                                */
+int rtm3d_raw_src_layout(int layout, int bits, int h, int w, int* min_pitch, int* rows);
+typedef struct rtm3d_demosaic_plan {
+    int first, count;                      /* frames first .. first + count - 1 */
+    int tile_w, tile_h, halo;              /* 128 x 32 pixels, 2 samples around them (both methods) */
+    int threads;                           /* per workgroup */
+    int tiles;                             /* tiles of the chunk's largest frame */
+    int grid_x, grid_y;
+} rtm3d_demosaic_plan;
+int rtm3d_frames_demosaic_plan(int B, const rtm3d_raw_src* h_src, int method, rtm3d_demosaic_plan* out);
+int rtm3d_frames_demosaic_check(int B, const rtm3d_raw_src* h_src, uint8_t* const* h_dst, int method, int dst_order);
+
+/* The demosaic: h_src[B] and h_dst[B] are HOST arrays, h_dst[b] a DEVICE pointer to h * w * 3 packed bytes.  Frames of
+ * different sizes, layouts and patterns may share a chunk.  Stream-ordered.                                              */
+int rtm3d_frames_demosaic(void* stream, int B, const rtm3d_raw_src* h_src, uint8_t* const* h_dst, int method, int dst_order);
+
+/* One detect step of an engine fed by raw sensor frames, the twin of rtm3d_engine_detect_frames_src: rtm3d_frames_demosaic
+ * into h_packed[B] (DEVICE buffers of h * w * 3 bytes, which hold the packed frames afterwards), then
+ * rtm3d_engine_detect_frames on h_packed with the (h, w) of the sources.  Same workspace, same rtm3d_engine_set_frame_params,
+ * stream-ordered with no host synchronisation; everything either step would refuse is refused before the first launch.   */
+int rtm3d_engine_detect_frames_raw(rtm3d_ctx* ctx, void* stream, const rtm3d_raw_src* h_src, uint8_t* const* h_packed,
+                                   int method, int dst_order, const double* d_K_camera, float* d_rec, double* d_kitti,
+                                   void* d_workspace);
+
 /* ------------------------------------------------------------------ lens undistortion (csrc/lens.hip, csrc/engine.cpp)
  * Every other entry point takes a frame for a pinhole image described by a 3 x 3 K.  A frame of a real camera is one only
  * after rectification: this section builds rectifying maps on the device and resamples packed frames through them, the stage

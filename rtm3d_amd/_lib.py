@@ -122,6 +122,19 @@ class ConvertPlan(ctypes.Structure):
                 ('runs', c_int), ('grid_x', c_int), ('grid_y', c_int)]
 
 
+class RawSrc(ctypes.Structure):
+    """Mirror of struct rtm3d_raw_src (rtm3d_amd/raw.py)."""
+    _fields_ = [('plane', c_void_p), ('d_tone', c_void_p), ('pitch', c_int), ('h', c_int), ('w', c_int),
+                ('layout', c_int), ('bits', c_int), ('pattern', c_int), ('reserved', c_int),
+                ('black', ctypes.c_uint16 * 4), ('gain', ctypes.c_uint16 * 4), ('ccm', ctypes.c_int16 * 9), ('pad', ctypes.c_int16)]
+
+
+class DemosaicPlan(ctypes.Structure):
+    """Mirror of struct rtm3d_demosaic_plan (one per chunk of 32 frames)."""
+    _fields_ = [('first', c_int), ('count', c_int), ('tile_w', c_int), ('tile_h', c_int), ('halo', c_int), ('threads', c_int),
+                ('tiles', c_int), ('grid_x', c_int), ('grid_y', c_int)]
+
+
 class LensMapC(ctypes.Structure):
     """Mirror of struct rtm3d_lens_map (rtm3d_amd/lens.py)."""
     _fields_ = [('d_map', c_void_p), ('ho', c_int), ('wo', c_int), ('reserved', c_int)]
@@ -235,6 +248,13 @@ SIGNATURES = {
     'rtm3d_frames_convert': (c_int, [c_void_p, c_int, ctypes.POINTER(FrameSrc), c_void_p, c_int]),
     'rtm3d_engine_detect_frames_src': (c_int, [c_void_p, c_void_p, ctypes.POINTER(FrameSrc), c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                                c_void_p]),
+    # raw sensor frames: Bayer mosaics to packed frames (rtm3d_amd/raw.py, rtm3d_amd/engine.py)
+    'rtm3d_raw_src_layout': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'rtm3d_frames_demosaic_plan': (c_int, [c_int, ctypes.POINTER(RawSrc), c_int, ctypes.POINTER(DemosaicPlan)]),
+    'rtm3d_frames_demosaic_check': (c_int, [c_int, ctypes.POINTER(RawSrc), c_void_p, c_int, c_int]),
+    'rtm3d_frames_demosaic': (c_int, [c_void_p, c_int, ctypes.POINTER(RawSrc), c_void_p, c_int, c_int]),
+    'rtm3d_engine_detect_frames_raw': (c_int, [c_void_p, c_void_p, ctypes.POINTER(RawSrc), c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]),
     # lens undistortion: rectifying maps and the bilinear remap (rtm3d_amd/lens.py, rtm3d_amd/engine.py)
     'rtm3d_frames_remap_plan': (c_int, [c_int, ctypes.POINTER(LensMapC), ctypes.POINTER(RemapPlan)]),
     'rtm3d_frames_remap_check': (c_int, [c_int, c_void_p, c_void_p, ctypes.POINTER(LensMapC), c_void_p, c_void_p]),
@@ -310,7 +330,7 @@ def check(rc, what=''):
         raise RuntimeError('rtm3d_hip %s failed: %s' % (what, msg.decode() if msg else 'unknown error'))
 
 
-# what the camera-frame wrappers (engine, draw, lens, pixfmt, preprocess) hand to the library
+# what the camera-frame wrappers (engine, draw, lens, pixfmt, raw, preprocess) hand to the library
 def stream_ptr(device):
     """The current stream of ``device`` as the `void* stream` of an entry point."""
     import torch

@@ -372,7 +372,7 @@ struct EngineState {
     const uint16_t* d_lut16 = nullptr;
     std::vector<rtm3d_frame_geom> geom;
     std::vector<int> resized_hw;
-    std::vector<int> src_hw;             // (h, w) of the sources of rtm3d_engine_detect_frames_src
+    std::vector<int> src_hw;             // (h, w) of the sources of rtm3d_engine_detect_frames_src / _raw
     std::vector<int> rect_hw;            // (ho, wo) of the maps of rtm3d_engine_detect_frames_lens
 };
 
@@ -565,6 +565,23 @@ extern "C" int rtm3d_engine_detect_frames_src(rtm3d_ctx* ctx, void* stream, cons
     for (int b = 0; b < I.B; ++b) { st->src_hw[2 * b] = h_src[b].h; st->src_hw[2 * b + 1] = h_src[b].w; }
     if (rtm3d_frame_geometry(I.B, st->src_hw.data(), st->resize_to, I.H, I.W, st->geom.data())) return 1;
     if (rtm3d_frames_convert(stream, I.B, h_src, h_packed, dst_order)) return 1;
+    return rtm3d_engine_detect_frames(ctx, stream, h_packed, st->src_hw.data(), d_K_camera, d_rec, d_kitti, d_workspace);
+}
+
+extern "C" int rtm3d_engine_detect_frames_raw(rtm3d_ctx* ctx, void* stream, const rtm3d_raw_src* h_src, uint8_t* const* h_packed,
+                                              int method, int dst_order, const double* d_K_camera, float* d_rec, double* d_kitti,
+                                              void* d_workspace) {
+    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
+    if (!st) EFAIL("engine_detect_frames_raw: the context was not made by rtm3d_engine_load");
+    if (!h_src || !h_packed || !d_K_camera || !d_rec || !d_workspace) EFAIL("engine_detect_frames_raw: null argument");
+    if (!st->frames) EFAIL("engine_detect_frames_raw: call rtm3d_engine_set_frame_params first");
+    const rtm3d_engine_info& I = st->info;
+    // everything either step would refuse, before the first launch: the sources, then the frames' place on the canvas
+    if (rtm3d_frames_demosaic_check(I.B, h_src, h_packed, method, dst_order)) return 1;
+    st->src_hw.resize((size_t)I.B * 2);
+    for (int b = 0; b < I.B; ++b) { st->src_hw[2 * b] = h_src[b].h; st->src_hw[2 * b + 1] = h_src[b].w; }
+    if (rtm3d_frame_geometry(I.B, st->src_hw.data(), st->resize_to, I.H, I.W, st->geom.data())) return 1;
+    if (rtm3d_frames_demosaic(stream, I.B, h_src, h_packed, method, dst_order)) return 1;
     return rtm3d_engine_detect_frames(ctx, stream, h_packed, st->src_hw.data(), d_K_camera, d_rec, d_kitti, d_workspace);
 }
 

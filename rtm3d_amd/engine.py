@@ -390,7 +390,7 @@ class Engine(object):
             _lib.check(self.lib.rtm3d_forward(self.ctx, _lib.stream_ptr(self.device), ctypes.c_void_p(x.data_ptr()), ptrs), 'forward')
         return tuple(outs)
 
-    # ---- what detect and the three detect_frames* share: the refusals in front of the step, its outputs, and what follows it
+    # ---- what detect and the detect_frames* share: the refusals in front of the step, its outputs, and what follows it
     def _frames_ready(self, who, frames, *maps):
         """Engine.<who> has its workspace and a full batch of frames (and of maps, where it takes them); returns them as lists."""
         B = self.info['B']
@@ -560,6 +560,36 @@ class Engine(object):
                 self.ctx, _lib.stream_ptr(self.device), src, _lib.ptr_array(packed), pixfmt._lookup(pixfmt.ORDERS, order, 'order'),
                 ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(rows.data_ptr()) if kitti else None,
                 ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames_src')
+            self.last_packed = packed
+            panels, ids = self._after_step(rec, rows, K, packed, draw, tracker, nms3d)
+        return self._result(rec, rows, panels, ids)
+
+    def detect_frames_raw(self, sources, K_camera, method='mhc', order='rgb', packed=None, kitti=False, out=None, draw=None, tracker=None,
+                          nms3d=None):
+        """detect_frames fed by raw sensor frames (rtm3d_engine_detect_frames_raw), the twin of detect_frames_src: sources = list
+        of B raw.RawSource (Bayer mosaics as bytes, uint16 or MIPI RAW10 / RAW12, of any sizes that fit the canvas after Resize).
+        One more launch in front of the step - black level, white balance, demosaic, colour matrix, tone table - writes them
+        into ``packed``: B contiguous uint8 (h, w, 3) CUDA tensors, allocated when None and reachable afterwards as
+        ``engine.last_packed``; the step reads those and nothing synchronises.
+        method: 'mhc' | 'bilinear'.  order: 'rgb' | 'bgr', the byte order of the packed pixels = the channel order the
+        checkpoint was trained on.  Every other keyword is detect_frames' and what is returned is what it returns; draw= paints
+        into ``packed``.  For a real lens chain the stages yourself: raw.demosaic(sources) gives the packed frames that
+        detect_frames_lens(frames, maps) takes."""
+        import torch
+        from . import box_overlap, raw
+        nms3d = box_overlap.nms3d_options(nms3d)
+        sources = self._frames_ready('detect_frames_raw', sources)
+        src = raw.c_sources(sources)
+        K = self._intrinsics(K_camera)
+        with torch.cuda.device(self.device):
+            self._check_draw('detect_frames_raw', draw, tracker)
+            packed = raw.packed_buffers(sources, packed)
+            rec, rows = self._outputs(out, kitti)
+            _lib.check(self.lib.rtm3d_engine_detect_frames_raw(
+                self.ctx, _lib.stream_ptr(self.device), src, _lib.ptr_array(packed), raw._lookup(raw.METHODS, method, 'method'),
+                raw._lookup(raw.ORDERS, order, 'order'), ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+                ctypes.c_void_p(rows.data_ptr()) if kitti else None, ctypes.c_void_p(self.frames_workspace.data_ptr())),
+                'engine_detect_frames_raw')
             self.last_packed = packed
             panels, ids = self._after_step(rec, rows, K, packed, draw, tracker, nms3d)
         return self._result(rec, rows, panels, ids)
