@@ -57,11 +57,10 @@ def same_bytes(a, b):
     return all(a[k].tobytes() == b[k].tobytes() for k in ('out', 'box', 'info', 'map', 'n'))
 
 
-@pytest.mark.parametrize('case', CASES, ids=[c['name'] for c in CASES])
-def test_cases_equal_the_yardstick(dev, case):
-    want = rc.reference(case)
+def equals_the_yardstick(case, got, want):
+    """The comparison rule of the rig fusion (shared with tests/test_gpu_rig_regimes.py): asserts it, prints and returns the
+    largest disagreement of a fused box component."""
     assert want['margin'] >= rc.MARGIN
-    got = run_device(case, dev)
     assert np.array_equal(got['n'], want['n']), (case['name'], got['n'], want['n'])
     assert np.array_equal(got['map'], want['map']), (case['name'], np.argwhere(got['map'] != want['map'])[:8].tolist())
     assert np.array_equal(got['info'], want['info']), (case['name'], np.argwhere(got['info'] != want['info'])[:8].tolist())
@@ -75,6 +74,12 @@ def test_cases_equal_the_yardstick(dev, case):
     with np.errstate(invalid='ignore', over='ignore'):
         own = got['box'].astype(np.float32)
     assert np.array_equal(got['out'][..., 24:31].view(np.uint32), own.view(np.uint32)), case['name']
+    return err
+
+
+@pytest.mark.parametrize('case', CASES, ids=[c['name'] for c in CASES])
+def test_cases_equal_the_yardstick(dev, case):
+    equals_the_yardstick(case, run_device(case, dev), rc.reference(case))
 
 
 def test_two_runs_are_bit_identical(dev):
