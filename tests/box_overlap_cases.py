@@ -8,7 +8,9 @@ from tests import box_overlap_ref as ref
 MIN_EDGE_ANGLE = 1e-3          # rad: within a random pair no two edges are closer to parallel than this
 IOU_GAP = 1e-6                 # no pairwise IoU of the NMS inputs lies this close to the threshold
 NMS_THRESH = {'bev': 0.5, '3d': 0.4}
-NMS_SHAPES = (100, 7, 130)     # the shipped topk; less than a wave; bit rows that cross 64 and 128
+NMS_SHAPES = (100, 7, 130)     # the shipped topk; less than a wave; slots past 128.  In CANDIDATES (the bit rows are indexed by
+#                                candidate number, not slot) these reach 66 / 66, 6 / 0 and 78 / 84 per image: no candidate >= 84, words
+#                                3 .. 7 of a bit row never set.  tests/box_overlap_regimes.py holds the cases up to 256 candidates.
 
 
 def _shift(box, dx_local, dz_local, dy=0.0):
