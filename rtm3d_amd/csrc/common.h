@@ -118,6 +118,32 @@ struct SoftmaxKArgs {
     int chunks, rows_per_chunk;    // reduce pass: one workgroup per (u, image, chunk of rows)
     int apply_chunks, apply_rows, xsplit, seg_w;   // apply pass: one workgroup per (image, chunk of rows, column segment)
     int partial_chunks;            // > 0: `partial` was written by the producers' epilogues with this many chunks per image
+    int stats_only;                // 1: stop behind the combine pass - the apply pass runs in the epilogue of the conv that makes z_in (ApplyFoldArgs)
+};
+
+// One element of the fusion's apply pass: acc + f * exp(f - M) / S with the outer product and sum as ONE fused multiply-add and
+// exp(f - M) * invS a product of its own - what the default contraction made of `acc += f * (__expf(f - M) * invS)` in the apply
+// kernel (pool_softmax.hip: v_pk_fma_f32).  Spelled out, because the contraction is the compiler's choice per use: in the conv
+// epilogue that stands in for the apply kernel (conv_mfma256.hip, ApplyFoldArgs) it paired the products of two maps into a
+// v_pk_mul_f32 and ADDED them, unfused, in 224 of 768 places.  Both kernels go through this helper, map after map from
+// acc = (float)z_in, and round once: the same bits.  (The apply kernel's ISA with the helper: the same instructions, opcode for
+// opcode, plus one s_waitcnt, in another register allocation and order; 0.455 ms against 0.454 at bs = 32.)
+__device__ __forceinline__ float softmax_apply_elem(float acc, float f, float M, float invS) {
+    return __builtin_fmaf(f, __expf(f - M) * invS, acc);
+}
+
+// The apply pass of a softmax fusion run in the epilogue of the persistent conv256 kernel that computes z_in: the tile is rounded
+// to the fp16 values z_in would hold and z_out = z_in + sum_i u_i * exp(u_i - M_i) / S_i is stored instead (every tensor has 256
+// channels; stats = SoftmaxKArgs.stats of the fusion, written by its combine pass in front of this launch).
+struct ApplyFoldArgs {
+    // every map as the address of channel 0 of pixel (0, 0) of image 0 (the border is folded in) and its image / row pitch in BYTES;
+    // byte offsets inside a map fit 32 bits (the recorder keeps larger tensors off the fold)
+    const f16* u[3];
+    f16* z_out;
+    const float* stats;            // [n_u][B][256][2] (max, 1/sum)
+    int n_u, B;
+    uint32_t u_img[3], u_row[3];
+    uint32_t z_img, z_row;
 };
 
 // Workgroup b of an n-workgroup launch runs on XCD b % 8 (round-robin dispatch).  Index of the work item it should take so that
@@ -228,6 +254,8 @@ hipError_t launch_conv_headout(const HeadOutArgs& a, hipStream_t s);
 hipError_t launch_conv_mfma(const ConvKArgs& a, int bn_tile, int groups, int epi_nchw, hipStream_t s);
 hipError_t launch_conv_mfma_deep(const ConvKArgs& a, int bn_tile, int groups, unsigned int* tile_ctr, hipStream_t s);
 hipError_t launch_conv_mfma256(const ConvKArgs& a, int groups, unsigned int* tile_ctr, float* stat_out, hipStream_t s);
+// the same conv on the generic persistent kernel with a softmax fusion's apply pass in its epilogue (a.out is not written)
+hipError_t launch_conv_mfma256_apply(const ConvKArgs& a, int groups, const ApplyFoldArgs& f, unsigned int* tile_ctr, hipStream_t s);
 // the kernel launch_conv_mfma256 runs a conv on (conv_mfma256_route; ht: the halo route's packed taps, may be null): one tile per
 // workgroup (conv_mfma256_kernel), the generic persistent kernel, the halo-tile kernel, the dilation row-sub-lattice kernel
 enum Conv256Route { C256_ONE_TILE, C256_PERSISTENT, C256_HALO, C256_LATTICE };

@@ -33,6 +33,15 @@
 // j * 128 + wc * 32 + c * 16 + frow of every 256-row K-tile holds channel wc * 64 + frow * 4 + j * 2 + c, re-swizzled for its new
 // row (conv_mfma256_permute_weights; made once per op by rtm3d_op_conv's admission - the weights are constant for the life of a
 // plan).  Reading the permuted rows from the unpermuted image instead would put the 16 lanes of a fragment on two swizzle keys.
+//
+// The apply fold (RES >= 2 of the persistent kernel, launch_conv_mfma256_apply): the apply pass of the neck's spatial-softmax fusion in
+// the epilogue of the launch that computes the fusion's z_in.  Built: the epilogue mode (see the kernel), for 1-3 maps, one group or
+// the sub-pixel phases of a transposed conv, statistics per tile or - in tiles that straddle images - per pixel; the bytes of the
+// two-kernel path (tests/test_gpu_apply_fold.py).  Measured (profiles/apply_fold_ab.txt, bs = 32 DLA-34, same box, interleaved): the
+// launch 457.5 -> 708.1 us, the 455.6 us apply kernel gone, the default bench.py 12.342-12.352 -> 12.156-12.199 ms/step, 0.58 GB less
+// fetched and 0.50 GB less written per forward; the load batch (C256_APPLY_RUNS).  Not measured: the epilogue's loads and exponentials
+// apart (the launch grew by 0.25 ms against an estimate of 0.19), in-kernel stamps of the new epilogue, small batches.  Not built:
+// the loads under the last K-tiles (no registers), the same epilogue in the halo kernel.
 #include <string.h>
 #include "common.h"
 
@@ -436,8 +445,31 @@ __global__ __launch_bounds__(512) void conv_mfma256_kernel(const ConvKArgs a) {
 
 // XNT = 1: a 1x1 conv with one channel tile reads every input byte once - its pixel operand goes through a non-temporal DMA
 // (see conv_mfma.hip).  A template parameter, not a run-time flag: as a flag it cost the head convs 12 SGPRs and 20 B of scratch.
+// RES = 2 / 3 / 4: the apply pass of a softmax fusion over 1 / 2 / 3 maps runs in the epilogue (ApplyFoldArgs, common.h): the tile is
+// rounded to the fp16 values the conv would store (bias, ReLU flag) and z_out = that + sum_i u_i * exp(u_i - M_i) / S_i goes to
+// af.z_out; a.out is not written.  One channel tile of 256 at output channel offset 0; groups as for any launch - the four sub-pixel
+// phases of a transposed conv (out_scale 2) are four groups that write z_out's pixels between them (launch_conv_mfma256_apply).
+// `af` is NOT read as a kernel parameter: its scalars (five per map) would be loaded in front of the tile loop and parked in
+// VGPR lanes across the K loop, which is full (tests/test_isa_guard.py caps the parked scalars).  The epilogue reads the struct
+// from the kernel-argument segment through an address the compiler cannot see through, once per tile.
+struct C256PersistentKernargs { ConvKArgs a; int groups, nbias; unsigned int* tile_ctr; int one_list; ApplyFoldArgs af; };   // the kernel's parameter list
+#define CONST_AS __attribute__((address_space(4)))
+// Four-pixel runs of a lane per load batch of the fused apply epilogue (of its 4 per tile half).  Same box, per-op pass at bs = 32,
+// the fusion's slot (combine pass + fused conv), two rounds: 1 run 0.685 / 0.699 ms | 2 runs 0.724 / 0.726 | 4 (a half at a time, as
+// the residual path loads) spills 82 VGPRs, not run.  -DC256_T_APPLY_PLAIN (ordinary instead of non-temporal loads, 2 runs): 0.736 / 0.747.
+#ifndef C256_APPLY_RUNS
+#define C256_APPLY_RUNS 1
+#endif
+#ifdef C256_T_APPLY_PLAIN                // (same-box A/B only: the u tiles through ordinary loads)
+#define C256_APPLY_LOAD(p) (*(p))
+#else
+#define C256_APPLY_LOAD(p) __builtin_nontemporal_load(p)
+#endif
 template <int RES, int XNT>
-__global__ __launch_bounds__(512) void conv_mfma256_persistent_kernel(const ConvKArgs a, const int groups, const int nbias, unsigned int* tile_ctr, const int one_list) {
+__global__ __launch_bounds__(512) void conv_mfma256_persistent_kernel(const ConvKArgs a, const int groups, const int nbias, unsigned int* tile_ctr, const int one_list,
+                                                                      const ApplyFoldArgs af) {
+    constexpr int NU = RES >= 2 ? RES - 1 : 0, NUA = NU ? NU : 1;
+    constexpr bool ADD_RES = RES == 1;
     __shared__ __attribute__((aligned(16))) f16 lds[2 * BUF_ELEMS + HALF_ELEMS];
     __shared__ __attribute__((aligned(16))) float lds_bias[CONV256_MAX_BIAS + 4];   // + two ticket words
 #ifdef C256_STAMPS
@@ -671,7 +703,109 @@ __global__ __launch_bounds__(512) void conv_mfma256_persistent_kernel(const Conv
         TSTAMP(1)
 
         // ---- epilogue of the current tile: 32 independent 8-byte stores (behind the half's residual loads, RES)
-        {
+        if constexpr (NU > 0) {
+            // ---- the apply pass of the softmax fusion instead (see the kernel's head).  Per four-pixel run of the lane (C256_APPLY_RUNS;
+            // a half at a time, as the residual is loaded, does not fit beside the 128 accumulators): the run's 4 x NU tile loads in
+            // the residual's shape (8 bytes per lane, lanes 16 k .. 16 k + 15 = one pixel's 128 bytes) with each map's own pitch and
+            // border, all in front of the run's first store; 32 stores per tile as before, every load retired before the store
+            // that needs it, so the K loop's counted waits hold as they do for RES = 1.  Non-temporal loads: every u byte is read once.
+            uintptr_t kp = (uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(C256PersistentKernargs, af);
+            asm volatile("" : "+s"(kp));
+            const CONST_AS ApplyFoldArgs& F = *(const CONST_AS ApplyFoldArgs*)kp;
+            // the lane's place in its fragment once more, from a value the K loop keeps anyway and through an asm the compiler cannot
+            // hoist: what the epilogue derives from it is made here, per tile, instead of living in VGPRs across the (full) K loop
+            uint32_t tid16 = wvoff;
+            asm volatile("" : "+v"(tid16));
+            const int frow_e = (int)(tid16 >> 4) & 15, fk_e = (int)(tid16 >> 8) & 3;
+            const uint32_t cb2 = (uint32_t)(wc * 64 + frow_e * 4) * 2u;            // this lane's four channels, BYTES (nt_c = 0, out_coff = 0)
+            const int g_oy = a.g[gi_c].out_oy, g_ox = a.g[gi_c].out_ox;          // iteration pixel (y, x) -> map pixel (y * out_scale + g_oy, x * out_scale + g_ox)
+            // (max, 1 / sum) of this lane's four channels of map ui in image n: (M0 S0 M1 S1) (M2 S2 M3 S3)
+            auto load_stats = [&](int ui, int n, f32x4 (&st)[2]) {
+                const GLB_AS f32x4* sp = (const GLB_AS f32x4*)((uintptr_t)F.stats + ((size_t)(ui * F.B + n) * 2048u + cb2 * 4u));
+                st[0] = sp[0]; st[1] = sp[1];
+            };
+            auto fused = [&](int i, int p, int e, const f16x4 (&uv)[NUA], const f32x4 (&st)[NUA][2]) -> f16x4 {
+                const f32x4 vv = {acc[i][0][0][p][e], acc[i][0][1][p][e], acc[i][1][0][p][e], acc[i][1][1][p][e]};
+                f16x4 h = {(f16)vv[0], (f16)vv[1], (f16)vv[2], (f16)vv[3]};
+                h = __builtin_elementwise_max(h, lo4);                           // the fp16 value z_in would hold
+                f16x4 o;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float z = (float)h[k];
+#pragma unroll
+                    for (int ui = 0; ui < NU; ++ui) z = softmax_apply_elem(z, (float)uv[ui][k], st[ui][k >> 1][(k & 1) * 2], st[ui][k >> 1][(k & 1) * 2 + 1]);
+                    // the sum rounds to fp32 and THEN to fp16, as in the apply kernel (v_pk_fma_f32, v_cvt_pk_f16_f32).  Left to itself the
+                    // compiler folds the last multiply-add and the conversion of the pixel-at-a-time path into v_fma_mixlo_f16, which
+                    // rounds once: one fp16 ulp off in about one value of 10^4 (seen on the GPU: max |diff| 2^-11 on a 24 x 40 map)
+                    asm volatile("" : "+v"(z));
+                    o[k] = (f16)z;
+                }
+                return o;
+            };
+            const int mfirst = mt_c * 256, mlast = mfirst + 255 < a.M ? mfirst + 255 : a.M - 1;
+            const int n_tile = div_small_q(mfirst, a.HmWm, rcp_hw);
+            if (mlast < (n_tile + 1) * a.HmWm) {
+                // the whole tile lies in one image (always, when 256 divides H * W): its statistics once per tile, the image's
+                // offset in the scalar base of every map
+                f32x4 st[NUA][2];
+                uintptr_t ub[NUA];
+#pragma unroll
+                for (int ui = 0; ui < NU; ++ui) { load_stats(ui, n_tile, st[ui]); ub[ui] = (uintptr_t)F.u[ui] + (size_t)n_tile * F.u_img[ui]; }
+                const uintptr_t zb = (uintptr_t)F.z_out + (size_t)n_tile * F.z_img;
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int ph = 0; ph < 4 / C256_APPLY_RUNS; ++ph) {
+                        uint32_t zo[C256_APPLY_RUNS][4];
+                        f16x4 uv[C256_APPLY_RUNS][4][NUA];
+#pragma unroll
+                        for (int pq = 0; pq < C256_APPLY_RUNS; ++pq) {
+                            // rows past M were staged from pixel M-1 and hold its result: the same value stored twice (no input aliases z_out)
+                            const int m0 = mt_c * 256 + i * 128 + wp * 64 + (ph * C256_APPLY_RUNS + pq) * 16 + fk_e * 4;
+                            const int m = m0 < a.M ? m0 : a.M - 1;
+                            int n = n_tile;
+                            const int rem = m - n * a.HmWm;
+                            int y = div_small_q(rem, a.Wm, rcp_w), x = rem - y * a.Wm;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                if (e) c256_next_pixel(n, y, x, m0 + e < a.M, a.Wm, Hm);
+                                const uint32_t oy = (uint32_t)(y * a.out_scale + g_oy), xc = (uint32_t)(x * a.out_scale + g_ox) * 512u + cb2;
+                                zo[pq][e] = oy * F.z_row + xc;
+#pragma unroll
+                                for (int ui = 0; ui < NU; ++ui)
+                                    uv[pq][e][ui] = C256_APPLY_LOAD((const GLB_AS f16x4*)(ub[ui] + (oy * F.u_row[ui] + xc)));
+                            }
+                        }
+#pragma unroll
+                        for (int pq = 0; pq < C256_APPLY_RUNS; ++pq)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                *(GLB_AS f16x4*)(zb + zo[pq][e]) = fused(i, ph * C256_APPLY_RUNS + pq, e, uv[pq][e], st);
+                    }
+            } else {
+                // the tile straddles images (H * W is no multiple of 256): statistics per pixel, one pixel at a time
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int p = 0; p < 4; ++p)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int m0 = mt_c * 256 + i * 128 + wp * 64 + p * 16 + fk_e * 4 + e;
+                            const int m = m0 < a.M ? m0 : a.M - 1;
+                            const int n = div_small_q(m, a.HmWm, rcp_hw), rem = m - n * a.HmWm;
+                            const int y = div_small_q(rem, a.Wm, rcp_w), x = rem - y * a.Wm;
+                            const uint32_t oy = (uint32_t)(y * a.out_scale + g_oy), xc = (uint32_t)(x * a.out_scale + g_ox) * 512u + cb2;
+                            f32x4 st[NUA][2];
+                            f16x4 uv[NUA];
+#pragma unroll
+                            for (int ui = 0; ui < NU; ++ui) {
+                                load_stats(ui, n, st[ui]);
+                                uv[ui] = C256_APPLY_LOAD((const GLB_AS f16x4*)((uintptr_t)F.u[ui] + ((uint32_t)n * F.u_img[ui] + oy * F.u_row[ui] + xc)));
+                            }
+                            *(GLB_AS f16x4*)((uintptr_t)F.z_out + ((uint32_t)n * F.z_img + oy * F.z_row + xc)) = fused(i, p, e, uv, st);
+                        }
+            }
+        } else {
             const ConvGroupArgs& g = a.g[gi_c];
             const int cbase = nt_c * 256 + wc * 64 + frow * 4;
 #pragma unroll
@@ -691,7 +825,7 @@ __global__ __launch_bounds__(512) void conv_mfma256_persistent_kernel(const Conv
                         if (e) c256_next_pixel(n, y, x, m0 + e < a.M, a.Wm, Hm);
                         const int oy = y * a.out_scale + g.out_oy, ox = x * a.out_scale + g.out_ox;
                         opix[p][e] = ((size_t)(n * a.out_Hp + oy + a.out_P) * a.out_Wp + ox + a.out_P) * a.out_C + g.out_coff + cbase;
-                        if (RES) rv[p][e] = *(const f16x4*)(a.res + ((size_t)(n * a.res_Hp + oy + a.res_P) * a.res_Wp + ox + a.res_P) * a.res_C + g.res_coff + cbase);
+                        if (ADD_RES) rv[p][e] = *(const f16x4*)(a.res + ((size_t)(n * a.res_Hp + oy + a.res_P) * a.res_Wp + ox + a.res_P) * a.res_C + g.res_coff + cbase);
                     }
                 }
 #pragma unroll
@@ -699,7 +833,7 @@ __global__ __launch_bounds__(512) void conv_mfma256_persistent_kernel(const Conv
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         f32x4 vv = {acc[i][0][0][p][e], acc[i][0][1][p][e], acc[i][1][0][p][e], acc[i][1][1][p][e]};   // (bias: the accumulators started at it)
-                        if (RES) {
+                        if (ADD_RES) {
                             const f16x4 r = rv[p][e];
                             vv[0] += (float)r[0]; vv[1] += (float)r[1]; vv[2] += (float)r[2]; vv[3] += (float)r[3];
                         }
@@ -778,6 +912,38 @@ Conv256Route conv_mfma256_route(const ConvKArgs& a, int groups, HaloTaps* ht) {
     return C256_PERSISTENT;
 }
 
+template <int RES, int XNT>
+static hipError_t launch_persistent(const ConvKArgs& a, int groups, int nbias, unsigned int* tile_ctr, const ApplyFoldArgs& af, hipStream_t s) {
+    // One workgroup per CU even when there are fewer tiles (level 4: 240): with exactly as many workgroups as tiles ONE CU held
+    // by another stream's workgroup costs the launch a second round; the spare workgroups find the list empty and leave.
+    // Launches of at most one round take one list for the whole chip (see the kernel).  Round 6, same box, pipelined bs=32
+    // ms/step (the previous batch's 3D decode beside every forward): grid clamped to the tile count, lists per XCD 12.82-12.87 |
+    // + second ticket behind the prologue 12.79-12.86 | + 256 workgroups 12.79-12.84 | + ONE list 12.60-12.63.
+    const int per_xcd = device_cu_count() / 8;
+    const int one_list = (long long)a.MT * a.NT * groups <= device_cu_count() ? 1 : 0;
+    hipLaunchKernelGGL((conv_mfma256_persistent_kernel<RES, XNT>), dim3(per_xcd * 8, 1, 1), dim3(512, 1, 1), 0, s, a, groups, nbias, tile_ctr, one_list, af);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_mfma256_apply(const ConvKArgs& a, int groups, const ApplyFoldArgs& f, unsigned int* tile_ctr, hipStream_t s) {
+    // what the epilogue assumes (the recorder checked it too, and that the groups write every pixel of the map once): the generic
+    // persistent route, one channel tile written from channel 0 of 256-channel maps, no residual
+    if (f.n_u < 1 || f.n_u > 3 || !f.z_out || !f.stats || !tile_ctr || groups < 1 || groups > RT_MAX_GROUPS || a.res || a.NT != 1 || a.cout != 256 ||
+        conv_mfma256_route(a, groups, nullptr) != C256_PERSISTENT)
+        return hipErrorInvalidValue;
+    for (int g = 0; g < groups; ++g) if (a.g[g].out_coff != 0) return hipErrorInvalidValue;
+    const int nbias = conv256_nbias(a, groups);
+    const bool x_once = a.ntaps == 1 && a.in_stride == 1;
+    switch (f.n_u * 2 + (x_once ? 1 : 0)) {
+        case 2: return launch_persistent<2, 0>(a, groups, nbias, tile_ctr, f, s);
+        case 3: return launch_persistent<2, 1>(a, groups, nbias, tile_ctr, f, s);
+        case 4: return launch_persistent<3, 0>(a, groups, nbias, tile_ctr, f, s);
+        case 5: return launch_persistent<3, 1>(a, groups, nbias, tile_ctr, f, s);
+        case 6: return launch_persistent<4, 0>(a, groups, nbias, tile_ctr, f, s);
+        default: return launch_persistent<4, 1>(a, groups, nbias, tile_ctr, f, s);
+    }
+}
+
 hipError_t launch_conv_mfma256(const ConvKArgs& a, int groups, unsigned int* tile_ctr, float* stat_out, hipStream_t s) {
     dim3 block(512, 1, 1);
     HaloTaps ht;
@@ -788,19 +954,11 @@ hipError_t launch_conv_mfma256(const ConvKArgs& a, int groups, unsigned int* til
     if (route == C256_HALO) return launch_conv_mfma256_halo(a, ht, groups, nbias, device_cu_count(), tile_ctr, stat_out, s);
     if (route == C256_LATTICE) return launch_conv_mfma256_lattice(a, groups, nbias, device_cu_count(), tile_ctr, s);
     if (route == C256_PERSISTENT) {
-        // One workgroup per CU even when there are fewer tiles (level 4: 240): with exactly as many workgroups as tiles ONE CU held
-        // by another stream's workgroup costs the launch a second round; the spare workgroups find the list empty and leave.
-        // Launches of at most one round take one list for the whole chip (see the kernel).  Round 6, same box, pipelined bs=32
-        // ms/step (the previous batch's 3D decode beside every forward): grid clamped to the tile count, lists per XCD 12.82-12.87 |
-        // + second ticket behind the prologue 12.79-12.86 | + 256 workgroups 12.79-12.84 | + ONE list 12.60-12.63.
-        const int per_xcd = device_cu_count() / 8;
-        const int one_list = (long long)a.MT * a.NT * groups <= device_cu_count() ? 1 : 0;
-        dim3 grid(per_xcd * 8, 1, 1);
         const bool x_once = !a.res && a.ntaps == 1 && a.NT == 1 && a.in_stride == 1;
-        if (a.res) hipLaunchKernelGGL((conv_mfma256_persistent_kernel<1, 0>), grid, block, 0, s, a, groups, nbias, tile_ctr, one_list);
-        else if (x_once) hipLaunchKernelGGL((conv_mfma256_persistent_kernel<0, 1>), grid, block, 0, s, a, groups, nbias, tile_ctr, one_list);
-        else hipLaunchKernelGGL((conv_mfma256_persistent_kernel<0, 0>), grid, block, 0, s, a, groups, nbias, tile_ctr, one_list);
-        return hipGetLastError();
+        const ApplyFoldArgs none = {};
+        if (a.res) return launch_persistent<1, 0>(a, groups, nbias, tile_ctr, none, s);
+        if (x_once) return launch_persistent<0, 1>(a, groups, nbias, tile_ctr, none, s);
+        return launch_persistent<0, 0>(a, groups, nbias, tile_ctr, none, s);
     }
     const int mt8 = (a.MT + 7) / 8 * 8;
     dim3 grid(mt8 * a.NT, groups, 1);

@@ -3,6 +3,12 @@
 //   softmax fusion : models/nets/keypoint_fpn_fusion.py:60-69
 //                    z += u * softmax(u over H*W) per (image, channel), for up to three u.
 // All accesses are 8- or 16-byte vectors along the contiguous channel axis.
+// The apply fold: where the conv launch that computes z_in can take the apply pass into its epilogue (runtime.hip,
+// rtm3d_op_softmax_fuse; conv_mfma256.hip, RES >= 2), launch_softmax_fuse stops behind the combine pass (SoftmaxKArgs.stats_only) and
+// softmax_apply_kernel is not launched; the geometry of the passes that still run is unchanged.  Both forms compute an element with
+// softmax_apply_elem (common.h).  Measured (profiles/apply_fold_ab.txt, bs = 32): the apply kernel, 0.456 ms, against + 0.251 ms on
+// the conv launch; the apply kernel with the helper 0.455 ms against 0.454 before (its ISA: the same instructions, one s_waitcnt
+// more, another register allocation and order).  Not measured: the fold at small batches.
 #include "common.h"
 
 __global__ __launch_bounds__(256) void maxpool_kernel(const PoolKArgs a) {
@@ -178,7 +184,7 @@ __global__ __launch_bounds__(256) void softmax_apply_kernel(const SoftmaxKArgs a
 #pragma unroll
                     for (int ui = 0; ui < NU; ++ui) {
                         const float f = (float)v[k][ui][e];
-                        acc += f * (__expf(f - M[ui][e]) * invS[ui][e]);
+                        acc = softmax_apply_elem(acc, f, M[ui][e], invS[ui][e]);
                     }
                     o[e] = (f16)acc;
                 }
@@ -194,6 +200,8 @@ hipError_t launch_softmax_fuse(const SoftmaxKArgs& a, hipStream_t s) {
     // pass 1 is skipped when the producing convolutions emitted the partials from their epilogues
     if (a.partial_chunks <= 0) hipLaunchKernelGGL(softmax_reduce_kernel, dim3(a.chunks, a.B, a.n_u), dim3(256), 0, s, a);
     hipLaunchKernelGGL(softmax_combine_kernel, dim3(a.B, a.n_u, a.C / 64), dim3(1024), 0, s, a);
+    // the apply pass runs in the epilogue of the conv that computes z_in (runtime.hip, rtm3d_op_softmax_fuse): statistics only
+    if (a.stats_only) return hipGetLastError();
     if (a.n_u == 3) hipLaunchKernelGGL(softmax_apply_kernel<3>, dim3(a.apply_chunks, a.B, 1), dim3(256), 0, s, a);
     else if (a.n_u == 2) hipLaunchKernelGGL(softmax_apply_kernel<2>, dim3(a.apply_chunks, a.B, 1), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(softmax_apply_kernel<1>, dim3(a.apply_chunks, a.B, 1), dim3(256), 0, s, a);

@@ -4,6 +4,7 @@
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <string>
 #include <vector>
@@ -47,6 +48,15 @@ struct Op {
     ConvKArgs conv; int groups, bn_tile, epi_nchw, out_slot;
     int ticket_slot = -1;           // persistent kernels: index of this op's ticket counter (ticket_ctr)
     float* stat_out = nullptr;      // softmax partials written by this conv's epilogue (halo kernel), or null
+    // fp16 tensor ids this op reads (input, residual, space-to-depth source, u, in-place operand) and writes: what the apply fold
+    // (rtm3d_op_softmax_fuse) needs to know who else touches z_in
+    std::vector<int> reads, writes;
+    // apply fold: a deferred conv launches nothing in its own slot - the softmax op that took it in launches it, in its fused form,
+    // behind its own combine pass; that op names it in `fold_conv` (-1: none) and carries the epilogue's arguments in `af`
+    bool deferred = false;
+    int fold_conv = -1;
+    ApplyFoldArgs af;
+    double own_flops = 0, own_bytes = 0;   // flops / bytes of the op on its own (restored when a fold is undone)
     Tensor input4;                  // OP_INPUT4: the NHWC4 tensor the caller's fp32 batch is converted into
     bool input4_unread = false;     // OP_INPUT4: its only reader is the fused stem, which reads the fp32 batch itself: no launch
     PoolKArgs pool;
@@ -265,6 +275,27 @@ static void* get_blob(rtm3d_ctx* ctx, int id, size_t* bytes) {
     if (id < 0 || id >= (int)ctx->blobs.size()) return nullptr;
     if (bytes) *bytes = ctx->blob_bytes[id];
     return ctx->blobs[id];
+}
+
+// Undoes the apply fold of softmax op `si` (rtm3d_op_softmax_fuse): both ops launch in their own slots again.
+static void undo_apply_fold(rtm3d_ctx* ctx, int si) {
+    Op& sm = ctx->ops[si];
+    if (sm.fold_conv < 0) return;
+    Op& cv = ctx->ops[sm.fold_conv];
+    cv.deferred = false; cv.flops = cv.own_flops; cv.bytes = cv.own_bytes;
+    sm.fold_conv = -1; sm.sm.stats_only = 0; sm.flops = sm.own_flops; sm.bytes = sm.own_bytes;
+}
+
+// Appends `op` to the plan with the fp16 tensors it reads and writes (ids < 0: none).  A folded fusion never writes its z_in: an
+// op recorded later that reads that tensor puts the two ops back into their own slots.
+static void record_op(rtm3d_ctx* ctx, Op& op, std::initializer_list<int> reads, std::initializer_list<int> writes) {
+    for (int id : reads) if (id >= 0) op.reads.push_back(id);
+    for (int id : writes) if (id >= 0) op.writes.push_back(id);
+    for (size_t i = 0; i < ctx->ops.size(); ++i)
+        if (ctx->ops[i].fold_conv >= 0)
+            for (int id : op.reads)
+                if (id == ctx->ops[i].reads[0]) undo_apply_fold(ctx, (int)i);      // (reads[0] of a softmax op is its z_in)
+    ctx->ops.push_back(op);
 }
 
 // Admission of one rtm3d_op_conv launch per kernel id: the checks of what that kernel takes, its tile counts, weight / bias
@@ -564,7 +595,7 @@ extern "C" int rtm3d_op_conv(rtm3d_ctx* ctx, const rtm3d_conv_desc* d) {
         ctx->stat_tensor[stat_slot] = d->out_tensor;
         op.stat_out = ctx->stat_buf + (size_t)stat_slot * in->B * chunks * 256 * 2;
     }
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {d->in_tensor, d->res_tensor}, {out ? d->out_tensor : -1, s2d_id});
     return 0;
 }
 
@@ -656,7 +687,7 @@ extern "C" int rtm3d_op_quant_mx8(rtm3d_ctx* ctx, int in_tensor, int in_coff, in
     a.nblk = channels / 32;
     op.flops = 0;
     op.bytes = (double)in->B * in->H * in->W * channels * (2.0 + 1.0 + 1.0 / 32);
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {in_tensor}, {});
     return 0;
 }
 
@@ -717,7 +748,7 @@ extern "C" int rtm3d_op_conv_mx8(rtm3d_ctx* ctx, const rtm3d_conv_mx8_desc* d) {
     for (int t = 0; t < d->ntaps; ++t) a.tap_pix[t] = d->tap_dy[t] * in->Wp + d->tap_dx[t];
     op.flops = 2.0 * (double)M * d->groups * d->cin * d->ntaps * d->cout;
     op.bytes = (double)M * d->groups * (d->cin * (1.0 + 1.0 / 32) + d->cout * (of ? 2.0 : 1.0 + 1.0 / 32)) + (double)(wb + sb);
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {}, {of ? d->out_tensor : -1});
     return 0;
 }
 
@@ -728,7 +759,7 @@ extern "C" int rtm3d_op_input_nhwc4(rtm3d_ctx* ctx, int out_tensor) {
     op.kind = OP_INPUT4; op.name = "nchw_f32_to_nhwc4_f16";
     op.input4 = *o;
     op.flops = 0; op.bytes = (double)o->B * o->H * o->W * (12.0 + 8.0);
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {}, {out_tensor});
     return 0;
 }
 
@@ -770,7 +801,7 @@ extern "C" int rtm3d_op_stem_fused(rtm3d_ctx* ctx, int x4_tensor, int out_tensor
     // the reference layers (3 real input channels): 7x7 3->16, 3x3 16->16 at full resolution, 3x3 16->32 at half
     op.flops = 2.0 * px * (49.0 * 3 * 16 + 9.0 * 16 * 16 + (three ? 9.0 * 16 * 32 / 4 : 0.0));
     op.bytes = px * (8.0 + (three ? 64.0 / 4 : 32.0));           // NHWC4 image in, 16-channel map (or the 32-channel half-res map) out
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {x4_tensor}, {out_tensor});
     return 0;
 }
 
@@ -808,7 +839,7 @@ extern "C" int rtm3d_op_conv32s2_fused(rtm3d_ctx* ctx, int in_tensor, int in_cof
     const double opx = (double)x->B * oc->H * oc->W;
     op.flops = 2.0 * opx * (9.0 * 32 * 64 + 32.0 * 64);
     op.bytes = opx * (4 * 64.0 + 2 * 128.0);                   // 32-channel input once, two 64-channel outputs
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {in_tensor}, {conv_tensor, proj_tensor});
     return 0;
 }
 
@@ -875,7 +906,7 @@ extern "C" int rtm3d_op_conv64_root(rtm3d_ctx* ctx, int in_tensor, int in_coff, 
     const double M = (double)a.M;
     op.flops = 2.0 * M * (9.0 * 64 * 64 + 128.0 * 64);
     op.bytes = 2.0 * M * (64.0 * 2 + (out ? 64.0 : 0.0) + (pool ? 16.0 : 0.0) + (s2d ? 64.0 : 0.0));      // conv input, x1, root output (+ the pooled map, + the second copy)
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {in_tensor, res_tensor}, {out_tensor, pool_tensor, s2d_tensor});
     return 0;
 }
 
@@ -891,7 +922,7 @@ extern "C" int rtm3d_op_patch_mask(rtm3d_ctx* ctx, int tensor, int yx_blob, int 
     op.pm.base = t->base; op.pm.yx = yx; op.pm.n_slots = t->B; op.pm.S = t->H; op.pm.C = t->C;
     op.pm.img_H = img_H; op.pm.img_W = img_W; op.pm.origin = origin;
     op.flops = 0; op.bytes = 0;
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {tensor}, {tensor});
     return 0;
 }
 
@@ -919,7 +950,7 @@ extern "C" int rtm3d_op_headout(rtm3d_ctx* ctx, int in_tensor, int w_blob, int b
     a.tiles_x = (in->W + 31) / 32; a.tiles_y = (in->H + a.tile_rows - 1) / a.tile_rows;
     op.flops = 2.0 * in->B * in->H * in->W * 9.0 * 256.0 * csum;
     op.bytes = (double)in->B * in->H * in->W * (256.0 * nheads * 2 + csum * 4.0);
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {in_tensor}, {});
     return 0;
 }
 
@@ -940,7 +971,7 @@ extern "C" int rtm3d_op_maxpool(rtm3d_ctx* ctx, int in_tensor, int in_coff, int 
     a.ksize = ksize; a.stride = stride; a.pad = pad;
     op.flops = 0;
     op.bytes = 2.0 * in->B * channels * ((double)in->H * in->W + (double)out->H * out->W);
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {in_tensor}, {out_tensor});
     return 0;
 }
 
@@ -960,8 +991,61 @@ extern "C" int rtm3d_op_maxpool_s2d(rtm3d_ctx* ctx, int in_tensor, int in_coff, 
     a.ksize = 0; a.stride = 0; a.pad = 0;                       // ksize 0 = the space-to-depth form: max over the four phase slices of one pixel
     op.flops = 0;
     op.bytes = 2.0 * in->B * channels * 5.0 * (double)out->H * out->W;
-    ctx->ops.push_back(op);
+    record_op(ctx, op, {in_tensor}, {out_tensor});
     return 0;
+}
+
+// The apply fold's peephole: the index of the op whose epilogue can take over the apply pass of the fusion being recorded
+// (z_out = z_in + ...), or -1: record the fusion as it is.  The op must be the last writer of z_in, a conv on the generic persistent
+// 256 x 256 kernel that writes the whole 256-channel map and nothing else - as one group, or as the out_scale^2 sub-pixel phases of
+// a transposed conv, which write every pixel once between them (the DLA-34 plan's z0 launch, kfpn_up3+kfpn_proj3+head2, is
+// four such phases) - and deferring it into the fusion's slot must not change what any op sees.
+// RTM3D_NO_APPLY_FOLD (not 0) in the environment switches the fold off; it is read here, at every call.
+static int apply_fold_producer(rtm3d_ctx* ctx, int z_in, int z_out, int n_u, const int* u_tensors) {
+    const char* off = getenv("RTM3D_NO_APPLY_FOLD");
+    if (off && off[0] && strcmp(off, "0") != 0) return -1;
+    if (z_out == z_in) return -1;
+    Tensor* zi = get_tensor(ctx, z_in);
+    Tensor* zo = get_tensor(ctx, z_out);
+    // the epilogue addresses every map with 32-bit byte offsets
+    if ((zo->elems + 2 * GUARD) * sizeof(f16) >= ((size_t)1 << 32)) return -1;
+    for (int i = 0; i < n_u; ++i) {
+        if (u_tensors[i] == z_out || u_tensors[i] == z_in) return -1;
+        if ((get_tensor(ctx, u_tensors[i])->elems + 2 * GUARD) * sizeof(f16) >= ((size_t)1 << 32)) return -1;
+    }
+    const int n = (int)ctx->ops.size();
+    int ci = -1;
+    for (int i = n - 1; i >= 0 && ci < 0; --i)
+        for (int id : ctx->ops[i].writes) if (id == z_in) ci = i;
+    if (ci < 0) return -1;
+    const Op& cv = ctx->ops[ci];
+    const ConvKArgs& c = cv.conv;
+    if (cv.kind != OP_CONV_MFMA256 || cv.deferred || cv.epi_nchw || cv.stat_out) return -1;
+    if (conv_mfma256_route(c, cv.groups, nullptr) != C256_PERSISTENT) return -1;
+    if (c.res || c.s2d || c.NT != 1 || c.cout != 256 || c.out_C != 256) return -1;
+    // it writes every pixel of z_in exactly once: out_scale^2 groups, one per sub-pixel phase, each over the whole iteration map
+    const int sc = c.out_scale;
+    if (sc < 1 || sc > 2 || cv.groups != sc * sc || c.out != (void*)zi->base || cv.writes.size() != 1) return -1;
+    if (c.Wm * sc != zi->W || c.HmWm * sc * sc != zi->H * zi->W || c.M != zi->B * c.HmWm) return -1;
+    unsigned phases = 0;
+    for (int g = 0; g < cv.groups; ++g) {
+        const ConvGroupArgs& cg = c.g[g];
+        if (cg.out_coff != 0 || cg.out_oy < 0 || cg.out_oy >= sc || cg.out_ox < 0 || cg.out_ox >= sc) return -1;
+        phases |= 1u << (cg.out_oy * sc + cg.out_ox);
+    }
+    if (phases != (1u << (sc * sc)) - 1) return -1;
+    // the fused launch writes z_out while other workgroups still read the conv's input
+    for (int id : cv.reads) if (id == z_out) return -1;
+    // between the conv's slot and this one: nobody reads z_in, nobody writes what the conv reads, nobody touches z_out
+    for (int i = ci + 1; i < n; ++i) {
+        const Op& o = ctx->ops[i];
+        for (int id : o.reads) if (id == z_in || id == z_out) return -1;
+        for (int id : o.writes) {
+            if (id == z_out) return -1;
+            for (int rd : cv.reads) if (id == rd) return -1;
+        }
+    }
+    return ci;
 }
 
 extern "C" int rtm3d_op_softmax_fuse(rtm3d_ctx* ctx, int z_in, int z_out, int n_u, const int* u_tensors) {
@@ -1019,7 +1103,35 @@ extern "C" int rtm3d_op_softmax_fuse(rtm3d_ctx* ctx, int z_in, int z_out, int n_
     // apply pass: read z_in and every u once, write z_out; the stand-alone reduction pass (when the producers did not
     // emit the partials from their epilogues) reads every u once more
     op.bytes = 2.0 * a.B * a.H * a.W * 256.0 * ((emitted ? 1.0 : 2.0) * n_u + 2.0);
-    ctx->ops.push_back(op);
+    op.own_flops = op.flops; op.own_bytes = op.bytes;
+    const int ci = apply_fold_producer(ctx, z_in, z_out, n_u, u_tensors);
+    if (ci >= 0) {
+        // The apply pass runs in the epilogue of the conv that computes z_in (conv_mfma256.hip, RES >= 2).  Every op keeps its index
+        // (per-op timings and stage marks are keyed by it): the conv's slot launches nothing, this slot launches the reduce pass (if the
+        // partials were not emitted), the combine pass and then the conv in its fused form; z_in is neither written nor read.
+        Op& cv = ctx->ops[ci];
+        ApplyFoldArgs& f = op.af;
+        memset(&f, 0, sizeof(f));
+        auto origin = [](Tensor* t) { return t->base + ((size_t)t->P * t->Wp + t->P) * t->C; };
+        for (int i = 0; i < n_u; ++i) {
+            Tensor* u = get_tensor(ctx, u_tensors[i]);
+            f.u[i] = origin(u); f.u_img[i] = (uint32_t)((size_t)u->Hp * u->Wp * 512); f.u_row[i] = (uint32_t)((size_t)u->Wp * 512);
+        }
+        f.z_out = origin(zo); f.z_img = (uint32_t)((size_t)zo->Hp * zo->Wp * 512); f.z_row = (uint32_t)((size_t)zo->Wp * 512);
+        f.stats = a.stats; f.n_u = n_u; f.B = a.B;
+        a.stats_only = 1;
+        op.fold_conv = ci;
+        cv.own_flops = cv.flops; cv.own_bytes = cv.bytes;
+        cv.deferred = true;
+        // what the two slots now do and move: the conv's work is in this slot, less the store and the load of z_in
+        op.flops += cv.flops;
+        op.bytes += cv.bytes - 2.0 * (2.0 * a.B * a.H * a.W * 256.0);
+        cv.flops = 0; cv.bytes = 0;
+    }
+    std::initializer_list<int> none = {};
+    op.reads.push_back(z_in);                          // reads[0] (record_op, undo_apply_fold)
+    for (int i = 0; i < n_u; ++i) op.reads.push_back(u_tensors[i]);
+    record_op(ctx, op, none, {z_out});
     return 0;
 }
 
@@ -1034,7 +1146,9 @@ static int launch_op(rtm3d_ctx* ctx, Op& op, hipStream_t s, const float* d_in, f
                        : launch_conv_mfma(a, op.bn_tile, op.groups, op.epi_nchw, s);
             break;
         }
-        case OP_CONV_MFMA256: e = launch_conv_mfma256(op.conv, op.groups, ctr256, op.stat_out, s); break;
+        case OP_CONV_MFMA256:
+            if (op.deferred) break;                  // launched by the softmax op it is folded into
+            e = launch_conv_mfma256(op.conv, op.groups, ctr256, op.stat_out, s); break;
         case OP_CONV64_HALO: e = launch_conv64_halo(op.conv, ctx->n_cus, ticket_ctr(ctx, op), s); break;
         case OP_CONV64S2_HALO: e = launch_conv64s2_halo(op.conv, ctx->n_cus, ticket_ctr(ctx, op), s); break;
         case OP_CONV64_ROOT: e = launch_conv64_root(op.conv, op.root, ctx->n_cus, ticket_ctr(ctx, op), s); break;
@@ -1056,7 +1170,10 @@ static int launch_op(rtm3d_ctx* ctx, Op& op, hipStream_t s, const float* d_in, f
             break;
         }
         case OP_MAXPOOL: e = launch_maxpool(op.pool, s); break;
-        case OP_SOFTMAX: e = launch_softmax_fuse(op.sm, s); break;
+        case OP_SOFTMAX:
+            e = launch_softmax_fuse(op.sm, s);
+            if (e == hipSuccess && op.fold_conv >= 0) e = launch_conv_mfma256_apply(ctx->ops[op.fold_conv].conv, ctx->ops[op.fold_conv].groups, op.af, ctr256, s);
+            break;
         case OP_PATCH_MASK: e = launch_patch_mask(op.pm, s); break;
         case OP_QUANT_MX8: e = launch_quant_mx8(op.qm, s); break;
         case OP_CONV_MX8: e = launch_conv_mx8(op.cm, op.groups, s); break;
