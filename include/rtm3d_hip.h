@@ -800,6 +800,142 @@ int rtm3d_engine_detect_frames_raw(rtm3d_ctx* ctx, void* stream, const rtm3d_raw
                                    int method, int dst_order, const double* d_K_camera, float* d_rec, double* d_kitti,
                                    void* d_workspace);
 
+/* ------------------------------------------------------------------ JPEG frames (csrc/jpeg_host.cpp, csrc/jpeg.hip, csrc/engine.cpp)
+ * USB and IP cameras deliver MJPEG and recorded driving sets ship JPEG files.  This section turns baseline JPEG byte streams
+ * into the tightly packed uint8 (h, w, 3) frames every other entry point reads.  The work splits where the format splits: the
+ * Huffman decoding is serial per stream and stays on the HOST, threaded over the frames of a batch; dequantisation, the 8 x 8
+ * inverse DCT, chroma upsampling and YCbCr -> RGB - all the arithmetic and all the pixel traffic - run on the DEVICE, one
+ * launch per chunk of 32 frames, descriptors by value, no host synchronisation.  Added in ABI 9 without changing any existing
+ * declaration, struct, plan, engine file or default.  The rule is libjpeg's default decode (the `islow` inverse DCT, "fancy"
+ * upsampling, its fixed-point colour tables), bit for bit: tests/jpeg_ref.py restates it in numpy and tests/golden/jpeg_cases.npz
+ * pins it against libjpeg-turbo's pixels.  (One stated difference: libjpeg replicates a subsampled chroma plane of at most 2
+ * samples in width instead of interpolating it - 4:2:2 and 4:2:0 frames up to 4 pixels wide - while this rule interpolates at
+ * every width; measured against libjpeg-turbo, frames 5 pixels wide and wider agree, narrower subsampled ones need not.)
+ *
+ * ACCEPTED STREAMS: SOI ... EOI with one frame; SOF0, or SOF1 with Huffman coding; sample precision 8; ONE interleaved scan of
+ * all components with Ss = 0, Se = 63, Ah = Al = 0.  1 component (grey; any sampling factors, decoded as 1 x 1), or 3 components
+ * taken as Y Cb Cr with chroma sampling 1 x 1 and luma sampling (H, V) = (1, 1) 4:4:4, (2, 1) 4:2:2 or (2, 2) 4:2:0.  DQT with 8-
+ * or 16-bit entries; DHT anywhere before SOS, a later definition replaces an earlier one; a Huffman table 0 or 1 the stream
+ * never defines is the table of ITU-T T.81 Annex K (K.3 / K.5 for id 0, K.4 / K.6 for id 1), as MJPEG cameras rely on.  DRI /
+ * RSTn with any interval; fill bytes (0xFF) before markers; APPn and COM are skipped, except that an Adobe APP14 segment with
+ * transform 0 is refused.  Bytes after EOI are ignored; a missing EOI after a complete scan is accepted.
+ * REFUSED, each with a message that names the reason (and, through the batch entry points, the frame; a refused call has
+ * launched nothing): progressive (SOF2), lossless, hierarchical or arithmetic coding; 12-bit precision; 2 or 4 components; any
+ * other sampling, 1 x 2 included; several scans; a quantisation table that was never defined, a Huffman table 2 or 3 that was
+ * never defined; a Huffman code that is not in its table; a run that passes coefficient 63; entropy-coded data that ends before
+ * the last MCU; a restart marker that is missing or out of sequence; h or w of 0 or above 16384; a segment length that runs
+ * past the end of the buffer.
+ *
+ * THE COEFFICIENT BUFFER of a frame (int16, what rtm3d_jpeg_entropy_decode writes and the device stage reads):
+ *   [0, 192)      three quantisation tables of 64 uint16 in natural order k = 8 v + u, table c that of component c (zero when
+ *                 the frame has no such component);
+ *   then the planes Y, Cb, Cr (grey: Y alone).  The block grid of component c is padded to whole MCUs: bw_c = mcus_x * H_c,
+ *   bh_c = mcus_y * V_c with mcus_x = ceil(w / (8 Hmax)), mcus_y = ceil(h / (8 Vmax)).  Block (bx, by) starts at
+ *   (by * bw_c + bx) * 64 of its plane and holds its 64 coefficients in natural order.  Every offset is a multiple of 64.
+ *   Values are the decoded integers - DC after prediction, the predictor reset at every restart - stored with two's-complement
+ *   wrap.  mode: RTM3D_JPEG_GREY, _444, _422, _420; (h, w, mode) determine the whole layout.
+ *
+ * THE RULE (int32 with two's-complement wrap, >> arithmetic; on a stream an encoder produced nothing wraps).
+ * 1. Dequantise: d[k] = c[k] * q[k].
+ * 2. Inverse DCT.  The one-dimensional pass on x0..x7 with shift s (constants: round(x * 8192) of libjpeg's jidctint):
+ *      z1 = (x2 + x6) * 4433;  t2 = z1 - x6 * 15137;  t3 = z1 + x2 * 6270;  t0 = (x0 + x4) << 13;  t1 = (x0 - x4) << 13;
+ *      t10 = t0 + t3;  t13 = t0 - t3;  t11 = t1 + t2;  t12 = t1 - t2;
+ *      a0 = x7, a1 = x5, a2 = x3, a3 = x1;  z1 = a0 + a3;  z2 = a1 + a2;  z3 = a0 + a2;  z4 = a1 + a3;  z5 = (z3 + z4) * 9633;
+ *      a0 *= 2446;  a1 *= 16819;  a2 *= 25172;  a3 *= 12299;  z1 *= -7373;  z2 *= -20995;
+ *      z3 = z3 * -16069 + z5;  z4 = z4 * -3196 + z5;  a0 += z1 + z3;  a1 += z2 + z4;  a2 += z2 + z3;  a3 += z1 + z4;
+ *      outputs 0..7 = t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3, each (v + 2^(s-1)) >> s.
+ *    Pass 1 runs down every column with s = 11, pass 2 along every row of the result with s = 18; the sample is
+ *    clamp(v + 128, 0, 255).
+ * 3. Each component plane is cut to its real size cw = ceil(w * H_c / Hmax), ch = ceil(h * V_c / Vmax); the chroma of 4:2:2 and
+ *    4:2:0 is upsampled with neighbour indices clamped into that real size (never into the MCU padding):
+ *      4:2:2   o[2i] = (3 p[i] + p[i-1] + 1) >> 2,  o[2i+1] = (3 p[i] + p[i+1] + 2) >> 2;
+ *      4:2:0   output row 2j + k: s[i] = 3 p[j][i] + p[j-1][i] for k = 0, 3 p[j][i] + p[j+1][i] for k = 1; then
+ *              o[2i] = (3 s[i] + s[i-1] + 8) >> 4,  o[2i+1] = (3 s[i] + s[i+1] + 7) >> 4.
+ * 4. Colour: R = y + ((91881 (cr - 128) + 32768) >> 16),  B = y + ((116130 (cb - 128) + 32768) >> 16),
+ *    G = y + ((-22554 (cb - 128) - 46802 (cr - 128) + 32768) >> 16), each clamped to [0, 255]; grey writes y three times.
+ * 5. The three bytes are written R G B (dst_order 0) or B G R (1).  Exactly h * w * 3 bytes are written per frame; the
+ *    destination may be any byte address.
+ *
+ * OUT OF SCOPE: entropy decoding on the device (one lane per restart interval included); progressive, arithmetic, 12-bit, CMYK /
+ * YCCK and 1 x 2 sampling; tolerant decoding of damaged streams (libjpeg paints the missing part grey; here the stream is
+ * refused); EXIF orientation, ICC profiles, JPEG encoding, PNG; decoding straight into the network input or through the lens
+ * map; skipping all-zero blocks by a per-block end index.                                                                 */
+#define RTM3D_JPEG_GREY 0
+#define RTM3D_JPEG_444 1
+#define RTM3D_JPEG_422 2
+#define RTM3D_JPEG_420 3
+typedef struct rtm3d_jpeg_stream_info {
+    int h, w, components, mode;            /* mode: RTM3D_JPEG_* */
+    int restart_interval;                  /* MCUs, 0 = none */
+    int mcus_x, mcus_y;
+    int bw[3], bh[3];                      /* block grid of each component (0 for a component the frame lacks) */
+    int reserved;
+    size_t table_offset[3];                /* 0, 64, 128 */
+    size_t plane_offset[3];                /* in int16, from the start of the buffer */
+    size_t coef_count;                     /* int16 of the whole buffer, a multiple of 64 */
+} rtm3d_jpeg_stream_info;
+
+/* HOST functions (csrc/jpeg_host.cpp; no device access, safe to call from several threads at once).
+ * rtm3d_jpeg_info: parses the headers up to and including SOS, makes every refusal that needs no entropy decoding.
+ * rtm3d_jpeg_entropy_decode: the same, then Huffman-decodes the scan (8 bits of lookahead per table step) into
+ * h_coef[0 .. coef_count) in the layout above; refused when capacity (in int16) is below coef_count.  Whatever the bytes
+ * are, nothing outside data[0 .. bytes) is read and nothing outside h_coef[0 .. capacity) is written.
+ * rtm3d_jpeg_workspace_bytes: the bytes of the staging buffer and of the device coefficient buffer of rtm3d_frames_jpeg for
+ * these B streams - the sum of their coef_count * 2.                                                                     */
+int rtm3d_jpeg_info(const uint8_t* data, size_t bytes, rtm3d_jpeg_stream_info* out);
+int rtm3d_jpeg_entropy_decode(const uint8_t* data, size_t bytes, int16_t* h_coef, size_t capacity);
+int rtm3d_jpeg_workspace_bytes(int B, const uint8_t* const* h_data, const size_t* h_bytes, size_t* bytes);
+
+/* The device stage alone (csrc/jpeg.hip): steps 1-5 for B frames whose coefficient buffers are on the device.  h_frames[B]
+ * and h_dst[B] are HOST arrays; d_coef a DEVICE pointer, 16-byte aligned, to the frame's buffer; h_dst[b] a DEVICE pointer
+ * to h * w * 3 bytes.  Frames of different sizes and modes may share a chunk.  Stream-ordered, no host synchronisation.
+ * rtm3d_frames_jpeg_plan: the schedule of a batch, the very numbers the launcher uses; out[(B + 31) / 32] receives one
+ * entry per chunk.  A frame is cut into tiles of tile_w x tile_h pixels.  A workgroup of `threads` first runs the inverse DCT
+ * of every block under its tile, one block per thread and step, into LDS - for subsampled chroma also the blocks that hold
+ * the `halo` chroma samples beyond each tile edge, which are computed again by the neighbouring tile - and then every thread
+ * writes 8 pixels of 4 consecutive rows.  Workgroup t of grid row i (frame first + i) takes tile t % tiles_x of tile row
+ * t / tiles_x, tiles_x = ceil(w / tile_w), and leaves when t >= the frame's own number of tiles.  tiles is the largest of the
+ * chunk, grid_x = tiles, grid_y = count.
+ * rtm3d_frames_jpeg_check: every refusal of rtm3d_frames_jpeg_idct, without a launch: B < 1, a NULL array, coefficient
+ * buffer or destination, a buffer that is not 16-byte aligned, an unknown mode or dst_order, reserved != 0, h or w outside
+ * 1..16384.  The message names the frame.                                                                                */
+typedef struct rtm3d_jpeg_frame {
+    const int16_t* d_coef;                 /* DEVICE */
+    int h, w, mode, reserved;              /* reserved = 0 */
+} rtm3d_jpeg_frame;
+typedef struct rtm3d_jpeg_plan {
+    int first, count;                      /* frames first .. first + count - 1 */
+    int tile_w, tile_h, halo;              /* 128 x 64 pixels; 1 chroma sample beyond each edge */
+    int threads;                           /* per workgroup */
+    int tiles;                             /* tiles of the chunk's largest frame */
+    int grid_x, grid_y;
+} rtm3d_jpeg_plan;
+int rtm3d_frames_jpeg_plan(int B, const rtm3d_jpeg_frame* h_frames, rtm3d_jpeg_plan* out);
+int rtm3d_frames_jpeg_check(int B, const rtm3d_jpeg_frame* h_frames, uint8_t* const* h_dst, int dst_order);
+int rtm3d_frames_jpeg_idct(void* stream, int B, const rtm3d_jpeg_frame* h_frames, uint8_t* const* h_dst, int dst_order);
+
+/* The chain: B streams h_data[b][0 .. h_bytes[b]) on the host to B packed frames on the device.
+ *   1. rtm3d_jpeg_info on every stream;  2. every refusal that needs no decoding, for the whole batch: a stream's own, a
+ *   destination of fewer than h * w * 3 bytes (h_dst_bytes[b]), a capacity below rtm3d_jpeg_workspace_bytes;
+ *   3. the entropy decode of the B streams into h_stage, frame after frame, on n_threads host threads (0: min(B, 8); at most
+ *   64), each stream refused as in "REFUSED";  4. one hipMemcpyAsync per chunk of 32 frames from h_stage to the same offset
+ *   of d_coef;  5. rtm3d_frames_jpeg_idct.
+ * Nothing is launched or copied unless every stream decoded.  h_stage is caller-owned HOST memory of `capacity` bytes -
+ * pinned, or the copies are not asynchronous - and d_coef a DEVICE buffer of as many, 128-byte aligned.  The call returns
+ * when the decode is done and the rest is queued: h_stage may be reused once the copies have completed on the stream (an
+ * event recorded behind the call), d_coef once the kernels have.                                                         */
+int rtm3d_frames_jpeg(void* stream, int B, const uint8_t* const* h_data, const size_t* h_bytes, int16_t* h_stage, int16_t* d_coef,
+                      size_t capacity, uint8_t* const* h_dst, const size_t* h_dst_bytes, int dst_order, int n_threads);
+
+/* One detect step of an engine fed by JPEG streams, the twin of rtm3d_engine_detect_frames_raw: rtm3d_frames_jpeg into
+ * h_packed[B] (DEVICE buffers of h_packed_bytes[b] >= h * w * 3 bytes, which hold the packed frames afterwards), then
+ * rtm3d_engine_detect_frames on h_packed with the (h, w) of the streams.  Same workspace, same rtm3d_engine_set_frame_params;
+ * everything either step would refuse is refused before the first launch.                                                */
+int rtm3d_engine_detect_frames_jpeg(rtm3d_ctx* ctx, void* stream, const uint8_t* const* h_data, const size_t* h_bytes,
+                                    int16_t* h_stage, int16_t* d_coef, size_t capacity, uint8_t* const* h_packed,
+                                    const size_t* h_packed_bytes, int dst_order, int n_threads, const double* d_K_camera, float* d_rec,
+                                    double* d_kitti, void* d_workspace);
+
 /* ------------------------------------------------------------------ lens undistortion (csrc/lens.hip, csrc/engine.cpp)
  * Every other entry point takes a frame for a pinhole image described by a 3 x 3 K.  A frame of a real camera is one only
  * after rectification: this section builds rectifying maps on the device and resamples packed frames through them, the stage

@@ -135,6 +135,24 @@ class DemosaicPlan(ctypes.Structure):
                 ('tiles', c_int), ('grid_x', c_int), ('grid_y', c_int)]
 
 
+class JpegInfo(ctypes.Structure):
+    """Mirror of struct rtm3d_jpeg_stream_info (rtm3d_amd/jpeg.py)."""
+    _fields_ = [('h', c_int), ('w', c_int), ('components', c_int), ('mode', c_int), ('restart_interval', c_int),
+                ('mcus_x', c_int), ('mcus_y', c_int), ('bw', c_int * 3), ('bh', c_int * 3), ('reserved', c_int),
+                ('table_offset', c_size_t * 3), ('plane_offset', c_size_t * 3), ('coef_count', c_size_t)]
+
+
+class JpegFrame(ctypes.Structure):
+    """Mirror of struct rtm3d_jpeg_frame."""
+    _fields_ = [('d_coef', c_void_p), ('h', c_int), ('w', c_int), ('mode', c_int), ('reserved', c_int)]
+
+
+class JpegPlan(ctypes.Structure):
+    """Mirror of struct rtm3d_jpeg_plan (one per chunk of 32 frames)."""
+    _fields_ = [('first', c_int), ('count', c_int), ('tile_w', c_int), ('tile_h', c_int), ('halo', c_int), ('threads', c_int),
+                ('tiles', c_int), ('grid_x', c_int), ('grid_y', c_int)]
+
+
 class LensMapC(ctypes.Structure):
     """Mirror of struct rtm3d_lens_map (rtm3d_amd/lens.py)."""
     _fields_ = [('d_map', c_void_p), ('ho', c_int), ('wo', c_int), ('reserved', c_int)]
@@ -255,6 +273,16 @@ SIGNATURES = {
     'rtm3d_frames_demosaic': (c_int, [c_void_p, c_int, ctypes.POINTER(RawSrc), c_void_p, c_int, c_int]),
     'rtm3d_engine_detect_frames_raw': (c_int, [c_void_p, c_void_p, ctypes.POINTER(RawSrc), c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                c_void_p, c_void_p]),
+    # JPEG frames: host entropy decode, device IDCT into packed frames (rtm3d_amd/jpeg.py, rtm3d_amd/engine.py)
+    'rtm3d_jpeg_info': (c_int, [c_void_p, c_size_t, ctypes.POINTER(JpegInfo)]),
+    'rtm3d_jpeg_entropy_decode': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t]),
+    'rtm3d_jpeg_workspace_bytes': (c_int, [c_int, c_void_p, c_void_p, ctypes.POINTER(c_size_t)]),
+    'rtm3d_frames_jpeg_plan': (c_int, [c_int, ctypes.POINTER(JpegFrame), ctypes.POINTER(JpegPlan)]),
+    'rtm3d_frames_jpeg_check': (c_int, [c_int, ctypes.POINTER(JpegFrame), c_void_p, c_int]),
+    'rtm3d_frames_jpeg_idct': (c_int, [c_void_p, c_int, ctypes.POINTER(JpegFrame), c_void_p, c_int]),
+    'rtm3d_frames_jpeg': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int]),
+    'rtm3d_engine_detect_frames_jpeg': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     # lens undistortion: rectifying maps and the bilinear remap (rtm3d_amd/lens.py, rtm3d_amd/engine.py)
     'rtm3d_frames_remap_plan': (c_int, [c_int, ctypes.POINTER(LensMapC), ctypes.POINTER(RemapPlan)]),
     'rtm3d_frames_remap_check': (c_int, [c_int, c_void_p, c_void_p, ctypes.POINTER(LensMapC), c_void_p, c_void_p]),
@@ -330,7 +358,7 @@ def check(rc, what=''):
         raise RuntimeError('rtm3d_hip %s failed: %s' % (what, msg.decode() if msg else 'unknown error'))
 
 
-# what the camera-frame wrappers (engine, draw, lens, pixfmt, raw, preprocess) hand to the library
+# what the camera-frame wrappers (engine, draw, lens, pixfmt, raw, jpeg, preprocess) hand to the library
 def stream_ptr(device):
     """The current stream of ``device`` as the `void* stream` of an entry point."""
     import torch

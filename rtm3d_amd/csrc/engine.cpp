@@ -585,6 +585,31 @@ extern "C" int rtm3d_engine_detect_frames_raw(rtm3d_ctx* ctx, void* stream, cons
     return rtm3d_engine_detect_frames(ctx, stream, h_packed, st->src_hw.data(), d_K_camera, d_rec, d_kitti, d_workspace);
 }
 
+extern int rt_jpeg_info(const uint8_t* data, size_t bytes, rtm3d_jpeg_stream_info* out, char* msg, size_t msg_len);
+
+extern "C" int rtm3d_engine_detect_frames_jpeg(rtm3d_ctx* ctx, void* stream, const uint8_t* const* h_data, const size_t* h_bytes,
+                                               int16_t* h_stage, int16_t* d_coef, size_t capacity, uint8_t* const* h_packed,
+                                               const size_t* h_packed_bytes, int dst_order, int n_threads, const double* d_K_camera,
+                                               float* d_rec, double* d_kitti, void* d_workspace) {
+    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
+    if (!st) EFAIL("engine_detect_frames_jpeg: the context was not made by rtm3d_engine_load");
+    if (!h_data || !h_bytes || !h_stage || !d_coef || !h_packed || !h_packed_bytes || !d_K_camera || !d_rec || !d_workspace)
+        EFAIL("engine_detect_frames_jpeg: null argument");
+    if (!st->frames) EFAIL("engine_detect_frames_jpeg: call rtm3d_engine_set_frame_params first");
+    const rtm3d_engine_info& I = st->info;
+    // the frames' place on the canvas, before anything is decoded or launched; rtm3d_frames_jpeg refuses the rest before its first launch
+    st->src_hw.resize((size_t)I.B * 2);
+    for (int b = 0; b < I.B; ++b) {
+        rtm3d_jpeg_stream_info J;
+        char msg[200];
+        if (rt_jpeg_info(h_data[b], h_bytes[b], &J, msg, sizeof(msg))) EFAIL("engine_detect_frames_jpeg: frame %d: %s", b, msg);
+        st->src_hw[2 * b] = J.h; st->src_hw[2 * b + 1] = J.w;
+    }
+    if (rtm3d_frame_geometry(I.B, st->src_hw.data(), st->resize_to, I.H, I.W, st->geom.data())) return 1;
+    if (rtm3d_frames_jpeg(stream, I.B, h_data, h_bytes, h_stage, d_coef, capacity, h_packed, h_packed_bytes, dst_order, n_threads)) return 1;
+    return rtm3d_engine_detect_frames(ctx, stream, h_packed, st->src_hw.data(), d_K_camera, d_rec, d_kitti, d_workspace);
+}
+
 extern "C" int rtm3d_engine_detect_frames_lens(rtm3d_ctx* ctx, void* stream, const rtm3d_frame_src* h_src, uint8_t* const* h_packed,
                                                const int* h_hw, int dst_order, const rtm3d_lens_map* h_maps, uint8_t* const* h_rect,
                                                const uint8_t fill[3], const double* d_K_rect, float* d_rec, double* d_kitti,

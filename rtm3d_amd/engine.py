@@ -594,6 +594,38 @@ class Engine(object):
             panels, ids = self._after_step(rec, rows, K, packed, draw, tracker, nms3d)
         return self._result(rec, rows, panels, ids)
 
+    def detect_frames_jpeg(self, datas, K_camera, order='rgb', packed=None, kitti=False, out=None, draw=None, tracker=None, nms3d=None):
+        """detect_frames fed by JPEG streams (rtm3d_engine_detect_frames_jpeg), the twin of detect_frames_raw: datas = list of B
+        baseline JPEG streams (bytes objects or 1-D uint8 arrays: jpeg.read_files, an MJPEG camera's frames) of any sizes that fit
+        the canvas after Resize.  The host entropy-decodes them on a few threads, one copy and one launch in front of the step
+        write the frames into ``packed`` - B contiguous uint8 (h, w, 3) CUDA tensors, allocated when None and reachable afterwards
+        as ``engine.last_packed`` - and the step reads those; the device is never waited for.
+        order: 'rgb' | 'bgr', the byte order of the packed pixels = the channel order the checkpoint was trained on.  Every other
+        keyword is detect_frames' and what is returned is what it returns; draw= paints into ``packed``."""
+        import torch
+        from . import box_overlap, jpeg
+        nms3d = box_overlap.nms3d_options(nms3d)
+        datas = self._frames_ready('detect_frames_jpeg', datas)
+        arrs, ptrs, sizes = jpeg._streams(datas)
+        infos = jpeg.batch_info(arrs, 'engine_detect_frames_jpeg')
+        K = self._intrinsics(K_camera)
+        with torch.cuda.device(self.device):
+            self._check_draw('detect_frames_jpeg', draw, tracker)
+            packed = jpeg._destinations([(i['h'], i['w']) for i in infos], packed, self.device)
+            rec, rows = self._outputs(out, kitti)
+            s, cap = jpeg.staging(self.device, sum(i['coef_count'] for i in infos) * 2)
+            nbytes = (ctypes.c_size_t * len(packed))(*[p.numel() for p in packed])
+            _lib.check(self.lib.rtm3d_engine_detect_frames_jpeg(
+                self.ctx, _lib.stream_ptr(self.device), ptrs, sizes, s.host.data_ptr(), s.dev.data_ptr(), cap, _lib.ptr_array(packed), nbytes,
+                jpeg._order(order), 0, ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+                ctypes.c_void_p(rows.data_ptr()) if kitti else None, ctypes.c_void_p(self.frames_workspace.data_ptr())),
+                'engine_detect_frames_jpeg')
+            s.event = torch.cuda.Event()
+            s.event.record(torch.cuda.current_stream(self.device))
+            self.last_packed = packed
+            panels, ids = self._after_step(rec, rows, K, packed, draw, tracker, nms3d)
+        return self._result(rec, rows, panels, ids)
+
     def detect_frames_lens(self, frames_or_sources, maps, order='rgb', fill=(0, 0, 0), K_rect=None, packed=None, rect=None, kitti=False,
                            out=None, draw=None, tracker=None, nms3d=None):
         """detect_frames fed by frames of a real lens (rtm3d_engine_detect_frames_lens): frames_or_sources = list of B raw

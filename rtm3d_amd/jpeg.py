@@ -1,0 +1,191 @@
+"""JPEG frames (include/rtm3d_hip.h, "JPEG frames"): baseline JPEG byte streams - what USB / IP cameras deliver as MJPEG and
+what recorded driving sets ship as files - become the tightly packed uint8 (h, w, 3) frames that Engine.detect_frames,
+lens.remap, preprocess_batch and the drawing entry points read.  The Huffman decoding runs on the host, threaded over the
+frames of a batch (rtm3d_jpeg_entropy_decode); dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the
+device, one launch per 32 frames (rtm3d_frames_jpeg_idct).  No image library is involved.  The integer rule - libjpeg's default
+decode, bit for bit - is written out in the header; tests/jpeg_ref.py restates it in numpy."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+MODES = {'grey': 0, '444': 1, '422': 2, '420': 3}
+MODE_NAMES = {v: k for k, v in MODES.items()}
+ORDERS = {'rgb': 0, 'bgr': 1}
+CHUNK = 32
+TABLE_WORDS = 192                        # int16 in front of the planes of a coefficient buffer: three tables of 64
+
+
+def _order(order):
+    if isinstance(order, str):
+        if order.lower() not in ORDERS:
+            raise ValueError("unknown order %r ('rgb' or 'bgr')" % (order,))
+        return ORDERS[order.lower()]
+    return int(order)                    # a number is passed on: the library refuses what it does not know
+
+
+def _stream(data):
+    """bytes | bytearray | memoryview | 1-D uint8 array -> a contiguous 1-D uint8 numpy array that shares or copies the bytes."""
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8 or data.ndim != 1:
+            raise ValueError('a stream is bytes or a 1-D uint8 array, got %s %s' % (data.dtype, data.shape))
+        return np.ascontiguousarray(data)
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(data, dtype=np.uint8)
+    raise ValueError('a stream is bytes or a 1-D uint8 array, got %s' % type(data).__name__)
+
+
+def _streams(datas):
+    arrs = [_stream(d) for d in datas]
+    if not arrs:
+        raise ValueError('expected a non-empty list of JPEG streams')
+    ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    sizes = (ctypes.c_size_t * len(arrs))(*[a.size for a in arrs])
+    return arrs, ptrs, sizes
+
+
+def info(data):
+    """rtm3d_jpeg_info (host only): dict with h, w, components, mode ('grey' '444' '422' '420'), restart_interval, mcus_x, mcus_y,
+    bw / bh (the block grid of each component), table_offset / plane_offset (in int16) and coef_count of the stream's coefficient
+    buffer.  RuntimeError with the reason for a stream that is refused."""
+    a = _stream(data)
+    out = _lib.JpegInfo()
+    _lib.check(_lib.load().rtm3d_jpeg_info(a.ctypes.data, a.size, ctypes.byref(out)), 'jpeg_info')
+    n = out.components
+    return dict(h=out.h, w=out.w, components=n, mode=MODE_NAMES[out.mode], restart_interval=out.restart_interval, mcus_x=out.mcus_x,
+                mcus_y=out.mcus_y, bw=list(out.bw)[:n], bh=list(out.bh)[:n], table_offset=list(out.table_offset)[:n],
+                plane_offset=list(out.plane_offset)[:n], coef_count=out.coef_count)
+
+
+def batch_info(arrs, who):
+    """info of every stream of a batch; a refusal names the frame, as the library's batch entry points do."""
+    out = []
+    for b, a in enumerate(arrs):
+        try:
+            out.append(info(a))
+        except RuntimeError as e:
+            raise RuntimeError('rtm3d_hip %s failed: %s: frame %d: %s' % (who, who, b, str(e).split('jpeg_info: ', 1)[-1]))
+    return out
+
+
+def entropy_decode(data):
+    """rtm3d_jpeg_entropy_decode (host only): the stream's coefficient buffer as an int16 numpy array of info(data)['coef_count']."""
+    a = _stream(data)
+    buf = np.empty(info(a)['coef_count'], np.int16)
+    _lib.check(_lib.load().rtm3d_jpeg_entropy_decode(a.ctypes.data, a.size, buf.ctypes.data, buf.size), 'jpeg_entropy_decode')
+    return buf
+
+
+def c_frames(frames):
+    """[(int16 CUDA tensor holding a coefficient buffer, h, w, mode)] -> ctypes array of rtm3d_jpeg_frame."""
+    arr = (_lib.JpegFrame * len(frames))()
+    for i, (coef, h, w, mode) in enumerate(frames):
+        arr[i].d_coef = coef if isinstance(coef, int) else coef.data_ptr()
+        arr[i].h, arr[i].w, arr[i].reserved = int(h), int(w), 0
+        arr[i].mode = MODES[mode] if isinstance(mode, str) else int(mode)
+    return arr
+
+
+def plan(frames):
+    """rtm3d_frames_jpeg_plan: the launch schedule of idct(frames), one JpegPlan per chunk of 32 frames (host only; ``frames``:
+    what c_frames takes, or its result)."""
+    arr = frames if isinstance(frames, ctypes.Array) else c_frames(frames)
+    out = (_lib.JpegPlan * ((len(arr) + CHUNK - 1) // CHUNK))()
+    _lib.check(_lib.load().rtm3d_frames_jpeg_plan(len(arr), arr, out), 'frames_jpeg_plan')
+    return list(out)
+
+
+def _destinations(sizes, out, dev):
+    import torch
+    if out is None:
+        return [torch.empty(h, w, 3, dtype=torch.uint8, device=dev) for h, w in sizes]
+    out = list(out)
+    if len(out) != len(sizes):
+        raise ValueError('%d destinations for %d streams' % (len(out), len(sizes)))
+    for (h, w), o in zip(sizes, out):
+        if not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or not o.is_cuda or tuple(o.shape) != (h, w, 3) or not o.is_contiguous():
+            raise ValueError('a destination is a contiguous uint8 CUDA tensor of its stream\'s (h, w, 3) = %s' % ((h, w, 3),))
+    return out
+
+
+def idct(frames, order='rgb', out=None):
+    """rtm3d_frames_jpeg_idct, the device stage alone: frames = [(int16 CUDA tensor holding a coefficient buffer, h, w, mode)] ->
+    list of packed uint8 (h, w, 3) CUDA tensors (``out``, or new ones)."""
+    import torch
+    frames = list(frames)
+    dev = frames[0][0].device
+    with torch.cuda.device(dev):
+        out = _destinations([(f[1], f[2]) for f in frames], out, dev)
+        _lib.check(_lib.load().rtm3d_frames_jpeg_idct(_lib.stream_ptr(dev), len(frames), c_frames(frames), _lib.ptr_array(out), _order(order)),
+                   'frames_jpeg_idct')
+    return out
+
+
+class _Staging(object):
+    """One set of buffers of the chain: pinned host memory for the coefficients, the device buffer they are copied to, and the
+    event behind the last call that used them."""
+
+    def __init__(self):
+        self.host = self.dev = self.event = None
+
+    def ready(self, nbytes, device):
+        import torch
+        if self.event is not None:
+            self.event.synchronize()                 # the copy and the kernels of the call before last have left these buffers
+        if self.host is None or self.host.numel() * 2 < nbytes:
+            self.host = torch.empty(max(nbytes // 2, 1), dtype=torch.int16).pin_memory()
+        if self.dev is None or self.dev.numel() * 2 < nbytes or self.dev.device != device:
+            self.dev = torch.empty(max(nbytes // 2, 1), dtype=torch.int16, device=device)
+        return min(self.host.numel(), self.dev.numel()) * 2
+
+
+_sets = {}                               # device -> [two _Staging, the index of the next]
+
+
+def staging(device, nbytes):
+    """The staging set of the next call on ``device``, grown to ``nbytes``: (set, capacity in bytes).  Two sets alternate, so the
+    host decodes batch n + 1 while the copy of batch n is still under way; a set is reused only after the event recorded behind
+    its last call has completed."""
+    entry = _sets.setdefault(str(device), [[_Staging(), _Staging()], 0])
+    s = entry[0][entry[1]]
+    entry[1] ^= 1
+    return s, s.ready(nbytes, device)
+
+
+def workspace_bytes(datas):
+    """rtm3d_jpeg_workspace_bytes: the bytes of staging memory (and of device coefficients) the batch needs."""
+    _, ptrs, sizes = _streams(datas)
+    n = ctypes.c_size_t()
+    _lib.check(_lib.load().rtm3d_jpeg_workspace_bytes(len(ptrs), ptrs, sizes, ctypes.byref(n)), 'jpeg_workspace_bytes')
+    return n.value
+
+
+def decode(datas, order='rgb', out=None, threads=0, device=None):
+    """rtm3d_frames_jpeg: list of JPEG streams (bytes objects or 1-D uint8 arrays) -> list of packed uint8 (h, w, 3) CUDA tensors
+    (``out``, or new ones) on ``device`` (None: the current one).  order: 'rgb' | 'bgr', the byte order of a written pixel - the
+    channel order the checkpoint was trained on.  threads: host threads of the entropy decode, 0 = min(B, 8).  The call returns
+    when the streams are entropy-decoded and the copies and launches are queued on the current stream; one refused stream
+    refuses the batch (RuntimeError naming the frame and the reason) and nothing is launched."""
+    import torch
+    arrs, ptrs, sizes = _streams(datas)
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    infos = batch_info(arrs, 'frames_jpeg')
+    with torch.cuda.device(dev):
+        out = _destinations([(i['h'], i['w']) for i in infos], out, dev)
+        s, cap = staging(dev, sum(i['coef_count'] for i in infos) * 2)
+        nbytes = (ctypes.c_size_t * len(out))(*[o.numel() for o in out])
+        _lib.check(_lib.load().rtm3d_frames_jpeg(_lib.stream_ptr(dev), len(arrs), ptrs, sizes, s.host.data_ptr(), s.dev.data_ptr(), cap,
+                                                 _lib.ptr_array(out), nbytes, _order(order), int(threads)), 'frames_jpeg')
+        s.event = torch.cuda.Event()
+        s.event.record(torch.cuda.current_stream(dev))
+    return out
+
+
+def read_files(paths):
+    """The bytes of the files, as decode takes them."""
+    out = []
+    for p in paths:
+        with open(p, 'rb') as f:
+            out.append(f.read())
+    return out
