@@ -1455,8 +1455,8 @@ int rtm3d_draw_label_text(const rtm3d_draw_tracks_params* p, int id, int cls, fl
  * CLEAR-MOT (rtm3d_mot_clear), per sequence, frames in order with carried state: last[gid] = the tracker id of the ground truth's
  * most recent match, or none; prev[gid] = the tracker id it was matched to in the most recent PROCESSED frame, or none.  thr is
  * the similarity threshold (0.5 in the host's default).  Per frame:
- *   ng == 0: FP += nt, nothing else changes.  nt == 0: FN += ng, nothing else changes.  Neither frame is PROCESSED: the carried
- *   state, prev included, stays as it is.
+ *   ng == 0: FP += nt, nothing else changes.  nt == 0: FN += ng and idcount[gid] += 1 for every ground truth of the frame;
+ *   nothing else changes.  Neither frame is PROCESSED: the carried state, prev included, stays as it is.
  *   otherwise w[g][t] = 1000 * (prev[gid[g]] == tid[t]) + sim[g][t] (1000 + sim, or sim), set to 0 where sim < thr - EPS; ASSIGN.
  *   A matched pair is an identity switch (IDSW += 1) iff last[gid] exists and differs from the matched tid.
  *   idcount[gid] += 1 for every ground truth present, matched[gid] += 1 for the matched ones.  A ground truth whose prev was none

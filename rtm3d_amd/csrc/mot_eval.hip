@@ -273,6 +273,13 @@ __global__ __launch_bounds__(64) void mot_clear_kernel(int cap_g, int cap_t, int
             fp += nt;
             if (wl == 0) fn += ng;
             for (int g = wl; g < cap_g; g += 64) mrow[g] = -1;
+            if (ng > 0) {                                     // the tracker is empty: the frame still counts in its ids' lives
+                for (int g = wl; g < ng; g += 64) {
+                    const int gi = gid[(size_t)f * cap_g + g];
+                    if (gi >= 0 && gi < n_gid) idcount[gi] += 1;
+                }
+                MOT_GSYNC();                                  // another lane may own the id in the next frame
+            }
             continue;
         }
         const int32_t* gf = gid + (size_t)f * cap_g;

@@ -151,6 +151,8 @@ def clear(sim, ng, nt, gid, tid, seq_start, thr=0.5, with_margin=True):
                 continue
             if m == 0:
                 counts[s, 1] += n
+                for g in range(n):
+                    idcount[s, gid[f, g]] += 1
                 continue
             w = np.zeros((n, m))
             for g in range(n):

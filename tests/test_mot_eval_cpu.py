@@ -7,22 +7,8 @@ from rtm3d_amd import kitti_results, mot_eval
 from tests import kitti_eval_ref
 from tests import mot_eval_cases as mc
 from tests import mot_eval_ref as ref
+from tests import mot_eval_regimes as mr
 from tests import track_assign_ref as ar
-
-
-def pack(frames, seq_start=None):
-    """frames: [(gids, tids, {(g slot, t slot): sim})] -> the arrays of the rule (ids given dense)."""
-    F = len(frames)
-    cap_g, cap_t = max([len(f[0]) for f in frames] + [1]), max([len(f[1]) for f in frames] + [1])
-    sim = np.zeros((F, cap_g, cap_t))
-    gid, tid = np.full((F, cap_g), -1, np.int32), np.full((F, cap_t), -1, np.int32)
-    ng, nt = np.zeros(F, np.int32), np.zeros(F, np.int32)
-    for f, (g, t, s) in enumerate(frames):
-        ng[f], nt[f] = len(g), len(t)
-        gid[f, :len(g)], tid[f, :len(t)] = g, t
-        for (i, j), v in s.items():
-            sim[f, i, j] = v
-    return dict(sim=sim, ng=ng, nt=nt, gid=gid, tid=tid, seq_start=np.array([0, F] if seq_start is None else seq_start, np.int32))
 
 
 def both(a, thr=0.5):
@@ -32,16 +18,13 @@ def both(a, thr=0.5):
 
 
 def test_perfect_tracker():
-    a = pack([([0, 1], [0, 1], {(0, 0): 1.0, (1, 1): 1.0})] * 5)
-    h, hm, c, cm = both(a)
+    h, hm, c, cm = both(mr.hand('perfect'))
     assert all(np.array_equal(v, np.ones(19)) for v in hm.values())
     assert cm['MOTA'] == 1.0 and cm['MOTP'] == 1.0 and cm['IDSW'] == 0 and cm['Frag'] == 0 and cm['MT'] == 2 and (cm['TP'], cm['FN'], cm['FP']) == (10, 0, 0)
 
 
 def test_ids_that_swap_halfway():
-    straight, crossed = {(0, 0): 1.0, (1, 1): 1.0}, {(0, 1): 1.0, (1, 0): 1.0}
-    a = pack([([0, 1], [0, 1], straight)] * 2 + [([0, 1], [0, 1], crossed)] * 2)
-    h, hm, c, cm = both(a)
+    h, hm, c, cm = both(mr.hand('swap_halfway'))
     # every pair (g, t) is matched in 2 of the 4 frames both ids live: assa = 2 / (4 + 4 - 2) = 1 / 3; AssA = 4 * 2 * (1 / 3) / 8
     assert np.array_equal(h['potential'][0], np.full((2, 2), 2.0)) and np.array_equal(h['mc'][0, 7], np.full((2, 2), 2))
     assert np.array_equal(hm['DetA'], np.ones(19)) and np.allclose(hm['AssA'], 1.0 / 3.0, rtol=0, atol=1e-15)
@@ -51,28 +34,35 @@ def test_ids_that_swap_halfway():
 
 @pytest.mark.parametrize('new_id', [False, True])
 def test_track_lost_for_two_frames(new_id):
-    seen = ([0, 1], [0, 1], {(0, 0): 0.9, (1, 1): 0.8})
-    lost = ([0, 1], [1], {(1, 0): 0.8})
-    back = ([0, 1], [2 if new_id else 0, 1], {(0, 0): 0.9, (1, 1): 0.8})
-    h, hm, c, cm = both(pack([seen, seen, lost, lost, back, back]))
+    h, hm, c, cm = both(mr.hand('lost_new_id' if new_id else 'lost_same_id'))
     assert cm['Frag'] == 1 and cm['IDSW'] == (1 if new_id else 0) and (cm['TP'], cm['FN'], cm['FP']) == (10, 2, 0)
     assert c['frag'][0].tolist() == [2, 1] and c['matched'][0].tolist() == [4, 6] and c['idcount'][0].tolist() == [6, 6]
     assert abs(cm['MOTP'] - (4 * 0.9 + 6 * 0.8) / 10) < 1e-14
 
 
 def test_empty_frames_leave_the_carried_state_alone():
-    one = ([0], [0], {(0, 0): 0.7})
     # frame 4: tracker 1 overlaps better than tracker 0, but tracker 0 held the ground truth in the last PROCESSED frame (frame 0)
-    a = pack([one, ([0], [], {}), ([], [1], {}), ([], [], {}), ([0], [1, 0], {(0, 0): 0.9, (0, 1): 0.6})])
-    h, hm, c, cm = both(a)
+    h, hm, c, cm = both(mr.hand('empty_frames'))
     assert c['clear_match'][4, 0] == 1 and cm['IDSW'] == 0 and cm['Frag'] == 0 and c['frag'][0, 0] == 1
     assert (cm['TP'], cm['FN'], cm['FP']) == (2, 1, 2) and abs(c['simsum'][0] - 1.3) < 1e-15
     assert h['match'][4, 0] in (0, 1) and h['gcount'][0, 0] == 3 and h['tcount'][0].tolist() == [2, 2]
+    # the frame in which the tracker is empty counts in the ground truth's life, as it does in HOTA's gcount
+    assert c['idcount'][0, 0] == 3 and c['matched'][0, 0] == 2 and (cm['MT'], cm['PT'], cm['ML']) == (0, 1, 0)
     # the same frames with the gap PROCESSED (another pair keeps the tracker non-empty): prev is cleared, the better overlap wins
-    other = {(1, 1): 0.8}
-    b = pack([([0, 1], [0, 2], {(0, 0): 0.7, **other}), ([1], [2], {(0, 0): 0.8}), ([0, 1], [1, 2, 0], {(0, 0): 0.9, (0, 2): 0.6, **other})])
+    b = mr.hand('gap_processed')
     c2 = ref.clear(b['sim'], b['ng'], b['nt'], b['gid'], b['tid'], b['seq_start'])
     assert c2['clear_match'][2, 0] == 0 and c2['counts'][0, 3] == 1 and c2['frag'][0, 0] == 2
+
+
+def test_frames_with_an_empty_tracker_count_in_the_life_of_an_object():
+    # present for 10 frames, matched in 2, the tracker empty in the other 8: 2 of 10, not 2 of 2 - never "mostly tracked".  2 / 10 is
+    # ">= 0.2", which test_mt_pt_ml_boundaries pins as partly tracked; with one more empty frame (2 of 11) the object is mostly lost
+    h, hm, c, cm = both(mr.hand('empty_tracker_8_of_10'))
+    assert c['idcount'][0, 0] == 10 and c['matched'][0, 0] == 2 and h['gcount'][0, 0] == 10
+    assert (cm['MT'], cm['PT'], cm['ML']) == (0, 1, 0) and (cm['TP'], cm['FN'], cm['FP'], cm['IDSW'], cm['Frag']) == (2, 8, 0, 0, 0)
+    h, hm, c, cm = both(mr.hand('empty_tracker_9_of_11'))
+    assert c['idcount'][0, 0] == 11 and c['matched'][0, 0] == 2 and (cm['MT'], cm['PT'], cm['ML']) == (0, 0, 1)
+    assert (cm['TP'], cm['FN'], cm['FP'], cm['IDSW'], cm['Frag']) == (2, 9, 0, 0, 0) and abs(cm['MOTP'] - 0.7) < 1e-15
 
 
 def test_mt_pt_ml_boundaries():
