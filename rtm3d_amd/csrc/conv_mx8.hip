@@ -8,6 +8,8 @@
 // Quantisation rule (OCP MX v1.0), identical on the host (rtm3d_amd/mx8.py):
 //   shared_exp = floor(log2(amax of the 32 values)) - 8, clamped to [-127, 127]; an all-zero block gets 127 (2^0);
 //   element = round-to-nearest-even e4m3(x / 2^shared_exp), saturated to +-448.
+//   Non-finite values: amax is an fmaxf, so a NaN never reaches a scale (an all-NaN block gets 127, an infinity gives 247); a
+//   NaN element, like an infinity, becomes sign | 0x7e.  Code 0x7f / 0xff is never written.
 //
 // conv_mx8_kernel: implicit GEMM, 256 pixels x 256 output channels per workgroup, 8 waves (2 pixel halves x 4 channel
 // quarters, 4 x 2 MFMA tiles of 32 x 32 each), K-step = (tap, 64-channel chunk) = ONE scaled MFMA per tile.  Weights and
@@ -27,7 +29,7 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------- quantisation (device half of rtm3d_amd/mx8.py)
-// E8M0 byte of a block with largest magnitude `amax` (finite, >= 0)
+// E8M0 byte of a block with largest magnitude `amax` (>= 0, never NaN: the callers take it with fmaxf; +inf gives 247)
 __device__ __forceinline__ int mx8_scale_byte(float amax) {
     const uint32_t bits = __float_as_uint(amax);
     const int e = (int)((bits >> 23) & 0xff);

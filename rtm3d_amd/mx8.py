@@ -4,6 +4,11 @@ on the device, restated in numpy, and the weight packing of rtm3d_op_conv_mx8 (i
 Per block of 32 values:  shared_exp = floor(log2(amax)) - 8, clamped to [-127, 127] (an all-zero block gets 0, i.e. scale
 byte 127); element = round-to-nearest-even e4m3fn(x / 2^shared_exp), saturated to +-448.  torch's float8_e4m3fn cast does not
 saturate (it returns NaN above 464), so nothing here goes through it.
+
+Non-finite values (fp16 head maps are not guaranteed finite), the device's rule: the block maximum is taken with fmax, so a NaN
+never reaches a scale - the scale comes from the other values of the block, an infinity among them gives byte 247, an all-NaN
+block gets 127 like an all-zero one.  A NaN element becomes sign | 0x7e, +-448 in its block's scale, as an infinity does: code
+0x7f / 0xff (e4m3fn's NaN) is never written.
 """
 import numpy as np
 
@@ -12,7 +17,7 @@ E4M3_MAX = 448.0
 
 
 def scale_bytes(amax):
-    """E8M0 byte (shared_exp + 127) of blocks with largest magnitude `amax` (float32 array, finite, >= 0)."""
+    """E8M0 byte (shared_exp + 127) of blocks with largest magnitude `amax` (float32 array, >= 0, not NaN; +inf gives 247)."""
     a = np.asarray(amax, np.float32)
     e = ((a.view(np.uint32) >> 23) & 0xff).astype(np.int32)
     s = np.clip(e - 127 - 8, -127, 127) + 127
@@ -35,9 +40,10 @@ def e4m3_encode(v):
     a = np.abs(v)
     e = ((a.view(np.uint32) >> 23) & 0xff).astype(np.int32) - 127
     e = np.maximum(e, -6)                                   # e4m3 subnormals share exponent -6 (quantum 2^-9)
-    q = np.rint(a * pow2(3 - np.minimum(e, 8))).astype(np.int64)
+    small = a < E4M3_MAX                                    # false for a NaN, like the device's !(a < 448)
+    q = np.rint(np.where(small, a, 0) * pow2(3 - np.minimum(e, 8))).astype(np.int64)
     code = ((e + 7) << 3) + q - 8
-    code = np.where(a < E4M3_MAX, code, 0x7e)               # (448, 464] rounds to 448; above saturates
+    code = np.where(small, code, 0x7e)                      # (448, 464] rounds to 448; above, infinities and NaNs saturate
     return (code.astype(np.uint32) | sign).astype(np.uint8)
 
 
@@ -55,8 +61,9 @@ def quantize(x):
     x = np.asarray(x, np.float32)
     assert x.shape[-1] % BLOCK == 0, x.shape
     xb = x.reshape(x.shape[:-1] + (x.shape[-1] // BLOCK, BLOCK))
-    sb = scale_bytes(np.abs(xb).max(-1))
-    codes = e4m3_encode(xb * pow2(127 - sb.astype(np.int32))[..., None])
+    sb = scale_bytes(np.fmax.reduce(np.abs(xb), axis=-1, initial=0.0))       # fmax: a NaN never reaches a scale
+    with np.errstate(invalid='ignore', over='ignore'):
+        codes = e4m3_encode(xb * pow2(127 - sb.astype(np.int32))[..., None])
     return codes.reshape(x.shape), sb
 
 

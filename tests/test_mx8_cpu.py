@@ -259,3 +259,47 @@ def test_refused_mode_combinations():
     from rtm3d_amd.pipeline import Detect3DPipeline
     with pytest.raises(NotImplementedError, match='sparse_heads'):
         Detect3DPipeline(m16, 1, 'cuda:0', sparse_heads=True, head_precision='mxfp8')
+
+
+# ------------------------------------------------------------------------------ non-finite values: the device's rule
+def test_quantiser_nan_never_reaches_a_scale():
+    """fmax semantics (quant_mx8_kernel): the scale comes from the block's other values, the NaN element becomes sign | 0x7e
+    (+-448 in the block's scale), an all-NaN block gets byte 127; code 0x7f / 0xff is never written."""
+    nan, nnan = np.float32(np.nan), np.copysign(np.float32(np.nan), np.float32(-1.0))
+    x = np.zeros((4, 32), np.float32)
+    x[0, :4] = [3.0, nan, -1.5, nnan]                       # one block with NaNs of both signs among finite values
+    x[1, :4] = [nan, np.inf, -2.0, nnan]                    # NaN plus an infinity
+    x[2, :] = nan                                           # all NaN
+    x[2, 1::2] = nnan
+    x[3, :3] = [3.0, -1.5, 0.0]                             # block 0 without its NaNs
+    c, s = mx8.quantize(x)
+    assert s[:, 0].tolist() == [mx8.scale_bytes(np.float32(3.0)), 247, 127, mx8.scale_bytes(np.float32(3.0))]
+    assert s[0, 0] == 127 + 1 - 8
+    assert c[0, :4].tolist() == [c[3, 0], 0x7e, c[3, 1], 0xfe] and not c[0, 4:].any()
+    assert c[1, :4].tolist() == [0x7e, 0x7e, 0x80, 0xfe]    # -2 x 2^-120 rounds to -0
+    assert c[2, ::2].tolist() == [0x7e] * 16 and c[2, 1::2].tolist() == [0xfe] * 16
+    assert not np.isin(c, (0x7f, 0xff)).any()
+    d = mx8.dequantize(c, s)
+    assert not np.isnan(d).any() and d[0, 1] == 448.0 * 2.0 ** -7 and d[0, 3] == -448.0 * 2.0 ** -7 and d[2, 0] == 448.0
+
+
+def test_quantiser_infinities_saturate_at_the_largest_scale():
+    x = np.ones((1, 64), np.float32)
+    x[0, 3], x[0, 40] = np.inf, -np.inf
+    c, s = mx8.quantize(x)
+    assert s.tolist() == [[247, 247]] and c[0, 3] == 0x7e and c[0, 40] == 0xfe
+    assert not np.delete(c[0], [3, 40]).any()               # 2^-120 rounds to zero
+
+
+def test_value_classes_of_the_regime_suite_quantise_without_nan_codes():
+    from tests import mx8_ref
+    rng = np.random.default_rng(4)
+    for name in mx8_ref.VALUE_CLASSES:
+        b = mx8_ref.value_block(name, rng)
+        c, s = mx8.quantize(b[None])
+        assert not np.isin(c, (0x7f, 0xff)).any(), name
+        if name not in mx8_ref.NAN_CLASSES:
+            rc, rs = _reference_quantize(np.where(np.isinf(b), np.sign(b) * np.float32(3e38), b)[None])
+            if not np.isinf(b).any():
+                np.testing.assert_array_equal(s, rs, name)
+                np.testing.assert_array_equal(c, rc, name)
