@@ -316,7 +316,10 @@ int rtm3d_pack_records(void* stream, int B, int topk, const int32_t* d_n, const 
  * box x = [sin, cos, l, h, w, X, Y, Z] projected through K - calc_proj_corners / create_corners / rotation_matrix,
  * utils/model_utils.py:66-152 - and the bounding rectangle of the eight corners (the 2D box a KITTI label line carries).
  * d_K: topk > 0 -> one K (9 doubles) per image, slot i belongs to image i / topk; topk == 0 -> one K per slot.
- * Outputs: d_proj[N][9][2], d_rect[N][4] = (x1, y1, x2, y2) fp64; unsolved slots get zeros.                                     */
+ * Outputs: d_proj[N][9][2], d_rect[N][4] = (x1, y1, x2, y2) fp64; unsolved slots get zeros.
+ * Non-finite projections (a corner on the plane z + 1e-6 = 0 projects to +-inf, or to NaN where the numerator is 0 too): the
+ * rectangle is reduced with IEEE fmin / fmax, where a NaN operand loses - a coordinate is NaN only where all eight corners
+ * are, and an infinite corner gives an infinite coordinate.                                                                  */
 int rtm3d_project_boxes(void* stream, int N, int topk, const double* d_x, const int32_t* d_status, const double* d_K,
                         double* d_proj, double* d_rect);
 
@@ -561,7 +564,9 @@ int rtm3d_normalize_luts(const float mean[3], const float std[3], float* h_lut32
 int rtm3d_frame_geometry(int B, const int* h_hw, int resize_to, int H, int W, rtm3d_frame_geom* out);
 
 /* Device kernels; h_geom[B] is HOST memory and travels as a kernel argument (no copy, no memset).  All arithmetic is fp64
- * in a fixed operation order, compiled without contraction, so the results are defined bit for bit.
+ * in a fixed operation order, compiled without contraction, so the results are defined bit for bit.  Both entries check the
+ * geometry of EVERY frame (h, w, rh, rw >= 1) before the first launch: a refusal names the frame and has changed nothing,
+ * whichever frame of the batch it is.
  * rtm3d_frames_adjust_k: d_K_net = the intrinsics of the network canvas from the camera's (both B x 9 fp64): row 0 / w
  * then * rw, row 1 / h then * rh (ToPercentCoords -> Resize -> ToAbsoluteCoords, transforms.py:146-176; the pair is
  * executed for equal sizes too), then cx + pad_w, cy + pad_h (dataset_reader.py:189-193); row 2 is copied.
@@ -570,12 +575,16 @@ int rtm3d_frame_geometry(int B, const int* h_hw, int resize_to, int H, int W, rt
  *   (float)(((double)x - pad_w) * ((double)w / (double)rw)),  (float)(((double)y - pad_h) * ((double)h / (double)rh));
  * [0:2] and [24:32] stay (with consistently adjusted intrinsics the 3D box is the same box); empty slots stay 32 zeros.
  * d_kitti (may be NULL, and then d_K_camera / d_x / d_fun / d_status may be too): B * topk * 16 fp64, one row per slot,
- * all zero unless the slot is kept (flag 2: d_status >= 0 and d_fun < fun_accept).  The row holds the numbers of a KITTI
- * label line (rtm3d_amd/kitti_results.py):
+ * all zero unless the slot is kept: the RECORD's flag [31] is 2, and d_status >= 0 and d_fun < fun_accept agree with it.  The
+ * flag decides because rtm3d_records_nms3d turns the flag of a suppressed slot 2 -> 1 and leaves the solver outputs alone: a
+ * slot it suppressed has no row, whether it ran before this entry or after it (then with its own d_kitti argument).  The row
+ * holds the numbers of a KITTI label line (rtm3d_amd/kitti_results.py):
  *   [0] class  [1] alpha = ry - atan2(x, z) wrapped to [-pi, pi)  [2:6] x1 y1 x2 y2 = the bounding rectangle of the eight
  *   corners projected through the CAMERA's intrinsics (the arithmetic of rtm3d_project_boxes), clipped to [0, w - 1] x
  *   [0, h - 1] of the frame  [6:9] h w l  [9:12] x, y + h / 2, z (centre of the bottom face)  [12] ry = atan2(x0, x1)
  *   [13] score  [14] 2  [15] 0.
+ *   Non-finite projections: the rectangle is reduced and clipped with IEEE fmin / fmax, where a NaN operand loses - a NaN
+ *   coordinate (all eight corners NaN) clips to 0, -inf to 0, +inf to w - 1 / h - 1.
  * d_x / d_fun / d_status: the outputs of rtm3d_decode3d_slots for the same slots.                                         */
 int rtm3d_frames_adjust_k(void* stream, int B, const rtm3d_frame_geom* h_geom, const double* d_K_camera, double* d_K_net);
 int rtm3d_records_to_camera(void* stream, int B, int topk, const rtm3d_frame_geom* h_geom, float* d_rec,
@@ -1076,7 +1085,8 @@ int rtm3d_engine_detect_frames_lens(rtm3d_ctx* ctx, void* stream, const rtm3d_fr
  * else of the record changes, so it still reads as "a detection" (> 0) and no longer as "3D kept" (> 1).  NOTE: a flag-1
  * slot may therefore carry a 3D box in [24:31] that is not kept - as it already may after rtm3d_pack_records, which writes
  * the solver's output of a solved-but-rejected slot (fun >= fun_accept) into those fields.  d_kitti (NULL or the B * topk *
- * 16 rows of rtm3d_records_to_camera): the row of a suppressed slot is zeroed, that array's rule for not-kept slots.
+ * 16 rows of rtm3d_records_to_camera): the row of a suppressed slot is zeroed, that array's rule for not-kept slots - the
+ * same rows rtm3d_records_to_camera writes when it runs after this entry, since it gives a row to flag-2 slots only.
  * One workgroup per image; topk > 256 is refused.  Stream-ordered: one kernel, no host synchronisation, no memset / memcpy
  * node, no allocation.                                                                                                      */
 int rtm3d_box_overlaps(void* stream, int B, int cap_a, int cap_b, const int32_t* d_na, const int32_t* d_nb,

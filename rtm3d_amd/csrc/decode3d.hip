@@ -267,8 +267,11 @@ __global__ __launch_bounds__(256) void project_boxes_kernel(int N, int topk, con
             const double* k = K + (size_t)(topk > 0 ? slot / topk : slot) * 9;
             double sn, cs;
             box_yaw(xs, sn, cs);
-            x1 = y1 = 1e300; x2 = y2 = -1e300;
-            for (int cc = 0; cc < 8; ++cc) {
+            // start from corner 0, not from a sentinel: an infinite corner stays infinite, and NaN (which fmin / fmax drop
+            // against any number) is the result exactly where all eight corners are NaN
+            box_project_corner(xs, k, sn, cs, 0, x1, y1);
+            x2 = x1; y2 = y1;
+            for (int cc = 1; cc < 8; ++cc) {
                 double uu, vv;
                 box_project_corner(xs, k, sn, cs, cc, uu, vv);
                 x1 = fmin(x1, uu); y1 = fmin(y1, vv); x2 = fmax(x2, uu); y2 = fmax(y2, vv);

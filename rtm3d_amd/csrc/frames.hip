@@ -54,7 +54,9 @@ __global__ __launch_bounds__(256) void records_to_camera_kernel(const FrameBatch
         rec[t] = (float)(((double)rec[t] - pad) * scale);
     }
     if (!kitti) return;
-    const bool kept = flag >= 1.0f && status[slot] >= 0 && fun[slot] < fun_accept;      // uniform over the slot's 32 lanes
+    // a row only where the RECORD says kept (flag 2; rtm3d_records_nms3d turns the flag of a suppressed slot 2 -> 1 and leaves
+    // the solver outputs alone) and the solver outputs agree; uniform over the slot's 32 lanes
+    const bool kept = flag == 2.0f && status[slot] >= 0 && fun[slot] < fun_accept;
     double out = 0.0;
     if (kept) {
         const double* xs = x + (size_t)slot * 8;
@@ -99,24 +101,29 @@ __global__ __launch_bounds__(256) void records_to_camera_kernel(const FrameBatch
 
 extern void rt_set_error(const char* fmt, ...);
 
-static int fill_batch(const char* what, FrameBatch& fb, const rtm3d_frame_geom* h_geom, int b0, int nb) {
-    for (int i = 0; i < nb; ++i) {
-        const rtm3d_frame_geom& g = h_geom[b0 + i];
+// every frame of the whole batch, before the first launch: a refusal leaves nothing rewritten
+static int check_geom(const char* what, const rtm3d_frame_geom* h_geom, int B) {
+    for (int i = 0; i < B; ++i) {
+        const rtm3d_frame_geom& g = h_geom[i];
         if (g.h < 1 || g.w < 1 || g.rh < 1 || g.rw < 1) {
-            rt_set_error("%s: frame %d has an empty size (%dx%d -> %dx%d)", what, b0 + i, g.h, g.w, g.rh, g.rw);
+            rt_set_error("%s: frame %d has an empty size (%dx%d -> %dx%d)", what, i, g.h, g.w, g.rh, g.rw);
             return 1;
         }
-        fb.g[i] = g;
     }
     return 0;
 }
 
+static void fill_batch(FrameBatch& fb, const rtm3d_frame_geom* h_geom, int b0, int nb) {
+    for (int i = 0; i < nb; ++i) fb.g[i] = h_geom[b0 + i];
+}
+
 extern "C" int rtm3d_frames_adjust_k(void* stream, int B, const rtm3d_frame_geom* h_geom, const double* d_K_camera, double* d_K_net) {
     if (B < 1 || !h_geom || !d_K_camera || !d_K_net) { rt_set_error("frames_adjust_K: bad arguments"); return 1; }
+    if (check_geom("frames_adjust_K", h_geom, B)) return 1;
     for (int b0 = 0; b0 < B; b0 += FRAMES_MAX_BATCH) {
         const int nb = B - b0 < FRAMES_MAX_BATCH ? B - b0 : FRAMES_MAX_BATCH;
         FrameBatch fb;
-        if (fill_batch("frames_adjust_K", fb, h_geom, b0, nb)) return 1;
+        fill_batch(fb, h_geom, b0, nb);
         hipLaunchKernelGGL(frames_adjust_K_kernel, dim3((nb * 9 + 255) / 256), dim3(256), 0, (hipStream_t)stream, fb, nb,
                            d_K_camera + (size_t)b0 * 9, d_K_net + (size_t)b0 * 9);
     }
@@ -132,10 +139,11 @@ extern "C" int rtm3d_records_to_camera(void* stream, int B, int topk, const rtm3
     if (d_kitti && (!d_K_camera || !d_x || !d_fun || !d_status)) {
         rt_set_error("records_to_camera: the KITTI rows need the camera intrinsics and the solver outputs"); return 1;
     }
+    if (check_geom("records_to_camera", h_geom, B)) return 1;
     for (int b0 = 0; b0 < B; b0 += FRAMES_MAX_BATCH) {
         const int nb = B - b0 < FRAMES_MAX_BATCH ? B - b0 : FRAMES_MAX_BATCH;
         FrameBatch fb;
-        if (fill_batch("records_to_camera", fb, h_geom, b0, nb)) return 1;
+        fill_batch(fb, h_geom, b0, nb);
         const size_t s0 = (size_t)b0 * topk;                   // first slot of the chunk
         const int total = nb * topk * 32;
         hipLaunchKernelGGL(records_to_camera_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, fb, total, topk,
