@@ -867,8 +867,8 @@ int rtm3d_engine_detect_frames_raw(rtm3d_ctx* ctx, void* stream, const rtm3d_raw
  *
  * OUT OF SCOPE: entropy decoding on the device (one lane per restart interval included); progressive, arithmetic, 12-bit, CMYK /
  * YCCK and 1 x 2 sampling; tolerant decoding of damaged streams (libjpeg paints the missing part grey; here the stream is
- * refused); EXIF orientation, ICC profiles, JPEG encoding, PNG; decoding straight into the network input or through the lens
- * map; skipping all-zero blocks by a per-block end index.                                                                 */
+ * refused); EXIF orientation, ICC profiles, PNG; decoding straight into the network input or through the lens map; skipping
+ * all-zero blocks by a per-block end index.  (Encoding: the section "JPEG encoding" below.)                               */
 #define RTM3D_JPEG_GREY 0
 #define RTM3D_JPEG_444 1
 #define RTM3D_JPEG_422 2
@@ -944,6 +944,138 @@ int rtm3d_engine_detect_frames_jpeg(rtm3d_ctx* ctx, void* stream, const uint8_t*
                                     int16_t* h_stage, int16_t* d_coef, size_t capacity, uint8_t* const* h_packed,
                                     const size_t* h_packed_bytes, int dst_order, int n_threads, const double* d_K_camera, float* d_rec,
                                     double* d_kitti, void* d_workspace);
+
+/* ------------------------------------------------------------------ JPEG encoding (csrc/jpeg_enc.hip, csrc/jpeg_host.cpp)
+ * The way back out: painted frames and bird's-eye panels (or any packed frame) become baseline JPEG streams - MJPEG, .jpg
+ * files - with no image library.  The mirror image of "JPEG frames", with the same split and the same coefficient buffer:
+ * colour conversion, edge replication, chroma downsampling, the 8 x 8 forward DCT and the quantisation - all the arithmetic
+ * and all the pixel traffic - run on the DEVICE, one launch per chunk of 32 frames, descriptors and tables by value, no host
+ * synchronisation; the Huffman coding is serial per stream and stays on the HOST, threaded over the frames of a batch.  Added
+ * in ABI 9 without changing any existing declaration, struct, plan, engine file or default.  The rule is libjpeg's default
+ * encode (jccolor, h2v1 / h2v2 downsampling without smoothing, the `islow` forward DCT, the Annex K Huffman tables, its
+ * marker layout), byte for byte: tests/jpeg_enc_ref.py restates it in numpy and tests/golden/jpeg_encode_cases.npz pins it
+ * against the streams libjpeg-turbo wrote (Huffman tables not optimised).
+ *
+ * THE RULE (int32, >> arithmetic).  Input: a packed uint8 (h, w, 3) frame at any byte address, bytes R G B (src_order 0) or
+ * B G R (1); 1 <= h, w <= 16384; mode RTM3D_JPEG_GREY / _444 / _422 / _420.
+ * 1. Colour:  Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *             Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16
+ *             Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16
+ *    Grey keeps Y alone; R = G = B = v gives Y = v exactly.
+ * 2. Edges, in libjpeg's order (it matters for the last chroma row).  For component c with luma sampling (H, V), in the
+ *    decoder's layout: cw = ceil(w H_c / H), ch = ceil(h V_c / V), wib = ceil(cw / 8), hib = ceil(ch / 8) - the REAL block grid.
+ *    Full-resolution columns are replicated from column w - 1 out to wib * 8 * (H / H_c); full-resolution rows from row h - 1
+ *    up to a multiple of V; then the plane is downsampled; then the downsampled rows are replicated from row ch - 1 up to
+ *    hib * 8.
+ * 3. Downsampling of chroma:  4:2:2  o[i] = (p[2i] + p[2i+1] + b) >> 1, b = 0, 1, 0, 1 ... by i;
+ *    4:2:0  o[j][i] = (p[2j][2i] + p[2j][2i+1] + p[2j+1][2i] + p[2j+1][2i+1] + b) >> 2, b = 1, 2, 1, 2 ... by i.
+ * 4. Forward DCT on samples - 128 (libjpeg's jfdctint: CONST_BITS 13, PASS1_BITS 2; the eight constants of the inverse rule).
+ *    The one-dimensional pass on d0..d7:
+ *      t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4;
+ *      t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+ *      o0 = (t10 + t11) << 2, o4 = (t10 - t11) << 2 in pass 1; (t10 + t11 + 2) >> 2, (t10 - t11 + 2) >> 2 in pass 2;
+ *      z1 = (t12 + t13) * 4433;  o2 = D(z1 + t13 * 6270);  o6 = D(z1 - t12 * 15137);
+ *      z1 = t4 + t7, z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7, z5 = (z3 + z4) * 9633;
+ *      t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299;  z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+ *      o7 = D(t4 + z1 + z3), o5 = D(t5 + z2 + z4), o3 = D(t6 + z2 + z3), o1 = D(t7 + z1 + z4);
+ *    D(x) = (x + 2^(s-1)) >> s.  Pass 1 runs along every row with s = 11, pass 2 down every column of the result with s = 15.
+ * 5. Quantisation: a = (|c| + 4 q[k]) / (8 q[k]), truncating; the coefficient is c < 0 ? -a : a; q in natural order, 1..255.
+ *    (The device divides by one multiplication, csrc/jpeg_quant.h, proven over every q and every |c| <= 32767.)
+ * 6. Tables: rtm3d_jpeg_quality_tables(quality 1..100): scale = quality < 50 ? 5000 / quality : 200 - 2 quality,
+ *    t[k] = clamp((base[k] * scale + 50) / 100, 1, 255), base the luminance / chrominance table of Annex K (K.1 / K.2).  A
+ *    caller may pass any two tables of 1..255 instead.  Y uses the first, Cb and Cr the second.
+ * 7. Entropy coding (host).  Blocks in the decoder's MCU order; the Huffman tables of Annex K (K.3 / K.5 for Y, K.4 / K.6 for
+ *    chroma; grey writes DC 0 / AC 0 only); one DC predictor per component, reset at every restart; a block outside its
+ *    component's wib x hib grid is coded as DC difference 0 and end of block without reading the buffer (what libjpeg's dummy
+ *    blocks come to); ZRL for every 16 zeros in front of a coefficient, EOB for a zero tail; 0xFF is followed by a stuffed
+ *    0x00; the last byte before every RSTn and before EOI is padded with 1-bits; RSTn after every `restart` MCUs (0: none).
+ *    Layout: SOI, APP0 (JFIF 1.01, units 0, density 1 x 1, no thumbnail), DQT table 0, [DQT table 1], SOF0 (components 1, 2, 3),
+ *    DHT DC 0, DHT AC 0, [DHT DC 1, DHT AC 1], [DRI], SOS, data, EOI - the bracketed tables for colour, DRI when restart > 0.
+ *
+ * THE COEFFICIENT BUFFER is the decoder's, exactly ("JPEG frames").  The device stage writes the three tables (zero for a
+ * component the frame lacks), every real block, and ZEROS into the padding blocks of the grid: the whole buffer is defined,
+ * rtm3d_frames_jpeg_idct can read it, and rtm3d_jpeg_entropy_decode of an encoded stream equals it on every real block.
+ *
+ * THE SIZE BOUND (rtm3d_jpeg_encode_bound).  Headers: 2 + 18 + 69 t + (10 + 3 n) + 216 t + [6] + (8 + 2 n) bytes for n
+ * components and t = 1 (grey) or 2 tables.  A block: the DC symbol is at most 11 code bits + 11 value bits; every Huffman
+ * symbol behind it can be charged to coefficients of its own - a coefficient's symbol (at most 16 code + 10 value bits) to that
+ * coefficient, a ZRL (at most 16 bits) to the 16 zeros it stands for, the EOB to the zero tail - so no coefficient carries
+ * more than 26 bits and a block no more than 22 + 63 * 26 = 1660 bits = 207.5 bytes.  k blocks between two markers end on a
+ * byte boundary after at most ceil(207.5 k) <= 208 k bytes, and stuffing at most doubles them: 416 bytes per coded block
+ * (padding blocks included), 2 per restart marker, 2 for EOI.  The bound is the sum.
+ *
+ * OUT OF SCOPE: optimised Huffman tables, progressive coding, trellis quantisation, rate control, EXIF / ICC segments, entropy
+ * coding on the device, encoding straight from the draw kernel.                                                           */
+
+/* HOST functions (csrc/jpeg_host.cpp; no device access, safe to call from several threads at once).
+ * rtm3d_jpeg_quality_tables: step 6 into q_luma[64] and q_chroma[64], natural order.
+ * rtm3d_jpeg_frame_layout: the coefficient-buffer layout of an (h, w, mode) frame, as rtm3d_jpeg_info reports it for a stream
+ * (restart_interval 0).
+ * rtm3d_jpeg_encode_bound: the bound above for a stream with a restart interval of `restart` MCUs (0: none).
+ * rtm3d_jpeg_entropy_encode: step 7 of the buffer h_coef (its tables included) into out[0 .. *bytes).  Refused with a reason:
+ * an unknown mode, h or w outside 1..16384, restart outside 0..65535, a table entry of 0 or above 255, a DC difference of a
+ * category above 11 or an AC coefficient of a category above 10 (|v| >= 1024; after a refusal of these two kinds the output
+ * holds a partial stream), a capacity below rtm3d_jpeg_encode_bound.  Nothing outside out[0 .. capacity) is written and
+ * nothing outside h_coef[0 .. coef_count) is read.                                                                        */
+int rtm3d_jpeg_quality_tables(int quality, uint16_t* q_luma, uint16_t* q_chroma);
+int rtm3d_jpeg_frame_layout(int h, int w, int mode, rtm3d_jpeg_stream_info* out);
+int rtm3d_jpeg_encode_bound(int h, int w, int mode, int restart, size_t* bytes);
+int rtm3d_jpeg_entropy_encode(const int16_t* h_coef, int h, int w, int mode, int restart, uint8_t* out, size_t capacity, size_t* bytes);
+
+/* The device stage alone (csrc/jpeg_enc.hip): steps 1-5 for B frames.  h_frames[B] is a HOST array; d_src a DEVICE pointer to
+ * h * w * 3 bytes at any address, d_coef a DEVICE pointer, 16-byte aligned, to the frame's coef_count int16.  q_luma[64] and
+ * q_chroma[64] are HOST arrays, natural order.  Frames of different sizes and modes may share a chunk.  Stream-ordered, no
+ * host synchronisation.
+ * rtm3d_frames_jpeg_fdct_plan: the schedule of a batch, the very numbers the launcher uses; out[(B + 31) / 32] receives one
+ * entry per chunk.  A frame is cut into tiles of tile_w x tile_h pixels - whole MCUs in every mode.  A workgroup of `threads`
+ * converts its tile into Y and downsampled Cb / Cr planes in LDS (rows of lds_stride bytes; subsampled chroma lds_stride_sub),
+ * every thread 8 pixels of 4 consecutive rows, and then runs the forward DCT and the quantisation of every block under the
+ * tile, one block per thread and step.  Workgroup t of grid row i (frame first + i) takes tile t % tiles_x of tile row
+ * t / tiles_x, tiles_x = ceil(w / tile_w), and leaves when t >= the frame's own number of tiles.  tiles is the largest of the
+ * chunk, grid_x = tiles, grid_y = count.  (d_src, d_coef are not looked at.)
+ * rtm3d_frames_jpeg_fdct_check: every refusal of rtm3d_frames_jpeg_fdct, without a launch: B < 1, a NULL array, source or
+ * coefficient buffer, a buffer that is not 16-byte aligned, an unknown mode or src_order, reserved != 0, h or w outside
+ * 1..16384, a table entry of 0 or above 255.  The message names the frame.                                                */
+typedef struct rtm3d_jpeg_enc_frame {
+    const uint8_t* d_src;                  /* DEVICE */
+    int16_t* d_coef;                       /* DEVICE */
+    int h, w, mode, reserved;              /* reserved = 0 */
+} rtm3d_jpeg_enc_frame;
+typedef struct rtm3d_jpeg_enc_plan {
+    int first, count;                      /* frames first .. first + count - 1 */
+    int tile_w, tile_h;                    /* 128 x 64 pixels */
+    int threads;                           /* per workgroup */
+    int lds_stride, lds_stride_sub;        /* 144, 72 */
+    int tiles;                             /* tiles of the chunk's largest frame */
+    int grid_x, grid_y;
+} rtm3d_jpeg_enc_plan;
+int rtm3d_frames_jpeg_fdct_plan(int B, const rtm3d_jpeg_enc_frame* h_frames, rtm3d_jpeg_enc_plan* out);
+int rtm3d_frames_jpeg_fdct_check(int B, const rtm3d_jpeg_enc_frame* h_frames, const uint16_t* q_luma, const uint16_t* q_chroma, int src_order);
+int rtm3d_frames_jpeg_fdct(void* stream, int B, const rtm3d_jpeg_enc_frame* h_frames, const uint16_t* q_luma, const uint16_t* q_chroma,
+                           int src_order);
+
+/* The chain: B packed frames h_src[b] on the device ((h, w) = h_hw[2 b], h_hw[2 b + 1]; one mode, one pair of tables, one
+ * restart interval for the batch) to B streams in caller-owned HOST buffers h_out[b][0 .. h_out_capacity[b]), their lengths
+ * in h_out_bytes[b].
+ *   1. every refusal that needs no encoding, for the whole batch, before the first launch: those of the device stage, a
+ *   capacity (bytes of d_coef and of h_stage) below rtm3d_jpeg_encode_workspace_bytes, an output below
+ *   rtm3d_jpeg_encode_bound;  2. per chunk of 32 frames rtm3d_frames_jpeg_fdct into d_coef (frame b at the int16 offset that
+ *   is the sum of the coef_count before it) and one hipMemcpyAsync of the chunk's buffers to the same offset of h_stage;
+ *   3. an event behind the last copy, and the host waits on that event and on nothing else;  4. rtm3d_jpeg_entropy_encode of
+ *   the B buffers on n_threads host threads (0: min(B, 8); at most 64).
+ * The wait is inherent - the result is host bytes.  d_coef is a DEVICE buffer, 128-byte aligned; h_stage caller-owned HOST
+ * memory of as many bytes - pinned, or the copies are not asynchronous.
+ * The two halves are exported for pipelines that encode batch n while batch n + 1 runs: rtm3d_frames_jpeg_encode_queue is
+ * steps 1 (without the outputs) and 2 and waits for nothing; rtm3d_frames_jpeg_encode_finish is step 4 alone, host only,
+ * to be called once an event the CALLER recorded behind the queue call has completed.                                     */
+int rtm3d_jpeg_encode_workspace_bytes(int B, const int* h_hw, int mode, size_t* bytes);
+int rtm3d_frames_jpeg_encode(void* stream, int B, const uint8_t* const* h_src, const int* h_hw, int mode, const uint16_t* q_luma,
+                             const uint16_t* q_chroma, int src_order, int restart, int16_t* d_coef, int16_t* h_stage, size_t capacity,
+                             uint8_t* const* h_out, const size_t* h_out_capacity, size_t* h_out_bytes, int n_threads);
+int rtm3d_frames_jpeg_encode_queue(void* stream, int B, const uint8_t* const* h_src, const int* h_hw, int mode, const uint16_t* q_luma,
+                                   const uint16_t* q_chroma, int src_order, int16_t* d_coef, int16_t* h_stage, size_t capacity);
+int rtm3d_frames_jpeg_encode_finish(int B, const int* h_hw, int mode, int restart, const int16_t* h_stage, uint8_t* const* h_out,
+                                    const size_t* h_out_capacity, size_t* h_out_bytes, int n_threads);
 
 /* ------------------------------------------------------------------ lens undistortion (csrc/lens.hip, csrc/engine.cpp)
  * Every other entry point takes a frame for a pinhole image described by a 3 x 3 K.  A frame of a real camera is one only

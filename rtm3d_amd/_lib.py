@@ -153,6 +153,17 @@ class JpegPlan(ctypes.Structure):
                 ('tiles', c_int), ('grid_x', c_int), ('grid_y', c_int)]
 
 
+class JpegEncFrame(ctypes.Structure):
+    """Mirror of struct rtm3d_jpeg_enc_frame."""
+    _fields_ = [('d_src', c_void_p), ('d_coef', c_void_p), ('h', c_int), ('w', c_int), ('mode', c_int), ('reserved', c_int)]
+
+
+class JpegEncPlan(ctypes.Structure):
+    """Mirror of struct rtm3d_jpeg_enc_plan (one per chunk of 32 frames)."""
+    _fields_ = [('first', c_int), ('count', c_int), ('tile_w', c_int), ('tile_h', c_int), ('threads', c_int), ('lds_stride', c_int),
+                ('lds_stride_sub', c_int), ('tiles', c_int), ('grid_x', c_int), ('grid_y', c_int)]
+
+
 class LensMapC(ctypes.Structure):
     """Mirror of struct rtm3d_lens_map (rtm3d_amd/lens.py)."""
     _fields_ = [('d_map', c_void_p), ('ho', c_int), ('wo', c_int), ('reserved', c_int)]
@@ -283,6 +294,19 @@ SIGNATURES = {
     'rtm3d_frames_jpeg': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int]),
     'rtm3d_engine_detect_frames_jpeg': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                                 c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # JPEG encoding: device colour / DCT / quantisation, host Huffman coding (rtm3d_amd/jpeg.py)
+    'rtm3d_jpeg_quality_tables': (c_int, [c_int, c_void_p, c_void_p]),
+    'rtm3d_jpeg_frame_layout': (c_int, [c_int, c_int, c_int, ctypes.POINTER(JpegInfo)]),
+    'rtm3d_jpeg_encode_bound': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    'rtm3d_jpeg_entropy_encode': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
+    'rtm3d_frames_jpeg_fdct_plan': (c_int, [c_int, ctypes.POINTER(JpegEncFrame), ctypes.POINTER(JpegEncPlan)]),
+    'rtm3d_frames_jpeg_fdct_check': (c_int, [c_int, ctypes.POINTER(JpegEncFrame), c_void_p, c_void_p, c_int]),
+    'rtm3d_frames_jpeg_fdct': (c_int, [c_void_p, c_int, ctypes.POINTER(JpegEncFrame), c_void_p, c_void_p, c_int]),
+    'rtm3d_jpeg_encode_workspace_bytes': (c_int, [c_int, c_void_p, c_int, ctypes.POINTER(c_size_t)]),
+    'rtm3d_frames_jpeg_encode': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                         c_void_p, c_void_p, c_void_p, c_int]),
+    'rtm3d_frames_jpeg_encode_queue': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
+    'rtm3d_frames_jpeg_encode_finish': (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     # lens undistortion: rectifying maps and the bilinear remap (rtm3d_amd/lens.py, rtm3d_amd/engine.py)
     'rtm3d_frames_remap_plan': (c_int, [c_int, ctypes.POINTER(LensMapC), ctypes.POINTER(RemapPlan)]),
     'rtm3d_frames_remap_check': (c_int, [c_int, c_void_p, c_void_p, ctypes.POINTER(LensMapC), c_void_p, c_void_p]),

@@ -401,3 +401,228 @@ extern "C" int rtm3d_jpeg_workspace_bytes(int B, const uint8_t* const* h_data, c
     *bytes = total;
     return 0;
 }
+
+// ==================================================================== JPEG encoding, host side (include/rtm3d_hip.h, "JPEG encoding")
+// The quality tables, the size bound and the Huffman encoder that turns a frame's coefficient buffer - what the device stage
+// (jpeg_enc.hip) wrote - into a baseline stream with libjpeg's marker layout.  Host only, no global state, thread-safe.
+//
+// Safety.  The encoder refuses a capacity below rtm3d_jpeg_encode_bound before it writes a byte; the bound's derivation (in the
+// header) covers every coefficient buffer that passes the category checks, so no write needs a check of its own - one is made
+// per block all the same.  Reads: the two tables and plane + block * 64 + k with the block inside the component's REAL grid,
+// below coef_count by construction.
+namespace {
+
+const uint8_t kBaseLuma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                               18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+const uint8_t kBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+
+#define JPEG_ENC_BLOCK_BYTES 416         // the most one block adds to the stream, stuffing included (see the header)
+
+struct EncHuff { uint16_t code[256]; uint8_t len[256]; };
+
+void enc_build(EncHuff& T, const uint8_t counts[16], const uint8_t* symbols) {
+    memset(&T, 0, sizeof(T));
+    unsigned code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < counts[len - 1]; ++i, ++code, ++k) { T.code[symbols[k]] = (uint16_t)code; T.len[symbols[k]] = (uint8_t)len; }
+        code <<= 1;
+    }
+}
+
+struct EncOut {
+    uint8_t* p;
+    uint64_t acc;                        // the low n bits are not written yet
+    int n;                               // 0..7 between calls
+
+    inline void put(uint32_t bits, int len) {                              // len <= 16 + 11
+        acc = (acc << len) | bits;
+        n += len;
+        while (n >= 8) {
+            const uint8_t b = (uint8_t)(acc >> (n - 8));
+            *p++ = b;
+            if (b == 0xFF) *p++ = 0;
+            n -= 8;
+        }
+    }
+    inline void flush() { if (n) put((1u << (8 - n)) - 1u, 8 - n); }      // the last byte is padded with 1-bits
+};
+
+inline int category(int v) { const unsigned a = (unsigned)(v < 0 ? -v : v); return a ? 32 - __builtin_clz(a) : 0; }
+
+uint8_t* put_segment(uint8_t* p, int marker, const uint8_t* body, size_t n) {
+    *p++ = 0xFF; *p++ = (uint8_t)marker; *p++ = (uint8_t)((n + 2) >> 8); *p++ = (uint8_t)((n + 2) & 255);
+    memcpy(p, body, n);
+    return p + n;
+}
+
+int enc_frame_info(int h, int w, int mode, rtm3d_jpeg_stream_info& I, char* msg, size_t msg_len) {
+    if (mode < RTM3D_JPEG_GREY || mode > RTM3D_JPEG_420) JFAIL("the unknown mode %d", mode);
+    if (h < 1 || w < 1 || h > JPEG_MAX_SIDE || w > JPEG_MAX_SIDE) JFAIL("a frame of %d x %d; a side must lie in 1..%d", h, w, JPEG_MAX_SIDE);
+    memset(&I, 0, sizeof(I));
+    I.h = h; I.w = w; I.mode = mode; I.components = mode == RTM3D_JPEG_GREY ? 1 : 3;
+    fill_layout(I);
+    return 0;
+}
+
+size_t enc_header_bytes(int components, int restart) {
+    const size_t nt = components == 3 ? 2 : 1;
+    return 2 + 18 + 69 * nt + (10 + 3 * (size_t)components) + (33 + 183) * nt + (restart ? 6 : 0) + (8 + 2 * (size_t)components);
+}
+
+}  // namespace
+
+int rt_jpeg_frame_layout(int h, int w, int mode, rtm3d_jpeg_stream_info* out, char* msg, size_t msg_len) {
+    return enc_frame_info(h, w, mode, *out, msg, msg_len);
+}
+
+int rt_jpeg_encode_bound(int h, int w, int mode, int restart, size_t* bytes, char* msg, size_t msg_len) {
+    rtm3d_jpeg_stream_info I;
+    if (enc_frame_info(h, w, mode, I, msg, msg_len)) return 1;
+    if (restart < 0 || restart > 65535) JFAIL("a restart interval of %d MCUs; 0 (none) .. 65535", restart);
+    const size_t mcus = (size_t)I.mcus_x * I.mcus_y;
+    const size_t per_mcu = (size_t)(I.bw[0] / I.mcus_x) * (size_t)(I.bh[0] / I.mcus_y) + (I.components == 3 ? 2 : 0);
+    const size_t n_rst = restart ? (mcus - 1) / (size_t)restart : 0;
+    *bytes = enc_header_bytes(I.components, restart) + JPEG_ENC_BLOCK_BYTES * mcus * per_mcu + 2 * n_rst + 2;
+    return 0;
+}
+
+int rt_jpeg_entropy_encode(const int16_t* h_coef, int h, int w, int mode, int restart, uint8_t* out, size_t capacity, size_t* bytes, char* msg,
+                           size_t msg_len) {
+    rtm3d_jpeg_stream_info I;
+    size_t bound = 0;
+    if (rt_jpeg_encode_bound(h, w, mode, restart, &bound, msg, msg_len)) return 1;
+    if (!h_coef || !out || !bytes) JFAIL("null pointer");
+    if (capacity < bound) JFAIL("the output holds %zu bytes, a stream of this frame may need %zu (rtm3d_jpeg_encode_bound)", capacity, bound);
+    enc_frame_info(h, w, mode, I, msg, msg_len);
+    const int nt = I.components == 3 ? 2 : 1, H = I.bw[0] / I.mcus_x, V = I.bh[0] / I.mcus_y;
+    for (int t = 0; t < nt; ++t)
+        for (int k = 0; k < 64; ++k) {
+            const unsigned q = (uint16_t)h_coef[64 * t + k];
+            if (q < 1 || q > 255) JFAIL("entry %d of quantisation table %d is %u; a baseline table holds 1..255", k, t, q);
+        }
+    EncHuff dc[2], ac[2];
+    enc_build(dc[0], kStdDcLumaCounts, kStdDcSymbols); enc_build(ac[0], kStdAcLumaCounts, kStdAcLumaSymbols);
+    enc_build(dc[1], kStdDcChromaCounts, kStdDcSymbols); enc_build(ac[1], kStdAcChromaCounts, kStdAcChromaSymbols);
+    // ---- the headers, in libjpeg's order: SOI APP0 DQT.. SOF0 DHT.. [DRI] SOS
+    uint8_t* p = out;
+    uint8_t body[200];
+    *p++ = 0xFF; *p++ = 0xD8;
+    static const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    p = put_segment(p, 0xE0, jfif, sizeof(jfif));
+    for (int t = 0; t < nt; ++t) {
+        body[0] = (uint8_t)t;
+        for (int i = 0; i < 64; ++i) body[1 + i] = (uint8_t)h_coef[64 * t + kZigzag[i]];
+        p = put_segment(p, 0xDB, body, 65);
+    }
+    body[0] = 8; body[1] = (uint8_t)(h >> 8); body[2] = (uint8_t)(h & 255); body[3] = (uint8_t)(w >> 8); body[4] = (uint8_t)(w & 255);
+    body[5] = (uint8_t)I.components;
+    for (int c = 0; c < I.components; ++c) {
+        body[6 + 3 * c] = (uint8_t)(c + 1);
+        body[7 + 3 * c] = (uint8_t)(c == 0 && I.components == 3 ? (H << 4) | V : 0x11);
+        body[8 + 3 * c] = (uint8_t)(c ? 1 : 0);
+    }
+    p = put_segment(p, 0xC0, body, 6 + 3 * (size_t)I.components);
+    for (int t = 0; t < nt; ++t) {
+        body[0] = (uint8_t)t;
+        memcpy(body + 1, t ? kStdDcChromaCounts : kStdDcLumaCounts, 16); memcpy(body + 17, kStdDcSymbols, 12);
+        p = put_segment(p, 0xC4, body, 29);
+        body[0] = (uint8_t)(0x10 | t);
+        memcpy(body + 1, t ? kStdAcChromaCounts : kStdAcLumaCounts, 16); memcpy(body + 17, t ? kStdAcChromaSymbols : kStdAcLumaSymbols, 162);
+        p = put_segment(p, 0xC4, body, 179);
+    }
+    if (restart) { body[0] = (uint8_t)(restart >> 8); body[1] = (uint8_t)(restart & 255); p = put_segment(p, 0xDD, body, 2); }
+    body[0] = (uint8_t)I.components;
+    for (int c = 0; c < I.components; ++c) { body[1 + 2 * c] = (uint8_t)(c + 1); body[2 + 2 * c] = (uint8_t)(c ? 0x11 : 0x00); }
+    body[1 + 2 * I.components] = 0; body[2 + 2 * I.components] = 63; body[3 + 2 * I.components] = 0;
+    p = put_segment(p, 0xDA, body, 4 + 2 * (size_t)I.components);
+    // ---- the scan
+    int rw[3], rh[3];                                                       // the REAL block grid of every component
+    for (int c = 0; c < I.components; ++c) {
+        const int hc = c == 0 ? H : 1, vc = c == 0 ? V : 1;
+        rw[c] = (((w * hc + H - 1) / H) + 7) / 8; rh[c] = (((h * vc + V - 1) / V) + 7) / 8;
+    }
+    EncOut o = {p, 0, 0};
+    const uint8_t* const end = out + capacity;
+    const int n_mcu = I.mcus_x * I.mcus_y;
+    int pred[3] = {0, 0, 0}, rst = 0, mx = 0, my = 0;
+    for (int mcu = 0; mcu < n_mcu; ++mcu) {
+        if (restart && mcu && mcu % restart == 0) {
+            o.flush();
+            *o.p++ = 0xFF; *o.p++ = (uint8_t)(0xD0 + rst);
+            rst = (rst + 1) & 7;
+            pred[0] = pred[1] = pred[2] = 0;
+        }
+        for (int c = 0; c < I.components; ++c) {
+            const int hc = c == 0 ? H : 1, vc = c == 0 ? V : 1, t = c ? 1 : 0;
+            for (int v = 0; v < vc; ++v) {
+                for (int u = 0; u < hc; ++u) {
+                    if ((size_t)(end - o.p) < JPEG_ENC_BLOCK_BYTES) JFAIL("the output is full at MCU %d (a bound that does not hold)", mcu);
+                    const int bx = mx * hc + u, by = my * vc + v;
+                    if (bx >= rw[c] || by >= rh[c]) {                       // a padding block: difference 0, end of block; the buffer is not read
+                        o.put(dc[t].code[0], dc[t].len[0]);
+                        o.put(ac[t].code[0], ac[t].len[0]);
+                        continue;
+                    }
+                    const int16_t* blk = h_coef + I.plane_offset[c] + ((size_t)by * I.bw[c] + (size_t)bx) * 64;
+                    const int diff = (int)blk[0] - pred[c];
+                    pred[c] = blk[0];
+                    int s = category(diff);
+                    if (s > 11) JFAIL("a DC difference of %d (MCU %d, component %d): category %d, baseline has 0..11", diff, mcu, c, s);
+                    o.put(dc[t].code[s], dc[t].len[s]);
+                    if (s) o.put((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1u), s);
+                    int run = 0;
+                    for (int k = 1; k < 64; ++k) {
+                        const int a = blk[kZigzag[k]];
+                        if (a == 0) { ++run; continue; }
+                        for (; run > 15; run -= 16) o.put(ac[t].code[0xF0], ac[t].len[0xF0]);
+                        s = category(a);
+                        if (s > 10) JFAIL("an AC coefficient of %d (MCU %d, component %d): category %d, baseline has 1..10", a, mcu, c, s);
+                        o.put(ac[t].code[(run << 4) | s], ac[t].len[(run << 4) | s]);
+                        o.put((uint32_t)(a < 0 ? a - 1 : a) & ((1u << s) - 1u), s);
+                        run = 0;
+                    }
+                    if (run) o.put(ac[t].code[0], ac[t].len[0]);
+                }
+            }
+        }
+        if (++mx == I.mcus_x) { mx = 0; ++my; }
+    }
+    o.flush();
+    *o.p++ = 0xFF; *o.p++ = 0xD9;
+    *bytes = (size_t)(o.p - out);
+    return 0;
+}
+
+extern "C" int rtm3d_jpeg_quality_tables(int quality, uint16_t* q_luma, uint16_t* q_chroma) {
+    if (!q_luma || !q_chroma) { rt_set_error("jpeg_quality_tables: null pointer"); return 1; }
+    if (quality < 1 || quality > 100) { rt_set_error("jpeg_quality_tables: quality %d; 1..100", quality); return 1; }
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int k = 0; k < 64; ++k) {
+        const int a = (kBaseLuma[k] * scale + 50) / 100, b = (kBaseChroma[k] * scale + 50) / 100;
+        q_luma[k] = (uint16_t)(a < 1 ? 1 : a > 255 ? 255 : a);
+        q_chroma[k] = (uint16_t)(b < 1 ? 1 : b > 255 ? 255 : b);
+    }
+    return 0;
+}
+
+extern "C" int rtm3d_jpeg_frame_layout(int h, int w, int mode, rtm3d_jpeg_stream_info* out) {
+    char msg[200];
+    if (!out) { rt_set_error("jpeg_frame_layout: null pointer"); return 1; }
+    if (rt_jpeg_frame_layout(h, w, mode, out, msg, sizeof(msg))) { rt_set_error("jpeg_frame_layout: %s", msg); return 1; }
+    return 0;
+}
+
+extern "C" int rtm3d_jpeg_encode_bound(int h, int w, int mode, int restart, size_t* bytes) {
+    char msg[200];
+    if (!bytes) { rt_set_error("jpeg_encode_bound: null pointer"); return 1; }
+    if (rt_jpeg_encode_bound(h, w, mode, restart, bytes, msg, sizeof(msg))) { rt_set_error("jpeg_encode_bound: %s", msg); return 1; }
+    return 0;
+}
+
+extern "C" int rtm3d_jpeg_entropy_encode(const int16_t* h_coef, int h, int w, int mode, int restart, uint8_t* out, size_t capacity, size_t* bytes) {
+    char msg[200];
+    if (rt_jpeg_entropy_encode(h_coef, h, w, mode, restart, out, capacity, bytes, msg, sizeof(msg))) { rt_set_error("jpeg_entropy_encode: %s", msg); return 1; }
+    return 0;
+}

@@ -198,3 +198,12 @@ def to_ppm(path, image):
     with open(path, 'wb') as f:
         f.write(b'P6\n%d %d\n255\n' % (a.shape[1], a.shape[0]))
         f.write(a.tobytes())
+
+
+def to_jpeg(path, image, quality=90, mode='420', order='rgb'):
+    """Write a uint8 (h, w, 3) CUDA tensor as a baseline JPEG file through rtm3d_amd.jpeg.encode (device DCT, host Huffman coding;
+    no image library).  order: the byte order of a pixel of ``image``."""
+    from . import jpeg
+    if not isinstance(image, torch.Tensor) or not image.is_cuda:
+        raise ValueError('to_jpeg: a uint8 (h, w, 3) CUDA tensor (to_ppm writes host arrays)')
+    jpeg.write_files([path], jpeg.encode([image.contiguous()], quality=quality, mode=mode, order=order))

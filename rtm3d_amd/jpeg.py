@@ -3,7 +3,12 @@ what recorded driving sets ship as files - become the tightly packed uint8 (h, w
 lens.remap, preprocess_batch and the drawing entry points read.  The Huffman decoding runs on the host, threaded over the
 frames of a batch (rtm3d_jpeg_entropy_decode); dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the
 device, one launch per 32 frames (rtm3d_frames_jpeg_idct).  No image library is involved.  The integer rule - libjpeg's default
-decode, bit for bit - is written out in the header; tests/jpeg_ref.py restates it in numpy."""
+decode, bit for bit - is written out in the header; tests/jpeg_ref.py restates it in numpy.
+
+JPEG encoding (the header's "JPEG encoding") is the way back: packed frames - painted ones, bird's-eye panels - become baseline
+streams byte for byte as libjpeg writes them.  Colour conversion, downsampling, forward DCT and quantisation run on the device
+(rtm3d_frames_jpeg_fdct), the Huffman coding on host threads (rtm3d_jpeg_entropy_encode); encode() is the chain, Encoder its
+two halves for pipelines; tests/jpeg_enc_ref.py restates the rule in numpy."""
 import ctypes
 
 import numpy as np
@@ -189,3 +194,207 @@ def read_files(paths):
         with open(p, 'rb') as f:
             out.append(f.read())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- encoding
+def _mode(mode):
+    if isinstance(mode, str):
+        if mode.lower() not in MODES:
+            raise ValueError("unknown mode %r ('grey', '444', '422' or '420')" % (mode,))
+        return MODES[mode.lower()]
+    return int(mode)                     # a number is passed on: the library refuses what it does not know
+
+
+def quality_tables(quality):
+    """rtm3d_jpeg_quality_tables (host only): (luma, chroma), two uint16 arrays of 64 in natural order, for quality 1..100."""
+    luma, chroma = np.empty(64, np.uint16), np.empty(64, np.uint16)
+    _lib.check(_lib.load().rtm3d_jpeg_quality_tables(int(quality), luma.ctypes.data, chroma.ctypes.data), 'jpeg_quality_tables')
+    return luma, chroma
+
+
+def _tables(quality, tables):
+    if tables is None:
+        return quality_tables(quality)
+    luma, chroma = [np.ascontiguousarray(np.asarray(t).reshape(-1)) for t in tables]
+    for t in (luma, chroma):
+        if t.size != 64 or t.dtype.kind not in 'iu' or t.min() < 0 or t.max() > 65535:
+            raise ValueError('a quantisation table is 64 integers in natural order (the library accepts 1..255)')
+    return luma.astype(np.uint16), chroma.astype(np.uint16)
+
+
+def frame_layout(h, w, mode):
+    """rtm3d_jpeg_frame_layout (host only): the dict info() gives for a stream of an (h, w, mode) frame."""
+    out = _lib.JpegInfo()
+    _lib.check(_lib.load().rtm3d_jpeg_frame_layout(int(h), int(w), _mode(mode), ctypes.byref(out)), 'jpeg_frame_layout')
+    n = out.components
+    return dict(h=out.h, w=out.w, components=n, mode=MODE_NAMES[out.mode], restart_interval=0, mcus_x=out.mcus_x, mcus_y=out.mcus_y,
+                bw=list(out.bw)[:n], bh=list(out.bh)[:n], table_offset=list(out.table_offset)[:n], plane_offset=list(out.plane_offset)[:n],
+                coef_count=out.coef_count)
+
+
+def encode_bound(h, w, mode, restart=0):
+    """rtm3d_jpeg_encode_bound (host only): an upper bound of the bytes of the stream of an (h, w, mode) frame."""
+    n = ctypes.c_size_t()
+    _lib.check(_lib.load().rtm3d_jpeg_encode_bound(int(h), int(w), _mode(mode), int(restart), ctypes.byref(n)), 'jpeg_encode_bound')
+    return n.value
+
+
+def entropy_encode(coef, h, w, mode, restart=0):
+    """rtm3d_jpeg_entropy_encode (host only): a coefficient buffer (int16 numpy array, its tables included) -> the stream as bytes."""
+    coef = np.ascontiguousarray(coef)
+    if coef.dtype != np.int16 or coef.ndim != 1 or coef.size < frame_layout(h, w, mode)['coef_count']:
+        raise ValueError('a coefficient buffer is an int16 array of at least frame_layout(h, w, mode)["coef_count"]')
+    out = np.empty(encode_bound(h, w, mode, restart), np.uint8)
+    n = ctypes.c_size_t()
+    _lib.check(_lib.load().rtm3d_jpeg_entropy_encode(coef.ctypes.data, int(h), int(w), _mode(mode), int(restart), out.ctypes.data, out.size,
+                                                     ctypes.byref(n)), 'jpeg_entropy_encode')
+    return out[:n.value].tobytes()
+
+
+def c_enc_frames(frames):
+    """[(uint8 CUDA tensor (h, w, 3) or its address, int16 CUDA tensor for the coefficient buffer or its address, h, w, mode)] ->
+    ctypes array of rtm3d_jpeg_enc_frame."""
+    arr = (_lib.JpegEncFrame * len(frames))()
+    for i, (src, coef, h, w, mode) in enumerate(frames):
+        arr[i].d_src = src if isinstance(src, int) else src.data_ptr()
+        arr[i].d_coef = coef if isinstance(coef, int) else coef.data_ptr()
+        arr[i].h, arr[i].w, arr[i].reserved = int(h), int(w), 0
+        arr[i].mode = _mode(mode)
+    return arr
+
+
+def fdct_plan(frames):
+    """rtm3d_frames_jpeg_fdct_plan: the launch schedule of fdct, one JpegEncPlan per chunk of 32 frames (host only; ``frames``: what
+    c_enc_frames takes, or its result)."""
+    arr = frames if isinstance(frames, ctypes.Array) else c_enc_frames(frames)
+    out = (_lib.JpegEncPlan * ((len(arr) + CHUNK - 1) // CHUNK))()
+    _lib.check(_lib.load().rtm3d_frames_jpeg_fdct_plan(len(arr), arr, out), 'frames_jpeg_fdct_plan')
+    return list(out)
+
+
+def _frame_list(frames):
+    """A list of contiguous uint8 (h, w, 3) CUDA tensors, or one (B, h, w, 3) tensor -> the list of its frames (views)."""
+    import torch
+    if isinstance(frames, torch.Tensor):
+        if frames.dim() == 3:
+            frames = [frames]
+        elif frames.dim() == 4:
+            frames = [frames[b] for b in range(frames.shape[0])]
+    frames = list(frames)
+    if not frames:
+        raise ValueError('expected a non-empty list of frames')
+    for f in frames:
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or not f.is_cuda or f.dim() != 3 or f.shape[2] != 3 or not f.is_contiguous():
+            raise ValueError('a frame is a contiguous uint8 (h, w, 3) CUDA tensor')
+    return frames
+
+
+def fdct(frames, modes='420', quality=90, tables=None, order='rgb'):
+    """rtm3d_frames_jpeg_fdct, the device stage alone: frames (what encode takes) -> list of int16 CUDA tensors, one coefficient
+    buffer per frame.  modes: one mode, or one per frame."""
+    import torch
+    frames = _frame_list(frames)
+    modes = [modes] * len(frames) if isinstance(modes, (str, int)) else list(modes)
+    luma, chroma = _tables(quality, tables)
+    dev = frames[0].device
+    with torch.cuda.device(dev):
+        out = [torch.empty(frame_layout(f.shape[0], f.shape[1], m)['coef_count'], dtype=torch.int16, device=dev) for f, m in zip(frames, modes)]
+        arr = c_enc_frames([(f, o, f.shape[0], f.shape[1], m) for f, o, m in zip(frames, out, modes)])
+        _lib.check(_lib.load().rtm3d_frames_jpeg_fdct(_lib.stream_ptr(dev), len(frames), arr, luma.ctypes.data, chroma.ctypes.data, _order(order)),
+                   'frames_jpeg_fdct')
+    return out
+
+
+_enc_sets = {}                           # device -> [two _Staging, the index of the next]
+
+
+def _enc_staging(device, nbytes):
+    entry = _enc_sets.setdefault(str(device), [[_Staging(), _Staging()], 0])
+    s = entry[0][entry[1]]
+    entry[1] ^= 1
+    return s, s.ready(nbytes, device)
+
+
+class Encoder(object):
+    """The chain in its two halves: submit(frames) queues the device stage and the copies of a batch behind the current stream
+    and returns at once (rtm3d_frames_jpeg_encode_queue, then an event); collect() waits on the OLDEST submitted batch's event
+    and on nothing else and Huffman-encodes it on the host (rtm3d_frames_jpeg_encode_finish) -> list of bytes.  Two staging sets
+    alternate, so one batch may be in flight while the one before it is collected: at most two batches are pending."""
+
+    def __init__(self, quality=90, mode='420', order='rgb', restart=0, tables=None, threads=0):
+        self.mode, self.order, self.restart, self.threads = _mode(mode), _order(order), int(restart), int(threads)
+        self.luma, self.chroma = _tables(quality, tables)
+        self.sets, self.next, self.pending = [_Staging(), _Staging()], 0, []
+
+    def submit(self, frames):
+        import torch
+        if len(self.pending) >= 2:
+            raise RuntimeError('jpeg.Encoder: two batches are pending; collect() one first')
+        frames = _frame_list(frames)
+        dev = frames[0].device
+        hw = _lib.hw_array(frames)
+        lib = _lib.load()
+        n = ctypes.c_size_t()
+        _lib.check(lib.rtm3d_jpeg_encode_workspace_bytes(len(frames), hw, self.mode, ctypes.byref(n)), 'jpeg_encode_workspace_bytes')
+        bounds = [encode_bound(f.shape[0], f.shape[1], self.mode, self.restart) for f in frames]     # refuses a bad restart before any launch
+        s = self.sets[self.next]
+        self.next ^= 1
+        with torch.cuda.device(dev):
+            cap = s.ready(n.value, dev)
+            _lib.check(lib.rtm3d_frames_jpeg_encode_queue(_lib.stream_ptr(dev), len(frames), _lib.ptr_array(frames), hw, self.mode, self.luma.ctypes.data,
+                                                          self.chroma.ctypes.data, self.order, s.dev.data_ptr(), s.host.data_ptr(), cap), 'frames_jpeg_encode')
+            s.event = torch.cuda.Event()
+            s.event.record(torch.cuda.current_stream(dev))
+        self.pending.append((s, len(frames), hw, bounds, frames))          # (the frames stay alive until their kernels have run)
+
+    def collect(self):
+        if not self.pending:
+            raise RuntimeError('jpeg.Encoder: nothing was submitted')
+        s, B, hw, bounds, _ = self.pending.pop(0)
+        s.event.synchronize()                                              # the one wait: the result is host bytes
+        outs = [np.empty(b, np.uint8) for b in bounds]
+        ptrs = (ctypes.c_void_p * B)(*[o.ctypes.data for o in outs])
+        caps = (ctypes.c_size_t * B)(*bounds)
+        lens = (ctypes.c_size_t * B)()
+        _lib.check(_lib.load().rtm3d_frames_jpeg_encode_finish(B, hw, self.mode, self.restart, s.host.data_ptr(), ptrs, caps, lens, self.threads),
+                   'frames_jpeg_encode')
+        return [o[:n].tobytes() for o, n in zip(outs, lens)]
+
+
+def encode(frames, quality=90, mode='420', order='rgb', restart=0, tables=None, threads=0):
+    """rtm3d_frames_jpeg_encode: contiguous uint8 (h, w, 3) CUDA tensors - a list, or one (B, h, w, 3) tensor such as the bird's-eye
+    panels - -> list of bytes, one baseline JPEG stream per frame, byte for byte what libjpeg writes for these pixels, tables and
+    sampling (Huffman tables not optimised).  quality 1..100 or ``tables`` = (luma, chroma), 64 entries of 1..255 in natural order;
+    mode 'grey' | '444' | '422' | '420'; order: the byte order of a pixel in the frames, 'rgb' | 'bgr'; restart: MCUs between
+    restart markers, 0 = none; threads: host threads of the Huffman coding, 0 = min(B, 8).  The call waits for its own copies
+    (the result is host bytes); one refused frame refuses the batch before anything is launched."""
+    import torch
+    frames = _frame_list(frames)
+    dev = frames[0].device
+    mode_, hw, lib = _mode(mode), _lib.hw_array(frames), _lib.load()
+    luma, chroma = _tables(quality, tables)
+    B = len(frames)
+    n = ctypes.c_size_t()
+    _lib.check(lib.rtm3d_jpeg_encode_workspace_bytes(B, hw, mode_, ctypes.byref(n)), 'jpeg_encode_workspace_bytes')
+    bounds = [encode_bound(f.shape[0], f.shape[1], mode_, restart) for f in frames]
+    outs = [np.empty(b, np.uint8) for b in bounds]
+    ptrs = (ctypes.c_void_p * B)(*[o.ctypes.data for o in outs])
+    caps = (ctypes.c_size_t * B)(*bounds)
+    lens = (ctypes.c_size_t * B)()
+    with torch.cuda.device(dev):
+        s, cap = _enc_staging(dev, n.value)
+        _lib.check(lib.rtm3d_frames_jpeg_encode(_lib.stream_ptr(dev), B, _lib.ptr_array(frames), hw, mode_, luma.ctypes.data, chroma.ctypes.data,
+                                                _order(order), int(restart), s.dev.data_ptr(), s.host.data_ptr(), cap, ptrs, caps, lens, int(threads)),
+                   'frames_jpeg_encode')
+        s.event = None                                                     # the call has waited for its copies already
+    return [o[:k].tobytes() for o, k in zip(outs, lens)]
+
+
+def write_files(paths, streams):
+    """Write every stream to its path."""
+    paths, streams = list(paths), list(streams)
+    if len(paths) != len(streams):
+        raise ValueError('%d paths for %d streams' % (len(paths), len(streams)))
+    for p, s in zip(paths, streams):
+        with open(p, 'wb') as f:
+            f.write(s)
