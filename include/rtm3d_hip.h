@@ -1730,6 +1730,96 @@ int rtm3d_rig_fuse(void* stream, int R, int C, int topk, int cap, const float* d
 int rtm3d_rig_scatter_ids(void* stream, int R, int C, int topk, int cap, const int32_t* d_map, const int32_t* d_ids_rig,
                           int32_t* d_ids_cam);
 
+/* ---- validation loss ------------------------------------------------------------------------------------------------
+ * The number the reference selects checkpoints by (train.py:61-81): KITTI label rows -> the targets of
+ * datasets/dataset_reader.py:215-291 (utils/data_utils.py:7-18, 97-141) -> the loss of models/rtm3d_loss.py:268-340
+ * (models/nets/module.py:41-68, utils/model_utils.py:10-14).  Forward value only: no gradient.
+ *
+ * INPUT.  N objects, sorted by image: d_obj [N][RTM3D_LOSS_ROW] fp64, one row per object
+ *   [0] img_id, 0 <= img_id < B, non-decreasing      [1] cls: the index into DATASET.OBJs, or -1, which sets mask = 0
+ *   [2] noise (0 / 1)      [3:7] bbox x1 y1 x2 y2 in network-input pixels (after the caller's resize and letterbox), x2 >= x1 and
+ *   y2 >= y1 (the caller's to ensure: the radius of a reversed box is not defined; the Python wrapper refuses it)
+ *   [7:10] dimension h w l      [10:13] location, the KITTI bottom centre      [13] Ry      [14] sin(Ry)  [15] cos(Ry) as the
+ *   HOST computed them: the device's fp64 sine is not every host's to the last bit, and the table below is defined bit for bit
+ *   [16] mask_3d: 0 / 1 supplied by the caller, or -1 = derive it      [17] reserved, 0
+ * d_K [B][9] fp64, one row-major K per image, in input pixels.  d_img_start [B + 1] int32: the objects of image b are the rows
+ * d_img_start[b] .. d_img_start[b + 1] - 1.
+ * Class mapping (the host's work, _transform_obj_label, dataset_reader.py:197-213): a type in DATASET.OBJs is one row of its
+ * class, noise 0; a type listed in DATASET.RELATE_OBJs[k] becomes one NOISE row of class k per list that contains it (with the
+ * defaults, Person_sitting becomes two rows); everything else becomes one row with cls = -1.
+ *
+ * PER OBJECT (the table d_table [N][RTM3D_LOSS_TABLE] fp64): fp64, the operation order written here, no contraction; sums and
+ * products associate left to right unless bracketed; ds = MODEL.DOWN_SAMPLE; trunc rounds toward zero as astype(long) does.
+ *   x1, y1, x2, y2 = bbox / ds;  cx = (x1 + x2) / 2, cy = (y1 + y2) / 2;  m_proj = trunc(centre);  m_off = centre - m_proj
+ *   radius (_compute_gaussian_radius, min_overlap mo = 0.7):  hh = ceil(y2 - y1), ww = ceil(x2 - x1)
+ *     b1 = hh + ww                c1 = ww * hh * (1 - mo) / (1 + mo)    r1 = (b1 + sqrt(b1 * b1 - 4 * c1)) / 2
+ *     b2 = 2 * (hh + ww)          c2 = (1 - mo) * ww * hh               r2 = (b2 + sqrt(b2 * b2 - 16 * c2)) / 2
+ *     b3 = (-2 * mo) * (hh + ww)  c3 = (mo - 1) * ww * hh               r3 = (b3 + sqrt(b3 * b3 - (4 * (4 * mo)) * c3)) / 2
+ *     r = min(r1, r2, r3);  sigma = (2 * r + 1) / 6;  R = ceil(r);  inv = 1 / (2 * (sigma * sigma))
+ *     Only DATASET.GAUSSIAN_GEN_TYPE = 'dynamic_radius' exists here ('dynamic_sigma' cannot run in the reference either).
+ *   vertices: k = K with its first two rows divided by ds;  s = sin(Ry), c = cos(Ry), each set to 0 where its magnitude is
+ *     below 1e-3 (rotation_matrix);  the 8 corners are csrc/box_project.h's box_project_corner of x = [s, c, l, h, w, X, Y - h / 2,
+ *     Z] - corner j = 4 i_x + 2 i_y + i_z with sign +1 for a 0 bit, (u, v) = (k[0:3] . P, k[3:6] . P) / (k[6:9] . P + 1e-6)
+ *     v_proj = trunc(v);  v_off = v - v_proj;  v_coor_off = v - centre;  v_mask = v_proj inside [0, W) x [0, H)
+ *   mask_3d: the caller's, or "all eight corners have camera depth ((-s * l / 2) * sx + (c * w / 2) * sz) + Z > 0".  PARITY
+ *     UNPINNED: the reference takes this mask from a KITTI devkit module that its tree does not contain.
+ *   mask = cls >= 0 (and img_id inside 0 .. B - 1: a row of no image takes no part).
+ * Table columns: 0 img  1 cls  2 mask  3 noise  4 mask_3d  5 m_proj inside the map  6:8 centre  8:10 m_proj  10:12 m_off  12 r
+ *   13 sigma  14 R  15 inv  16:32 vertices [8][2]  32:48 v_proj  48:64 v_off  64:80 v_coor_off  80:88 v_mask.
+ *
+ * HEAT-MAP TARGET m_hm[b][c][y][x] = the maximum over the objects i of image b with mask = 1, cls = c, |x - mx| <= R and
+ * |y - my| <= R (the full square, no circular cut) of g_i = exp(-((dx * dx + dy * dy) * inv)) in fp64, replaced by 0.9999 at
+ * the centre of a noise object; 0 where no object reaches; rounded to fp32 once.  The centre of a non-noise object is therefore
+ * exactly 1.0f, which the focal loss's target.eq(1) depends on.  An object whose centre lies outside the map still paints the
+ * cells its square reaches.
+ *
+ * LOSS.  Element terms fp32 as in the reference, every sum fp64 in an order that depends on the sizes only.
+ *   p = clamp(1 / (1 + expf(-x)), 1e-4f, 0.9999f) of the heat-map logit x (a NaN stays a NaN);  t = the target
+ *   t == 1: pos += logf(p) * (1 - p)^alpha, num_pos += 1;   t < 1: neg += (logf(1 - p) * p^alpha) * (1 - t)^beta
+ *   alpha = 2 and beta = 4 are squares ((v * v) * (v * v)), other values powf.  num_pos counts the whole batch.
+ *   main = -(pos + neg) / num_pos, or -neg when num_pos = 0.
+ *   The three L1 terms are means over their selections (rtm3d_loss.py:300-329), each |prediction - (float)target| in fp32:
+ *     ver_coor   the raw 16 ver_coor logits at m_proj, channels 2 j, 2 j + 1 against v_coor_off of vertex j, for the objects with
+ *                mask and not noise and mask_3d, of those the vertices with v_mask
+ *     vertex_off sigmoid of the 2 v_off logits at v_proj against v_off, the same objects and vertices
+ *     main_off   sigmoid of the 2 m_off logits at m_proj against m_off, for the objects with mask and not noise
+ *   An empty selection gives NaN (F.l1_loss of nothing; the reference's test_epoch stops on it).  An object with mask and not
+ *   noise whose m_proj lies outside the map - the reference would raise or wrap there - is left out of the three terms and
+ *   counted in n_outside.
+ *   d_out [5] fp32: W_MKF * main, W_VFM * ver_coor, W_M_OFF * main_off, W_V_OFF * vertex_off (each term rounded to fp32, times
+ *   the fp32 weight) and their fp32 sum in this order.  d_counts [5] int32: num_pos, the vertices of ver_coor, the vertices of
+ *   vertex_off, the objects of main_off, n_outside.  NaN or infinite logits propagate into the result; nothing faults on them.
+ *
+ * rtm3d_loss_objects: one lane per object, writes d_table.  rtm3d_loss_heatmap: m_hm [B][C][H][W] fp32 from the table, for
+ * inspection and tests - rtm3d_loss_eval never writes the map: a workgroup takes an image and a band of rows, stages that
+ * image's objects in LDS in chunks of 128 (no cap on the objects of an image), forms each cell's target as it reads the logit
+ * (16 bytes per lane when W % 4 == 0 and d_hm is 16-byte aligned) and leaves one fp64 triple (pos, neg, num_pos) in its own
+ * slot of d_ws (the byte count: rtm3d_loss_workspace_bytes); one wave then adds the slots - lane l the slots l, l + 64, ... in
+ * index order, the lanes by a fixed butterfly - gathers the regression logits, writes d_out / d_counts and, with d_accum
+ * [2] fp64 not NULL, adds total * B and B into it (test_epoch's mloss and num).  No atomics: two calls on the same inputs are
+ * bit-identical.  d_ws and d_accum belong to one stream at a time (d_accum is updated by a plain read-modify-write).  d_ver_coor [B][16][H][W], d_m_off [B][2][H][W], d_v_off [B][2][H][W], d_hm [B][C][H][W]: the four fp32 logit
+ * maps.  H, W must be those the table was built with.  All stream-ordered without host synchronisation, except
+ * rtm3d_loss_accum_read, which copies d_accum to h_sum_count [2] and waits for the stream; rtm3d_loss_accum_reset zeroes it.
+ * Refused before a launch, non-zero with the reason in rtm3d_last_error: B or C outside 1..65535, H, W < 1, N outside
+ * 0..RTM3D_LOSS_MAX_OBJECTS, a NULL pointer, alpha or beta outside (0, 64], a NaN weight, down_sample outside (0, 1e6]. */
+#define RTM3D_LOSS_ROW 18
+#define RTM3D_LOSS_TABLE 88
+#define RTM3D_LOSS_MAX_OBJECTS (1 << 20)
+typedef struct rtm3d_loss_params {
+    float alpha, beta;              /* MODEL.FOCAL_LOSS_ALPHA, MODEL.FOCAL_LOSS_BEDA */
+    float weight[4];                /* TRAINING.W_MKF, W_VFM, W_M_OFF, W_V_OFF */
+} rtm3d_loss_params;
+int rtm3d_loss_objects(void* stream, int N, int B, const double* d_obj, const double* d_K, double down_sample, int H, int W,
+                       double* d_table);
+int rtm3d_loss_heatmap(void* stream, int B, int C, int H, int W, const int32_t* d_img_start, const double* d_table, int N,
+                       float* d_hm);
+size_t rtm3d_loss_workspace_bytes(int B, int C, int H, int W);
+int rtm3d_loss_eval(void* stream, int B, int C, int H, int W, const float* d_hm, const float* d_ver_coor, const float* d_m_off,
+                    const float* d_v_off, const int32_t* d_img_start, const double* d_table, int N,
+                    const rtm3d_loss_params* params, void* d_ws, float* d_out, int32_t* d_counts, double* d_accum);
+int rtm3d_loss_accum_reset(void* stream, double* d_accum);
+int rtm3d_loss_accum_read(void* stream, const double* d_accum, double* h_sum_count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,11 @@ class RigParamsC(ctypes.Structure):
                 ('thresh', c_double), ('min_score', c_double)]
 
 
+class LossParamsC(ctypes.Structure):
+    """Mirror of struct rtm3d_loss_params (rtm3d_amd/loss.py)."""
+    _fields_ = [('alpha', c_float), ('beta', c_float), ('weight', c_float * 4)]
+
+
 class PreprocessPlan(ctypes.Structure):
     """Mirror of struct rtm3d_preprocess_plan (one per sub-batch of 64 images)."""
     _fields_ = [('first', c_int), ('count', c_int), ('col_bytes', c_int), ('stage_bytes', c_int), ('band_rows', c_int), ('bands', c_int),
@@ -348,6 +353,14 @@ SIGNATURES = {
     'rtm3d_rig_fuse': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(RigParamsC), c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
     'rtm3d_rig_scatter_ids': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # validation loss: KITTI labels -> targets -> RTM3D loss (rtm3d_amd/loss.py)
+    'rtm3d_loss_objects': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_double, c_int, c_int, c_void_p]),
+    'rtm3d_loss_heatmap': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    'rtm3d_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'rtm3d_loss_eval': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                ctypes.POINTER(LossParamsC), c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rtm3d_loss_accum_reset': (c_int, [c_void_p, c_void_p]),
+    'rtm3d_loss_accum_read': (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_double)]),
 }
 
 _lib = None
