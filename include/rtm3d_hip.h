@@ -1733,7 +1733,8 @@ int rtm3d_rig_scatter_ids(void* stream, int R, int C, int topk, int cap, const i
 /* ---- validation loss ------------------------------------------------------------------------------------------------
  * The number the reference selects checkpoints by (train.py:61-81): KITTI label rows -> the targets of
  * datasets/dataset_reader.py:215-291 (utils/data_utils.py:7-18, 97-141) -> the loss of models/rtm3d_loss.py:268-340
- * (models/nets/module.py:41-68, utils/model_utils.py:10-14).  Forward value only: no gradient.
+ * (models/nets/module.py:41-68, utils/model_utils.py:10-14).  This block is the forward value; its gradient with respect to the
+ * logits is the next block, "loss gradient".
  *
  * INPUT.  N objects, sorted by image: d_obj [N][RTM3D_LOSS_ROW] fp64, one row per object
  *   [0] img_id, 0 <= img_id < B, non-decreasing      [1] cls: the index into DATASET.OBJs, or -1, which sets mask = 0
@@ -1819,6 +1820,54 @@ int rtm3d_loss_eval(void* stream, int B, int C, int H, int W, const float* d_hm,
                     const rtm3d_loss_params* params, void* d_ws, float* d_out, int32_t* d_counts, double* d_accum);
 int rtm3d_loss_accum_reset(void* stream, double* d_accum);
 int rtm3d_loss_accum_read(void* stream, const double* d_accum, double* h_sum_count);
+
+/* ---- loss gradient --------------------------------------------------------------------------------------------------
+ * The gradient of total (d_out[4] of rtm3d_loss_eval) with respect to every element of the four fp32 logit maps, times an
+ * upstream scalar u (d_upstream: one fp32 on the device, NULL = 1): what loss.backward() of the reference's train_epoch leaves
+ * in the logits.  Element terms are fp32 in the operation order written here (no contraction, brackets as shown, otherwise left
+ * to right); there is no fp64 sum.  The symbols are those of "validation loss".
+ *
+ * HEAT MAP, every cell.  t = the target, formed exactly as the forward forms it (0.9999 at a noise centre, the test t == 1 on
+ * the fp32 value: where a huge Gaussian rounds a neighbour to 1.0f, that cell is a positive here too).
+ *   s = 1 / (1 + expf(-x));  p = clamp(s, 1e-4f, 0.9999f);  in = (s >= 1e-4f) && (s <= 0.9999f), the bounds inclusive as in the
+ *   backward of torch's clamp;  q = 1 - p
+ *   t == 1:  dp = q^alpha / p - (alpha * q^(alpha - 1)) * logf(p)
+ *   t <  1:  dp = (-(p^alpha) / q + (alpha * p^(alpha - 1)) * logf(q)) * (1 - t)^beta
+ *   alpha = 2 and beta = 4: v^alpha = v * v, v^(alpha - 1) = v, v^beta = (v * v) * (v * v); other values powf(v, alpha),
+ *   powf(v, alpha - 1.0f), powf(v, beta)
+ *   k = -((u * W_MKF) / (float)max(num_pos, 1));   g = (k * (in ? dp : 0)) * (s * (1 - s))
+ *   num_pos is d_counts[0], what the forward left on the device - not recomputed.  A NaN logit gives a NaN in its own cell only
+ *   (0 * NaN); +-inf and saturated logits give exactly 0 (of either sign).
+ * REGRESSION MAPS.  sign(d) = 1, -1 or +0 for d > 0, d < 0, d == 0, and d itself for a NaN (torch's sign gives 0 there: a NaN
+ * logit would go unseen).  n_* are d_counts[1], [2], [3].  The selections are the forward's, object by object and vertex by vertex:
+ *   ver_coor   channels 2 j + e at m_proj:   sign(x - (float)v_coor_off) * k_vc,                  k_vc = (u * W_VFM) / (2.0f * n_ver_coor)
+ *   main_off   channels e at m_proj:         (sign(s - (float)m_off) * (s * (1 - s))) * k_mo,     k_mo = (u * W_M_OFF) / (2.0f * n_main_off)
+ *   vertex_off channels e at v_proj:         (sign(s - (float)v_off) * (s * (1 - s))) * k_vo,     k_vo = (u * W_V_OFF) / (2.0f * n_vertex_off)
+ *   with s = (float)(1 / (1 + exp(-(double)x))) here: the sigmoid through fp64, rounded to fp32 once.  The contributions to one
+ *   element differ in their signs only, so whether a run of them cancels to exactly zero hangs on the last bit of s; an expf
+ *   differs from library to library in that bit, this value does not (measured: one element of the 150-object test case was an
+ *   ulp-sized residue on the device and 0 in numpy with expf).  Every element of the three maps starts as +0.0f and the contributions to it are
+ *   added in fp32 in rising object order, then rising vertex order (two objects on one m_proj cell, several vertices that
+ *   truncate to one v_proj cell); an element nothing contributes to is +0.0f.  An object counted in n_outside contributes
+ *   nothing; an empty selection contributes nothing - its forward item is NaN, the maps stay finite, as autograd leaves them.
+ * Every element of every requested output is written: the caller need not clear them.  No floating-point atomics; two calls on
+ * the same inputs are bit-identical.
+ *
+ * rtm3d_loss_grad: two launches, stream-ordered, no host synchronisation, no workspace.  The dense pass has the forward's
+ * decomposition (a workgroup per image and band of rows, the image's objects in LDS in chunks of 128; 16 bytes per lane in and
+ * out when W % 4 == 0 and d_hm and d_g_hm are 16-byte aligned, cell by cell otherwise), reads each logit and writes its gradient,
+ * and clears its band of the 20 regression channels (16-byte stores under the same condition per map).  The sparse pass runs
+ * behind it: a workgroup per image takes the image's objects 64 at a time, puts every contribution's element and value in LDS,
+ * and the first contribution to an element within the 64 reads the element, adds the others in order and writes it - one writer
+ * per element, the groups of 64 one after the other; an image's objects are the rows d_img_start gives it (their table image
+ * must be that image).  d_counts [5]: rtm3d_loss_eval's, of the same inputs, read on the device.  Any of the four outputs may be
+ * NULL: not wanted, not computed.  Refused before a launch with the reason in rtm3d_last_error: what rtm3d_loss_eval refuses
+ * of sizes, pointers and parameters, 16 * H * W beyond an int index, a NULL d_counts, all four outputs NULL, an output pointer
+ * equal to an input pointer.  Second derivatives do not exist. */
+int rtm3d_loss_grad(void* stream, int B, int C, int H, int W, const float* d_hm, const float* d_ver_coor, const float* d_m_off,
+                    const float* d_v_off, const int32_t* d_img_start, const double* d_table, int N, const rtm3d_loss_params* params,
+                    const int32_t* d_counts, const float* d_upstream, float* d_g_hm, float* d_g_ver_coor, float* d_g_m_off,
+                    float* d_g_v_off);
 
 #ifdef __cplusplus
 }

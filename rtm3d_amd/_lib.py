@@ -359,6 +359,8 @@ SIGNATURES = {
     'rtm3d_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'rtm3d_loss_eval': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                 ctypes.POINTER(LossParamsC), c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rtm3d_loss_grad': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                ctypes.POINTER(LossParamsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rtm3d_loss_accum_reset': (c_int, [c_void_p, c_void_p]),
     'rtm3d_loss_accum_read': (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_double)]),
 }

@@ -5,7 +5,10 @@
 //                        and a band of rows, keeps that image's objects in LDS and forms each cell's target as it reads the
 //                        logit - then one wave that sums the partials in a fixed order, gathers the regression logits of the
 //                        three L1 terms and writes the five losses and the counts;
-//   rtm3d_loss_heatmap   the target map itself, from the same device function (inspection and tests).
+//   rtm3d_loss_heatmap   the target map itself, from the same device function (inspection and tests);
+//   rtm3d_loss_grad      the gradient of the total with respect to the four logit maps ("loss gradient"): a dense pass with the
+//                        focal kernel's decomposition that turns each heat-map logit into its gradient and clears the regression
+//                        maps, then a sparse pass that adds the L1 terms' contributions in a fixed order, one writer per element.
 // The table is fp64 in the operation order the header writes out, compiled with -ffp-contract=off (Makefile) so that numpy
 // restates it bit for bit; the projection of the corners is box_project.h's, the one statement of the corner order the 3D decode
 // fits against.  Element terms of the loss are fp32 as in the reference, every sum is fp64 and no result depends on the order in
@@ -320,6 +323,227 @@ __global__ __launch_bounds__(64) void loss_finish_kernel(int B, int H, int W, in
     if (accum) { accum[0] += (double)total * (double)B; accum[1] += (double)B; }
 }
 
+// ---- loss gradient (include/rtm3d_hip.h, "loss gradient") -------------------------------------------------------------------
+#define LG_BATCH 64            // objects of one image the sparse pass resolves at a time
+#define LG_VERTS (LG_BATCH * 8)
+
+template <bool SQ> __device__ __forceinline__ float ls_pow1(float v, float e) { return SQ ? v : powf(v, e - 1.0f); }
+
+// The sigmoid of the sparse pass, through fp64 and rounded to fp32 once: the contributions to one element differ in sign only,
+// so whether a run of them cancels to exactly zero hangs on the last bit of s - this one is the same on every device and host.
+__device__ __forceinline__ float ls_sigmoid_cr(float x) { return (float)(1.0 / (1.0 + exp(-(double)x))); }
+
+// sign with sign(0) = +0; a NaN stays a NaN, so a NaN logit shows in its own element
+__device__ __forceinline__ float ls_sign(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : (d == d ? 0.f : d)); }
+
+// +0.0f into rows y0 .. y0 + rows - 1 of the ch channels of image b: 16-byte stores where the map allows them
+__device__ __forceinline__ void ls_zero_band(float* g, int ch, int b, int H, int W, int y0, int rows, bool vec, int tid) {
+    const size_t hw = (size_t)H * W;
+    float* base = g + ((size_t)b * ch * H + y0) * W;                            // channel c of the band: base + c * hw
+    const int plane = rows * W;
+    if (vec) {
+        const int q = plane / 4, n = ch * q;                                     // W % 4 == 0: whole float4s
+        for (int i = tid; i < n; i += LS_THREADS) {
+            const int c = i / q, r = i - c * q;
+            *reinterpret_cast<float4*>(base + c * hw + 4 * (size_t)r) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    } else {
+        const int n = ch * plane;
+        for (int i = tid; i < n; i += LS_THREADS) {
+            const int c = i / plane, r = i - c * plane;
+            base[c * hw + r] = 0.f;
+        }
+    }
+}
+
+// The dense pass: loss_focal_kernel's decomposition (one workgroup per image and band of rows, the image's objects in LDS), but
+// each cell's logit becomes its gradient instead of a term of a sum; the same workgroup clears its band of the regression maps.
+// g_hm, g_vc, g_mo, g_vo: NULL = not wanted.  zvec: bit 0 / 1 / 2 = g_vc / g_mo / g_vo take 16-byte stores.
+template <bool SQ, bool VEC>
+__global__ __launch_bounds__(LS_THREADS) void loss_grad_dense_kernel(int C, int H, int W, int band_rows, const float* __restrict__ hm,
+                                                                     const int32_t* __restrict__ img_start, const double* __restrict__ tab,
+                                                                     int N, float alpha, float beta, float w_mkf,
+                                                                     const int32_t* __restrict__ counts, const float* __restrict__ up,
+                                                                     float* __restrict__ g_hm, float* g_vc, float* g_mo, float* g_vo, int zvec) {
+    __shared__ LsObj objs[LS_CHUNK];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int y0 = blockIdx.x * band_rows;
+    const int rows = (y0 + band_rows <= H ? band_rows : H - y0);
+    if (g_vc) ls_zero_band(g_vc, 16, b, H, W, y0, rows, (zvec & 1) != 0, tid);
+    if (g_mo) ls_zero_band(g_mo, 2, b, H, W, y0, rows, (zvec & 2) != 0, tid);
+    if (g_vo) ls_zero_band(g_vo, 2, b, H, W, y0, rows, (zvec & 4) != 0, tid);
+    if (!g_hm) return;                                                           // (uniform over the grid)
+    const int plane = rows * W, cells = C * plane;
+    int o0, nobj;
+    ls_img_range(img_start, b, N, o0, nobj);
+    const bool single = nobj <= LS_CHUNK;
+    if (single) {
+        if (tid < nobj) objs[tid] = ls_load_obj(tab + (size_t)(o0 + tid) * LS_TAB);
+        __syncthreads();
+    }
+    const int np = counts[0];
+    const float u = up ? up[0] : 1.0f;
+    const float ks = -((u * w_mkf) / (float)(np > 1 ? np : 1));
+    const float* img = hm + (size_t)b * C * H * W;
+    float* gimg = g_hm + (size_t)b * C * H * W;
+    for (int base = 0; base < cells; base += LS_THREADS * LS_CELLS) {
+        int cc[LS_CELLS], yy[LS_CELLS], xx[LS_CELLS];
+        float lg[LS_CELLS];
+        double m[LS_CELLS];
+        size_t at[VEC ? 1 : LS_CELLS];
+        if (VEC) {
+            const int idx = base + tid * LS_CELLS;                               // cells is a multiple of 4 here: all four or none
+            const bool ok = idx < cells;
+            const int c = ok ? idx / plane : 0, rem = ok ? idx - c * plane : 0, y = rem / W, x = rem - y * W;
+            at[0] = ((size_t)c * H + y0 + y) * W + x;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ok) v = *reinterpret_cast<const float4*>(img + at[0]);
+            lg[0] = v.x; lg[1] = v.y; lg[2] = v.z; lg[3] = v.w;
+#pragma unroll
+            for (int k = 0; k < LS_CELLS; ++k) { cc[k] = ok ? c : -2; yy[k] = y0 + y; xx[k] = x + k; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < LS_CELLS; ++k) {
+                const int idx = base + k * LS_THREADS + tid;
+                const bool ok = idx < cells;
+                const int c = ok ? idx / plane : 0, rem = ok ? idx - c * plane : 0, y = rem / W, x = rem - y * W;
+                at[k] = ((size_t)c * H + y0 + y) * W + x;
+                lg[k] = ok ? img[at[k]] : 0.f;
+                cc[k] = ok ? c : -2; yy[k] = y0 + y; xx[k] = x;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < LS_CELLS; ++k) m[k] = 0.0;
+        for (int ob = 0; ob < nobj; ob += LS_CHUNK) {
+            const int cnt = nobj - ob < LS_CHUNK ? nobj - ob : LS_CHUNK;
+            if (!single) {                                                       // (uniform over the workgroup)
+                __syncthreads();
+                if (tid < cnt) objs[tid] = ls_load_obj(tab + (size_t)(o0 + ob + tid) * LS_TAB);
+                __syncthreads();
+            }
+            for (int i = 0; i < cnt; ++i) {
+                const LsObj o = objs[i];
+#pragma unroll
+                for (int k = 0; k < LS_CELLS; ++k) m[k] = ls_cover(o, cc[k], yy[k], xx[k], m[k]);
+            }
+        }
+        float g[LS_CELLS];
+#pragma unroll
+        for (int k = 0; k < LS_CELLS; ++k) {
+            const float t = (float)m[k];
+            const float s = ls_sigmoid(lg[k]);
+            const float p = s < 1e-4f ? 1e-4f : (s > 0.9999f ? 0.9999f : s);     // a NaN stays a NaN
+            const bool in = s >= 1e-4f && s <= 0.9999f;                          // (false for a NaN)
+            const float q = 1.0f - p;
+            float dp;
+            if (t == 1.0f) dp = ls_pow<SQ>(q, alpha, false) / p - (alpha * ls_pow1<SQ>(q, alpha)) * logf(p);
+            else dp = (-ls_pow<SQ>(p, alpha, false) / q + (alpha * ls_pow1<SQ>(p, alpha)) * logf(q)) * ls_pow<SQ>(1.0f - t, beta, true);
+            g[k] = (ks * (in ? dp : 0.0f)) * (s * (1.0f - s));
+        }
+        if (VEC) {
+            if (cc[0] >= 0) *reinterpret_cast<float4*>(gimg + at[0]) = make_float4(g[0], g[1], g[2], g[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < LS_CELLS; ++k)
+                if (cc[k] >= 0) gimg[at[k]] = g[k];
+        }
+    }
+}
+
+// The sparse pass, behind the dense one on the same stream: one workgroup per image walks that image's objects LG_BATCH at a
+// time.  Every contribution of a batch - its element (a cell key) and its fp32 value - goes to LDS; a contribution no earlier one
+// of the batch shares its element with owns the element: it reads the element, adds the batch's contributions to it in rising
+// (object, vertex) order and writes it back.  One writer per element and batch, the batches one after the other behind a
+// barrier: the sums are those of a serial walk, without atomics.  Elements of different images never meet.
+__global__ __launch_bounds__(LS_THREADS) void loss_grad_sparse_kernel(int B, int H, int W, const float* __restrict__ vc,
+                                                                      const float* __restrict__ moff, const float* __restrict__ voff,
+                                                                      const int32_t* __restrict__ img_start, const double* __restrict__ tab,
+                                                                      int N, float w_vfm, float w_moff, float w_voff,
+                                                                      const int32_t* __restrict__ counts, const float* __restrict__ up,
+                                                                      float* g_vc, float* g_mo, float* g_vo) {
+    __shared__ int mkey[LG_BATCH];                                               // the object's m_proj cell, -1: takes no part
+    __shared__ int vkey[LG_VERTS];                                               // the vertex's v_proj cell, -1: takes no part
+    __shared__ float c_mo[LG_BATCH][2], c_vc[LG_VERTS][2], c_vo[LG_VERTS][2];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    int o0, nobj;
+    ls_img_range(img_start, b, N, o0, nobj);
+    const float u = up ? up[0] : 1.0f;
+    const float k_vc = (u * w_vfm) / (2.0f * (float)counts[1]);
+    const float k_vo = (u * w_voff) / (2.0f * (float)counts[2]);
+    const float k_mo = (u * w_moff) / (2.0f * (float)counts[3]);
+    const size_t hw = (size_t)H * W;
+    for (int ob = 0; ob < nobj; ob += LG_BATCH) {
+        const int cnt = nobj - ob < LG_BATCH ? nobj - ob : LG_BATCH;
+        if (ob) __syncthreads();                                                 // the last batch's elements are written, its LDS is read
+        for (int c = tid; c < cnt * 8; c += LS_THREADS) {
+            const int i = c >> 3, j = c & 7;
+            const double* t = tab + (size_t)(o0 + ob + i) * LS_TAB;
+            const double mxd = t[T_MX], myd = t[T_MY], vx = t[T_VPROJ + 2 * j], vy = t[T_VPROJ + 2 * j + 1];
+            const bool sel = t[T_MASK] != 0.0 && t[T_NOISE] == 0.0 && t[T_IMG] == (double)b;
+            const bool use = sel && mxd >= 0.0 && mxd < (double)W && myd >= 0.0 && myd < (double)H;
+            const bool ok = use && t[T_MASK3D] != 0.0 && t[T_VMASK + j] != 0.0 && vx >= 0.0 && vx < (double)W && vy >= 0.0 && vy < (double)H;
+            const int cell = use ? (int)myd * W + (int)mxd : 0, vcell = ok ? (int)vy * W + (int)vx : 0;
+            if (j == 0) {
+                mkey[i] = use ? cell : -1;
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const float s = ls_sigmoid_cr(moff[((size_t)b * 2 + e) * hw + cell]);
+                    c_mo[i][e] = (ls_sign(s - (float)t[T_MOFF + e]) * (s * (1.0f - s))) * k_mo;
+                }
+            }
+            vkey[c] = ok ? vcell : -1;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const float x = vc[((size_t)b * 16 + 2 * j + e) * hw + cell];
+                const float s = ls_sigmoid_cr(voff[((size_t)b * 2 + e) * hw + vcell]);
+                c_vc[c][e] = ls_sign(x - (float)t[T_VCOOR + 2 * j + e]) * k_vc;
+                c_vo[c][e] = (ls_sign(s - (float)t[T_VOFF + 2 * j + e]) * (s * (1.0f - s))) * k_vo;
+            }
+        }
+        __syncthreads();
+        if (g_mo && tid < cnt && mkey[tid] >= 0) {
+            const int key = mkey[tid];
+            bool own = true;
+            for (int i = 0; i < tid; ++i) own = own && mkey[i] != key;
+            if (own) {
+                float* e0 = g_mo + ((size_t)b * 2) * hw + key;
+                float a0 = e0[0], a1 = e0[hw];
+                for (int i = tid; i < cnt; ++i)
+                    if (mkey[i] == key) { a0 += c_mo[i][0]; a1 += c_mo[i][1]; }
+                e0[0] = a0; e0[hw] = a1;
+            }
+        }
+        for (int c = tid; c < cnt * 8; c += LS_THREADS) {
+            if (vkey[c] < 0) continue;
+            const int i0 = c >> 3, j = c & 7;
+            if (g_vc) {                                                          // channels 2 j, 2 j + 1 at m_proj: the objects on one cell
+                const int key = mkey[i0];
+                bool own = true;
+                for (int i = 0; i < i0; ++i) own = own && !(mkey[i] == key && vkey[i * 8 + j] >= 0);
+                if (own) {
+                    float* e0 = g_vc + ((size_t)b * 16 + 2 * j) * hw + key;
+                    float a0 = e0[0], a1 = e0[hw];
+                    for (int i = i0; i < cnt; ++i)
+                        if (mkey[i] == key && vkey[i * 8 + j] >= 0) { a0 += c_vc[i * 8 + j][0]; a1 += c_vc[i * 8 + j][1]; }
+                    e0[0] = a0; e0[hw] = a1;
+                }
+            }
+            if (g_vo) {                                                          // channels 0, 1 at v_proj: any vertices on one cell
+                const int key = vkey[c];
+                bool own = true;
+                for (int d = 0; d < c; ++d) own = own && vkey[d] != key;
+                if (own) {
+                    float* e0 = g_vo + ((size_t)b * 2) * hw + key;
+                    float a0 = e0[0], a1 = e0[hw];
+                    for (int d = c; d < cnt * 8; ++d)
+                        if (vkey[d] == key) { a0 += c_vo[d][0]; a1 += c_vo[d][1]; }
+                    e0[0] = a0; e0[hw] = a1;
+                }
+            }
+        }
+    }
+}
+
 extern void rt_set_error(const char* fmt, ...);
 
 static int ls_band_rows(int B, int H) {
@@ -399,6 +623,48 @@ extern "C" int rtm3d_loss_eval(void* stream, int B, int C, int H, int W, const f
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(64), 0, s, B, H, W, bands * B, slots, d_ver_coor, d_m_off, d_v_off, d_table, N,
                        params->weight[0], params->weight[1], params->weight[2], params->weight[3], d_out, d_counts, d_accum);
     return ls_launched("loss_eval (finish)");
+}
+
+extern "C" int rtm3d_loss_grad(void* stream, int B, int C, int H, int W, const float* d_hm, const float* d_ver_coor, const float* d_m_off,
+                               const float* d_v_off, const int32_t* d_img_start, const double* d_table, int N,
+                               const rtm3d_loss_params* params, const int32_t* d_counts, const float* d_upstream, float* d_g_hm,
+                               float* d_g_ver_coor, float* d_g_m_off, float* d_g_v_off) {
+    if (!ls_sizes_ok("loss_grad", B, C, H, W, N)) return 1;
+    if ((long long)16 * H * W > 0x7fffffffLL / 2) { rt_set_error("loss_grad: a map of 16 x %d x %d cells is more than an int index holds", H, W); return 1; }
+    if (!d_hm || !d_ver_coor || !d_m_off || !d_v_off || !d_img_start || !params || (N > 0 && !d_table)) {
+        rt_set_error("loss_grad: null pointer");
+        return 1;
+    }
+    if (!d_counts) { rt_set_error("loss_grad: null d_counts (rtm3d_loss_eval's counts of the same inputs)"); return 1; }
+    const float alpha = params->alpha, beta = params->beta;
+    if (!(alpha > 0.f) || !(beta > 0.f) || alpha > 64.f || beta > 64.f) { rt_set_error("loss_grad: focal alpha %g / beta %g", alpha, beta); return 1; }
+    for (int k = 0; k < 4; ++k)
+        if (params->weight[k] != params->weight[k]) { rt_set_error("loss_grad: weight %d is NaN", k); return 1; }
+    const void* outs[4] = {d_g_hm, d_g_ver_coor, d_g_m_off, d_g_v_off};
+    const void* ins[8] = {d_hm, d_ver_coor, d_m_off, d_v_off, d_img_start, d_table, d_counts, d_upstream};
+    if (!d_g_hm && !d_g_ver_coor && !d_g_m_off && !d_g_v_off) { rt_set_error("loss_grad: no output wanted (all four are NULL)"); return 1; }
+    for (int o = 0; o < 4; ++o)
+        for (int i = 0; i < 8; ++i)
+            if (outs[o] && outs[o] == ins[i]) { rt_set_error("loss_grad: output %d is input %d (the gradient is not formed in place)", o, i); return 1; }
+    const int rb = ls_band_rows(B, H), bands = (H + rb - 1) / rb;
+    const bool sq = alpha == 2.f && beta == 4.f;
+    auto al16 = [&](const void* p) { return (W % 4) == 0 && (reinterpret_cast<uintptr_t>(p) % 16) == 0; };
+    const bool vec = al16(d_hm) && al16(d_g_hm);
+    const int zvec = (al16(d_g_ver_coor) ? 1 : 0) | (al16(d_g_m_off) ? 2 : 0) | (al16(d_g_v_off) ? 4 : 0);
+    const dim3 grid(bands, B), block(LS_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+#define LG_LAUNCH(SQ, VEC) hipLaunchKernelGGL((loss_grad_dense_kernel<SQ, VEC>), grid, block, 0, s, C, H, W, rb, d_hm, d_img_start, d_table, N, \
+                                              alpha, beta, params->weight[0], d_counts, d_upstream, d_g_hm, d_g_ver_coor, d_g_m_off, d_g_v_off, zvec)
+    if (sq && vec) LG_LAUNCH(true, true);
+    else if (sq) LG_LAUNCH(true, false);
+    else if (vec) LG_LAUNCH(false, true);
+    else LG_LAUNCH(false, false);
+#undef LG_LAUNCH
+    if (ls_launched("loss_grad (dense)")) return 1;
+    if (N == 0 || (!d_g_ver_coor && !d_g_m_off && !d_g_v_off)) return 0;
+    hipLaunchKernelGGL(loss_grad_sparse_kernel, dim3(B), block, 0, s, B, H, W, d_ver_coor, d_m_off, d_v_off, d_img_start, d_table, N,
+                       params->weight[1], params->weight[2], params->weight[3], d_counts, d_upstream, d_g_ver_coor, d_g_m_off, d_g_v_off);
+    return ls_launched("loss_grad (sparse)");
 }
 
 extern "C" int rtm3d_loss_accum_reset(void* stream, double* d_accum) {

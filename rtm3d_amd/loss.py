@@ -6,8 +6,10 @@ the label rows are packed on the host into one fp64 row per object (``LabelBatch
 fields from them (``build_targets``: m_proj, m_off, v_proj, v_off, v_coor_off, v_mask, mask_3d and, for inspection, m_hm) and
 ``RTM3DLoss(cfg)(pred_logits, batch)`` evaluates the loss of models/rtm3d_loss.py:268-340 on the four logit maps of
 ``Model.forward`` without ever writing the heat-map target.  ``ValidationLoss`` keeps test_epoch's running sum on the device:
-``add`` does no host synchronisation, ``result()`` synchronises once.  Forward value only - there is no gradient and no
-training loop.  Device tensors only: there is no CPU path.
+``add`` does no host synchronisation, ``result()`` synchronises once.  The loss is differentiable with respect to the four
+logit maps (the header's "loss gradient", rtm3d_loss_grad): with logits that require grad, ``loss`` carries a ``grad_fn`` and
+``loss.backward()`` is the line that follows it in the reference's train_epoch; ``RTM3DLoss.grad`` is the same gradient
+without autograd.  There is no second derivative, no optimiser and no training loop.  Device tensors only: there is no CPU path.
 
 ``mask_3d`` is "all eight corners in front of the camera" unless the caller supplies it: PARITY UNPINNED, the reference takes
 it from a KITTI devkit module that its tree does not contain.
@@ -248,8 +250,14 @@ class RTM3DLoss:
     stream, no host synchronisation - but the first call with a batch uploads its rows (``LabelBatch.to``: asynchronous) and
     launches its table kernel; do both ahead with ``batch.to(device).table(H, W)`` where that matters.  An empty selection
     gives NaN, as F.l1_loss of nothing does in the reference.
+    When grad mode is on and any of the four maps requires grad, ``loss`` carries a ``grad_fn`` (a once-differentiable autograd
+    node; ``loss_items`` stays detached, as in the reference): its backward is rtm3d_loss_grad on the current stream - two more
+    launches, the upstream gradient passed as a device scalar, only the maps that need a gradient computed, no host
+    synchronisation.  Otherwise, and under ``torch.no_grad()``, the call is the forward alone, value for value and launch for
+    launch.  ``grad(pred_logits, batch, upstream)`` returns the same four gradients without autograd.
     ONE STREAM PER OBJECT: the workspace is cached per shape and reused by every call, so calls through one RTM3DLoss must be
-    issued on one stream (or be ordered by the caller); use one object per stream."""
+    issued on one stream (or be ordered by the caller); use one object per stream.  That holds for the backward too: it reads the
+    ``counts`` its forward left on the device, so ``loss.backward()`` belongs on the stream of the call that made ``loss``."""
 
     def __init__(self, cfg=None):
         _check_gaussian_type(cfg)
@@ -262,6 +270,7 @@ class RTM3DLoss:
         self._params = _lib.LossParamsC(self.alpha, self.beta, (ctypes.c_float * 4)(*self.weights))
         self._ws = {}
         self.counts = None
+        self._items = None                   # loss_items of the last call that went through autograd
 
     def _check(self, pred_logits, batch):
         import torch
@@ -305,7 +314,83 @@ class RTM3DLoss:
         return items[4], items
 
     def __call__(self, pred_logits, targets):
-        return self._eval(pred_logits, targets, None)
+        import torch
+        pred = tuple(pred_logits)
+        if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in pred):
+            loss = _loss_function().apply(self, targets, *self._check(pred, targets)[0])
+            return loss, self._items
+        return self._eval(pred, targets, None)
+
+    def grad(self, pred_logits, batch, upstream=None, counts=None, want=(True, True, True, True), out=None):
+        """The gradient of ``loss`` with respect to the four logit maps, times ``upstream`` (a float, a one-element fp32 device
+        tensor, or None = 1) - rtm3d_loss_grad, the explicit path without autograd: -> four tensors shaped like the maps (None
+        where ``want`` is false).  ``counts``: the ``counts`` an earlier forward call on the same inputs left; without it
+        the forward is evaluated first.  ``out``: four preallocated contiguous fp32 tensors (or None each) to write into.
+        Two launches on the current stream, no host synchronisation, every element written."""
+        import torch
+        pred, B, C, H, W = self._check(pred_logits, batch)
+        dev = pred[0].device
+        if counts is None:
+            with torch.no_grad():
+                self._eval(pred, batch, None)
+            counts = self.counts
+        if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.numel() != 5 or counts.device != dev or not counts.is_contiguous():
+            raise ValueError('RTM3DLoss.grad: counts must be the (5,) int32 tensor of a forward call on %s' % dev)
+        want = tuple(bool(w) for w in want)
+        if len(want) != 4 or not any(want):
+            raise ValueError('RTM3DLoss.grad: want must hold four flags, at least one of them set')
+        if upstream is not None:
+            if isinstance(upstream, torch.Tensor):
+                if upstream.numel() != 1:
+                    raise ValueError('RTM3DLoss.grad: upstream must be one value, got shape %s' % (tuple(upstream.shape),))
+                upstream = upstream.detach().reshape(1).to(device=dev, dtype=torch.float32).contiguous()
+            else:
+                upstream = torch.full((1,), float(upstream), dtype=torch.float32, device=dev)
+        batch.to(dev)
+        tab = batch.table(H, W)
+        with torch.cuda.device(dev):
+            outs = []
+            for k, (p, w) in enumerate(zip(pred, want)):
+                o = out[k] if out is not None and w else None
+                if o is not None and (not isinstance(o, torch.Tensor) or o.shape != p.shape or o.dtype != torch.float32 or o.device != dev
+                                      or not o.is_contiguous()):
+                    raise ValueError('RTM3DLoss.grad: out[%d] must be a contiguous fp32 tensor %s on %s' % (k, tuple(p.shape), dev))
+                outs.append(o if o is not None else (torch.empty_like(p.detach()) if w else None))
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            _lib.check(_lib.load().rtm3d_loss_grad(_lib.stream_ptr(dev), B, C, H, W, pred[0].data_ptr(), pred[1].data_ptr(), pred[2].data_ptr(),
+                                                   pred[3].data_ptr(), batch._dev[2].data_ptr(), tab.data_ptr(), batch.N,
+                                                   ctypes.byref(self._params), counts.data_ptr(), ptr(upstream), *[ptr(o) for o in outs]),
+                       'loss_grad')
+        return tuple(outs)
+
+
+_LossFunction = None
+
+
+def _loss_function():
+    """The autograd node of RTM3DLoss.__call__ (made on first use: this module imports without torch)."""
+    global _LossFunction
+    if _LossFunction is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class _LossFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, fn, batch, hm, ver_coor, m_off, v_off):
+                pred = (hm, ver_coor, m_off, v_off)
+                loss, items = fn._eval(pred, batch, None)
+                fn._items = items
+                ctx.fn, ctx.batch, ctx.counts = fn, batch, fn.counts
+                ctx.save_for_backward(*pred)
+                return loss.clone()              # (not a view of loss_items, which stays a plain detached tensor)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad_loss):
+                want = ctx.needs_input_grad[2:6]
+                return (None, None) + ctx.fn.grad(ctx.saved_tensors, ctx.batch, upstream=grad_loss, counts=ctx.counts, want=want)
+
+    return _LossFunction
 
 
 class ValidationLoss:
