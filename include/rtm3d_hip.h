@@ -1869,6 +1869,114 @@ int rtm3d_loss_grad(void* stream, int B, int C, int H, int W, const float* d_hm,
                     const int32_t* d_counts, const float* d_upstream, float* d_g_hm, float* d_g_ver_coor, float* d_g_m_off,
                     float* d_g_v_off);
 
+/* ------------------------------------------------------------------ training augmentation (csrc/augment.hip, csrc/philox.h)
+ * The front of the chain uint8 frames -> network input -> logits -> loss -> gradient: the reference's TrainAugmentation
+ * (preprocess/data_preprocess.py: RandomBrightnessContrast, GaussNoise, RemoveBadBBox, Resize, RandomAffine(range (1, 1.2),
+ * offset 0), RandomMirror), then _apply_padding and Normalize, for B packed uint8 (h, w, 3) frames at once.  The pixels are made
+ * here; the labels move in step on the host (rtm3d_amd/augment.py).  One interior launch per chunk of 32 frames, then one border
+ * launch per chunk, descriptors by value, stream-ordered, no host synchronisation; the canvas is written directly, no
+ * intermediate image exists.  Added in ABI 9 without changing any existing declaration.
+ *
+ * THE RULE is "the reference's photometric steps applied to the SOURCE frame, then ONE bilinear resample through the composed
+ * Resize, RandomAffine and RandomMirror map, then letterbox and normalise".  One interpolation where the reference does two
+ * (cv2.resize, then cv2.warpAffine) is a deliberate deviation: a second resampling only blurs.  Integers only (int64 where
+ * stated, otherwise int32; >> is arithmetic); tests/augment_ref.py restates it in numpy.  Frame of h x w pixels, source byte v
+ * at source pixel p = j * w + i (column i, row j), channel c:
+ *   BRIGHTNESS / CONTRAST   L = clamp((v * alpha_q + beta_q) >> 16, 0, 255), the product and sum in int64.  alpha_q =
+ *     round(alpha * 65536), beta_q = round(beta * 255 * 65536): albumentations' uint8 table with brightness_by_max.  The
+ *     identity is alpha_q = 65536, beta_q = 0.
+ *   NOISE   sigma_q == 0: a = L, nothing is drawn.  Otherwise r[0..3] = Philox4x32-10 of counter (p, 0, 0, 0) and key (seed_lo,
+ *     seed_hi);  n = (T[r[c] >> 20] * sigma_q + 32768) >> 16;  a = clamp(L + n, 0, 255).  T is plain data, 4096 int16 on the
+ *     device, T[k] = round(1024 * Phi^-1((k + 0.5) / 4096)) (Phi the standard normal distribution function); sigma_q =
+ *     round(sigma * 64).  rtm3d_augment_noise_table builds T on the host in fp64 with an inverse of its own (Newton steps on
+ *     erfc); no entry is nearer than 2.8e-5 to a rounding tie, so any sound fp64 inverse gives the same table.  The largest
+ *     entry is 3756: the noise is cut off at 3.67 sigma.  The noise belongs to the source pixel, not to the canvas pixel: the
+ *     taps of neighbouring canvas pixels that share a source pixel share its noise.
+ *   GEOMETRY   canvas pixel (X, Y) inside the placed rectangle x0 <= X < x0 + rw, y0 <= Y < y0 + rh;  x = X - x0, y = Y - y0.
+ *     sx = (x * ax + bx) >> 16,  sy = (y * ay + by) >> 16  (int64): the source position in 1/32 pixel, integer coordinates are
+ *     pixel centres.  OUT if sx <= -32 or sx >= 32 * w or sy <= -32 or sy >= 32 * h: the pixel is fill[c].  Otherwise sx is
+ *     clamped to [0, 32 * (w - 1)] and sy to [0, 32 * (h - 1)] (edge replication, as cv2.resize does) and the remap rule of
+ *     "lens undistortion" is applied to the four values a: ix = sx >> 5, fx = sx & 31, iy = sy >> 5, fy = sy & 31,
+ *     out = ((32-fx)*(32-fy)*a(ix,iy) + fx*(32-fy)*a(ix+1,iy) + (32-fx)*fy*a(ix,iy+1) + fx*fy*a(ix+1,iy+1) + 512) >> 10.
+ *     A tap of weight 0 is not read (after the clamp those are the only taps that can lie outside the frame).
+ *   BORDER   per channel the rw * rh bytes written into the rectangle are summed as integers (the order does not matter);
+ *     the pad colour is sum / (rw * rh) truncated, as rtm3d_preprocess defines it; canvas pixels outside the rectangle take it.
+ *   NORMALISE   out_mode 0 and 1 put every canvas byte through the fp32 / fp16 table of rtm3d_normalize_luts.
+ * out_mode 0: d_out = fp32 NCHW (B, 3, H, W).  out_mode 1: d_out = the plan's fp16 NHWC4 input tensor
+ *   [B][H + 2 * out_border][W + 2 * out_border][4], 4th channel 0, the border itself not written - the contract of
+ *   rtm3d_preprocess_batch out_mode 1 (rtm3d_input_tensor, rtm3d_forward with d_in == NULL).  out_mode 2: d_out = packed uint8
+ *   (B, H, W, 3) canvases at any byte address, exactly B * H * W * 3 bytes written (for inspection, drawing, JPEG encoding).
+ *
+ * rtm3d_augment_geometry (HOST, no device access): fills h, w, the rectangle and ax, bx, ay, by of *out from a frame's
+ * rtm3d_frame_geom - x0 = pad_w, y0 = pad_h, the rectangle = the frame after Resize, centred - and the draw of the affine and the
+ * mirror; every other field of *out is left as it is.  The composed map of a rectangle column x to a source column:
+ *   no mirror xm = x, mirror xm = rw - 1 - x;   xr = (xm - off_x) / scale  (the affine is dst = scale * src + offset, in the
+ *   pixels of the resized frame);   xs = (xr + 0.5) * w / rw - 0.5  (the Resize, pixel centres);   rows alike, never mirrored.
+ * It is evaluated in fp64 in this order, every line left to right as written, compiled without contraction:
+ *   r = (double)w / (double)rw;   g = r / scale;   m0 = mirror ? (double)(rw - 1) : 0.0;
+ *   c = ((m0 - off_x) / scale + 0.5) * r - 0.5;   a = mirror ? -g : g;
+ *   ax = (int64)floor(a * 2097152.0 + 0.5);   bx = (int64)floor(c * 2097152.0 + 0.5) + 32768
+ * (2097152 = 32 * 65536; the + 32768 is the round-to-nearest of the >> 16, folded into bx); ay, by from h, rh, off_y with mirror
+ * = 0.  With scale 1, offsets 0, no mirror and rw == w this is ax = 2097152, bx = 32768: sx = 32 * x, the identity.  Refused: a
+ * NULL pointer, a side < 1, a scale that is not finite and > 0, an offset that is not finite, a coefficient beyond int64's 2^62.
+ *
+ * rtm3d_frames_augment_plan (HOST): the schedule rtm3d_frames_augment gives a batch - the launcher calls the same code;
+ * out[(B + 31) / 32] receives one entry per chunk.  A canvas row is cut into runs of px_per_thread consecutive pixels that
+ * begin at X = 4 * k - shift, shift = out_border & 3 in out_mode 1 (so that a run is 32 aligned bytes of the NHWC4 tensor) and
+ * 0 otherwise.  Interior launch: grid (grid_x, count) x threads; thread t = block * threads + lane of grid row i takes run
+ * t % runs_per_row of rectangle row t / runs_per_row of frame first + i, where runs_per_row is the number of runs that meet
+ * the columns of the rectangle, and idles when t >= rh * runs_per_row; runs is the largest such product of the chunk.  Border
+ * launch: grid (border_grid_x, count) x threads, grid-striding over the H * border_runs_per_row runs of the whole canvas and
+ * writing their pixels outside the rectangle; border_grid_x = 0 and no launch when every rectangle of the chunk is its canvas.
+ * rtm3d_frames_augment_check (HOST): every refusal of rtm3d_frames_augment, without a launch.  REFUSED, for the whole batch
+ * before the first memset or launch, the message naming the frame: a NULL pointer (source, destination, noise table, channel
+ * sums, the normalisation table of the mode); a side of a frame or of the canvas < 1 or > 16384; a rectangle with a side < 1 or
+ * one that leaves the canvas; sigma_q < 0 or > 65535; |alpha_q| > 2^24; |beta_q| > 2^31 - 2^24; |ax| or |ay| >= 2^40, |bx| or
+ * |by| >= 2^56; reserved != 0; out_border < 0 in out_mode 1; an out_mode 2 destination that overlaps a source; an unknown mode.
+ *
+ * Kernel shape: a thread makes the (up to) 4 pixels of its run and stores them as 2 x 16 B (mode 1), 16 B per plane (mode 0,
+ * where the addresses allow it) or through the shared run store of packed RGB (mode 2, csrc/rgb_runs.h); channel sums are
+ * reduced within the wave, then the workgroup issues one 64-bit integer atomic per channel.  No float atomics: two calls on the
+ * same inputs give the same bytes, and a frame's bytes do not depend on its place in the batch.
+ *
+ * OUT OF SCOPE: the mosaic path (IS_MOSAIC, RandomAffine2D with rotation and shear, HSV jitter) and PhotometricDistort; parity
+ * of pixels with OpenCV or albumentations - both are absent here, the rule above is a restatement that differs by design (one
+ * interpolation, 5-bit weights, integer noise cut off at 3.67 sigma); an optimiser and a training loop; a C engine entry point;
+ * drawing the parameters on the device.                                                                                  */
+typedef struct rtm3d_augment_frame {
+    int h, w;                              /* the source frame */
+    int x0, y0, rw, rh;                    /* the placed rectangle on the canvas */
+    int32_t alpha_q, beta_q;               /* brightness / contrast; identity 65536, 0 */
+    int32_t sigma_q;                       /* noise, round(sigma * 64); 0 = none */
+    uint32_t seed_lo, seed_hi;             /* the Philox key */
+    uint8_t fill[3];                       /* the colour of an OUT pixel */
+    uint8_t reserved;                      /* 0 */
+    int64_t ax, bx, ay, by;                /* rectangle pixel -> source position, 1/32 pixel << 16 */
+} rtm3d_augment_frame;
+typedef struct rtm3d_augment_plan {
+    int first, count;                      /* frames first .. first + count - 1 */
+    int px_per_thread;                     /* 4 consecutive canvas pixels of one row */
+    int threads;                           /* per workgroup */
+    int shift;                             /* a run begins at X = 4 * k - shift */
+    int runs;                              /* interior thread runs of the chunk's largest rectangle */
+    int grid_x, grid_y;                    /* interior launch */
+    int border_runs_per_row;               /* runs that meet the W columns of a canvas row */
+    int border_grid_x;                     /* border launch: grid (border_grid_x, count); 0 = no launch */
+} rtm3d_augment_plan;
+int rtm3d_augment_noise_table(int16_t out[4096]);
+int rtm3d_augment_geometry(const rtm3d_frame_geom* geom, double scale, double off_x, double off_y, int flip, rtm3d_augment_frame* out);
+int rtm3d_frames_augment_plan(int B, const rtm3d_augment_frame* h_frames, int out_mode, int H, int W, int out_border,
+                              rtm3d_augment_plan* out);
+int rtm3d_frames_augment_check(int B, const uint8_t* const* h_src, const rtm3d_augment_frame* h_frames, const void* d_out,
+                               int out_mode, int H, int W, int out_border, const int16_t* d_noise_table, const float* d_lut,
+                               const void* d_lut16, const unsigned long long* d_sums);
+/* h_src[B]: HOST array of DEVICE pointers to packed uint8 (h, w, 3) frames at any byte address; h_frames[B]: HOST descriptors;
+ * d_noise_table: T on the device; d_lut / d_lut16: the tables of rtm3d_normalize_luts on the device (d_lut for out_mode 0,
+ * d_lut16 for out_mode 1, neither for out_mode 2); d_sums: B * 3 uint64 of device scratch (cleared here, on the stream).  */
+int rtm3d_frames_augment(void* stream, int B, const uint8_t* const* h_src, const rtm3d_augment_frame* h_frames, void* d_out,
+                         int out_mode, int H, int W, int out_border, const int16_t* d_noise_table, const float* d_lut,
+                         const void* d_lut16, unsigned long long* d_sums);
+
 #ifdef __cplusplus
 }
 #endif

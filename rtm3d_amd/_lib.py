@@ -190,6 +190,20 @@ class RemapPlan(ctypes.Structure):
                 ('grid_y', c_int)]
 
 
+class AugmentFrameC(ctypes.Structure):
+    """Mirror of struct rtm3d_augment_frame (rtm3d_amd/augment.py)."""
+    _fields_ = [('h', c_int), ('w', c_int), ('x0', c_int), ('y0', c_int), ('rw', c_int), ('rh', c_int),
+                ('alpha_q', ctypes.c_int32), ('beta_q', ctypes.c_int32), ('sigma_q', ctypes.c_int32),
+                ('seed_lo', ctypes.c_uint32), ('seed_hi', ctypes.c_uint32), ('fill', ctypes.c_uint8 * 3), ('reserved', ctypes.c_uint8),
+                ('ax', ctypes.c_int64), ('bx', ctypes.c_int64), ('ay', ctypes.c_int64), ('by', ctypes.c_int64)]
+
+
+class AugmentPlan(ctypes.Structure):
+    """Mirror of struct rtm3d_augment_plan (one per chunk of 32 frames)."""
+    _fields_ = [('first', c_int), ('count', c_int), ('px_per_thread', c_int), ('threads', c_int), ('shift', c_int), ('runs', c_int),
+                ('grid_x', c_int), ('grid_y', c_int), ('border_runs_per_row', c_int), ('border_grid_x', c_int)]
+
+
 # name -> (restype, argtypes); also the list of symbols include/rtm3d_hip.h declares
 SIGNATURES = {
     'rtm3d_last_error': (ctypes.c_char_p, []),
@@ -363,6 +377,14 @@ SIGNATURES = {
                                 ctypes.POINTER(LossParamsC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rtm3d_loss_accum_reset': (c_int, [c_void_p, c_void_p]),
     'rtm3d_loss_accum_read': (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_double)]),
+    # training augmentation: frames -> network canvas, labels in step on the host (rtm3d_amd/augment.py)
+    'rtm3d_augment_noise_table': (c_int, [c_void_p]),
+    'rtm3d_augment_geometry': (c_int, [ctypes.POINTER(FrameGeom), c_double, c_double, c_double, c_int, ctypes.POINTER(AugmentFrameC)]),
+    'rtm3d_frames_augment_plan': (c_int, [c_int, ctypes.POINTER(AugmentFrameC), c_int, c_int, c_int, c_int, ctypes.POINTER(AugmentPlan)]),
+    'rtm3d_frames_augment_check': (c_int, [c_int, c_void_p, ctypes.POINTER(AugmentFrameC), c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+    'rtm3d_frames_augment': (c_int, [c_void_p, c_int, c_void_p, ctypes.POINTER(AugmentFrameC), c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
-// The store of a run of packed RGB pixels, shared by the two kernels that write tightly packed uint8 (h, w, 3) frames
-// (frames_convert.hip: frames_convert_kernel, runs of 8 pixels; lens.hip: frames_remap_kernel, runs of 4).  Integer code only:
+// The store of a run of packed RGB pixels, shared by the kernels that write tightly packed uint8 (h, w, 3) frames
+// (frames_convert.hip: frames_convert_kernel, runs of 8 pixels; lens.hip: frames_remap_kernel, runs of 4; augment.hip: out_mode 2,
+// runs of 4).  Integer code only:
 // it compiles the same with and without -ffp-contract=off.
 //
 // Any byte address is legal.  The 3 * PX output bytes of a full run leave as aligned dwords - 8 bytes at a time where the run
