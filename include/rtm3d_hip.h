@@ -1977,6 +1977,93 @@ int rtm3d_frames_augment(void* stream, int B, const uint8_t* const* h_src, const
                          int out_mode, int H, int W, int out_border, const int16_t* d_noise_table, const float* d_lut,
                          const void* d_lut16, unsigned long long* d_sums);
 
+/* ---- optimiser step (rtm3d_amd/optim.py): Adamax, an optional weight EMA and a non-finite-loss guard in one launch ------------
+ * The line after loss.backward() of a training loop: the reference's solver.step (torch.optim.Adamax, one parameter group per
+ * parameter) as one streaming pass over every parameter of the model.  "Solver" elsewhere in this header is the L-BFGS-B 3D fit.
+ *
+ * THE RULE, per fp32 element with gradient g, parameter p, first moment m and infinity norm u.  Every operation is its own
+ * correctly rounded fp32 operation (no FMA contraction: the translation unit is built with -ffp-contract=off; the quotient is the
+ * IEEE quotient), denormals are kept, and numpy restates it operation by operation (tests/optim_ref.py):
+ *     g1 = g + wd * p                        only when the element's class has wd != 0; otherwise g1 = g
+ *     m1 = m + w * (g1 - m)                  when w < 0.5;  otherwise  m1 = g1 - (g1 - m) * (1.0f - w)     [torch's two lerp branches]
+ *     a  = u * beta2,  b = |g1| + eps
+ *     u1 = a if (a > b or a is NaN) else b   [torch.maximum: a NaN operand gives NaN; fmaxf would return the other operand]
+ *     p1 = p + nclr * (m1 / u1)
+ *     e1 = e * d + omd * p1                  only where an EMA is kept
+ * Which NaN a NaN result is (sign, payload) is not part of the rule.  An element whose gradient is NaN or +-Inf becomes non-finite
+ * (Inf: m1 = u1 = Inf, the quotient NaN); its neighbours are untouched.  The scalars are formed ON THE HOST and passed by value:
+ *     w = (float)(1 - beta1), beta2 = (float)beta2, eps = (float)eps, wd = (float)weight_decay      [fp64 first, rounded once]
+ *     nclr = (float)(-(lr / (1 - beta1 ** t)))      t = the number of this step, 1, 2, ...; fp64 as torch forms clr
+ *     d = (float)(decay * (1 - exp(-n / 2000))),  omd = (float)(1.0 - that fp64 value)           n = the EMA's update count
+ * Elements with the same (lr, weight_decay) form a HYPER CLASS {nclr, wd}; a launch takes RTM3D_OPTIM_MAX_CLASSES.
+ * torch's CPU kernels contract some of these pairs to FMA, so the rule is torch's within rounding, not to the last bit
+ * (tests/test_optim_cpu.py holds it within max(4 x torch's own fp32-vs-fp64 distance, 4 ulp) of torch's fp64 trajectory).
+ *
+ * SEGMENTS.  The host describes N segments (rtm3d_optim_segment): n fp32 elements at DEVICE addresses that are multiples of 4,
+ * a class and a kind -
+ *     RTM3D_OPTIM_UPDATE_EMA (0)  p, g, m, u, e: the update, then the EMA line on p1
+ *     RTM3D_OPTIM_UPDATE     (1)  p, g, m, u:    the update alone
+ *     RTM3D_OPTIM_EMA        (2)  p, e:          the EMA line alone on p as it is, p is only read (a floating-point buffer of the
+ *                                                model, e.g. BatchNorm's running statistics)
+ * Pointers a kind does not use are ignored.  rtm3d_optim_plan (HOST) checks the segments and writes the two tables the kernel
+ * walks: the segment table (the N descriptors as given) and the chunk table, one rtm3d_optim_chunk {segment, index} per run of
+ * RTM3D_OPTIM_CHUNK elements index * CHUNK .. of a segment, segments in order, a segment's chunks in rising index; the last chunk
+ * of a segment is short, a chunk never crosses a segment, a segment of 0 elements has no chunk, and every element of every
+ * segment lies in exactly one chunk.  The caller copies both tables to the device (8-byte aligned).  REFUSED, by code
+ * (RTM3D_OPTIM_E_*, the message in rtm3d_last_error): a NULL argument or a NULL pointer a kind uses (E_NULL); N < 1 (E_COUNT);
+ * n < 0 or n > 2^40 (E_SIZE); a class outside 0 .. 15 (E_CLASS); an unknown kind (E_KIND); an address that is no multiple of 4 (E_ALIGN);
+ * any two used ranges of any segments that overlap (E_OVERLAP); more than 2^31 - 1 chunks (E_TOO_MANY).
+ * rtm3d_optim_table_bytes (HOST): the bytes of the two tables and the chunk count for N segment sizes.
+ *
+ * rtm3d_optim_step: ONE launch, no synchronisation, no atomics, no workspace.  min(chunks, compute units) workgroups of 1024
+ * threads (16 waves per compute unit) stride over the chunk table; a chunk whose pointers are all multiples of 16 moves 16 B per lane and access (its last
+ * n & 3 elements singly), any other chunk one element per lane and access - parameters are the caller's storage and may sit
+ * at any multiple of 4.  Gradients are read with non-temporal loads.  Each element has one writer: two runs on equal inputs
+ * leave equal bytes.
+ * GUARD: with d_loss != NULL the launch reads that fp32 value first; if it is NaN or +-Inf NO byte of p, m, u, e is written and
+ * one lane adds 1 to *d_skipped (an ordinary load and store: the counter belongs to one stream).  The host's counts t and n
+ * advance all the same - that is what lets it form the scalars without reading anything back.  With d_loss == NULL the update
+ * always applies.  DEVIATION from the reference, which tests torch.isfinite(loss) on the host (one synchronisation per step) and
+ * ends training: here the step is skipped and counted, and the caller reads the counter when it wants to.
+ *
+ * OUT OF SCOPE: the network's backward pass, a training loop, gradient clipping, loss scaling, SGD / Adam, an all-reduce (the
+ * gradient arena of rtm3d_amd/optim.py is one flat tensor so that one collective can reduce it), graph capture of the step, a C
+ * engine entry point.                                                                                                        */
+#define RTM3D_OPTIM_CHUNK 4096
+#define RTM3D_OPTIM_MAX_CLASSES 16
+enum { RTM3D_OPTIM_UPDATE_EMA = 0, RTM3D_OPTIM_UPDATE = 1, RTM3D_OPTIM_EMA = 2 };
+enum { RTM3D_OPTIM_E_NULL = 1, RTM3D_OPTIM_E_COUNT = 2, RTM3D_OPTIM_E_SIZE = 3, RTM3D_OPTIM_E_CLASS = 4, RTM3D_OPTIM_E_KIND = 5,
+       RTM3D_OPTIM_E_ALIGN = 6, RTM3D_OPTIM_E_OVERLAP = 7, RTM3D_OPTIM_E_TOO_MANY = 8, RTM3D_OPTIM_E_LAUNCH = 9 };
+typedef struct rtm3d_optim_segment {
+    void* p;                               /* parameter (kinds 0, 1: read and written) or buffer (kind 2: read) */
+    const void* g;                         /* gradient; kinds 0, 1 */
+    void* m;                               /* first moment (exp_avg); kinds 0, 1 */
+    void* u;                               /* infinity norm (exp_inf); kinds 0, 1 */
+    void* e;                               /* EMA; kinds 0, 2 */
+    long long n;                           /* fp32 elements */
+    int kind;                              /* RTM3D_OPTIM_UPDATE_EMA / _UPDATE / _EMA */
+    int cls;                               /* hyper class, 0 .. 15 (ignored by kind 2) */
+} rtm3d_optim_segment;
+typedef struct rtm3d_optim_chunk {
+    int segment;                           /* row of the segment table */
+    int index;                             /* elements index * RTM3D_OPTIM_CHUNK .. of that segment */
+} rtm3d_optim_chunk;
+typedef struct rtm3d_optim_hyper {         /* the scalars of one step, passed to the launch by value */
+    float nclr[RTM3D_OPTIM_MAX_CLASSES];
+    float wd[RTM3D_OPTIM_MAX_CLASSES];
+    float w, beta2, eps;
+    float ema_d, ema_omd;
+    int reserved;                          /* 0 */
+} rtm3d_optim_hyper;
+int rtm3d_optim_table_bytes(int n_segments, const long long* sizes, size_t* segment_bytes, size_t* chunk_bytes, int* n_chunks);
+int rtm3d_optim_plan(int n_segments, const rtm3d_optim_segment* segments, rtm3d_optim_segment* segment_table,
+                     rtm3d_optim_chunk* chunk_table, int* n_chunks);
+/* segments[N]: HOST descriptors holding DEVICE addresses; segment_table[N] and chunk_table[*n_chunks]: HOST memory of the sizes
+ * rtm3d_optim_table_bytes names.  Nothing is written when the call refuses. */
+int rtm3d_optim_step(void* stream, const rtm3d_optim_segment* d_segment_table, const rtm3d_optim_chunk* d_chunk_table, int n_chunks,
+                     const rtm3d_optim_hyper* hyper, const float* d_loss, unsigned* d_skipped);
+/* d_segment_table, d_chunk_table: the two tables on the DEVICE; hyper: HOST; d_loss: DEVICE fp32 or NULL; d_skipped: DEVICE uint32. */
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,23 @@ class AugmentPlan(ctypes.Structure):
                 ('grid_x', c_int), ('grid_y', c_int), ('border_runs_per_row', c_int), ('border_grid_x', c_int)]
 
 
+class OptimSegmentC(ctypes.Structure):
+    """Mirror of struct rtm3d_optim_segment (rtm3d_amd/optim.py)."""
+    _fields_ = [('p', c_void_p), ('g', c_void_p), ('m', c_void_p), ('u', c_void_p), ('e', c_void_p), ('n', ctypes.c_longlong),
+                ('kind', c_int), ('cls', c_int)]
+
+
+class OptimChunkC(ctypes.Structure):
+    """Mirror of struct rtm3d_optim_chunk."""
+    _fields_ = [('segment', c_int), ('index', c_int)]
+
+
+class OptimHyperC(ctypes.Structure):
+    """Mirror of struct rtm3d_optim_hyper (the scalars of one step)."""
+    _fields_ = [('nclr', c_float * 16), ('wd', c_float * 16), ('w', c_float), ('beta2', c_float), ('eps', c_float),
+                ('ema_d', c_float), ('ema_omd', c_float), ('reserved', c_int)]
+
+
 # name -> (restype, argtypes); also the list of symbols include/rtm3d_hip.h declares
 SIGNATURES = {
     'rtm3d_last_error': (ctypes.c_char_p, []),
@@ -385,6 +402,12 @@ SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p]),
     'rtm3d_frames_augment': (c_int, [c_void_p, c_int, c_void_p, ctypes.POINTER(AugmentFrameC), c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
+    # optimiser step: Adamax, weight EMA and the non-finite guard in one launch (rtm3d_amd/optim.py)
+    'rtm3d_optim_table_bytes': (c_int, [c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
+                                        ctypes.POINTER(c_int)]),
+    'rtm3d_optim_plan': (c_int, [c_int, ctypes.POINTER(OptimSegmentC), ctypes.POINTER(OptimSegmentC), ctypes.POINTER(OptimChunkC),
+                                 ctypes.POINTER(c_int)]),
+    'rtm3d_optim_step': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(OptimHyperC), c_void_p, c_void_p]),
 }
 
 _lib = None
