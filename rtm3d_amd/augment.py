@@ -17,11 +17,11 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _frames, _lib
+from ._frames import CHUNK  # noqa: F401  (a name the tests use)
 from .loss import LabelBatch, cfg_get, transform_obj_label, _check_gaussian_type
 from .preprocess import device_luts, frame_geometry, resized_size
 
-CHUNK = 32                              # frames per launch (AUG_MAX_BATCH)
 MODES = {'fp32': 0, 'nhwc4': 1, 'uint8': 2}
 
 
@@ -131,9 +131,7 @@ def descriptors(hw, params, size, resize_to=None):
 
 def plan(desc, size, mode=0, border=0):
     """rtm3d_frames_augment_plan: the launch schedule, one AugmentPlan per chunk of 32 frames (host only)."""
-    out = (_lib.AugmentPlan * ((len(desc) + CHUNK - 1) // CHUNK))()
-    _lib.check(_lib.load().rtm3d_frames_augment_plan(len(desc), desc, int(mode), int(size[0]), int(size[1]), int(border), out), 'frames_augment_plan')
-    return list(out)
+    return _frames.chunk_plans('frames_augment_plan', _lib.AugmentPlan, desc, int(mode), int(size[0]), int(size[1]), int(border))
 
 
 def noise_table():
@@ -171,11 +169,7 @@ def frames(images, params, size, mean, std, resize_to=None, out=None, model=None
     dev = images[0].device
     if dev.type != 'cuda':
         raise RuntimeError('rtm3d_amd.augment needs CUDA (ROCm) tensors; there is no CPU path')
-    imgs = []
-    for img in images:
-        if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or img.device != dev:
-            raise ValueError('expected uint8 (h, w, 3) images on one device')
-        imgs.append(img.contiguous())
+    imgs = _frames.packed_frames(images, 'expected uint8 (h, w, 3) images on one device', dev)
     B = len(imgs)
     if mode is None:
         mode = 'nhwc4' if model is not None else 'fp32'

@@ -1,6 +1,6 @@
 // Training augmentation (include/rtm3d_hip.h, "training augmentation"): B packed uint8 (h, w, 3) frames -> the network canvas in
 // one pass - brightness / contrast and Philox noise on the source bytes, one bilinear resample through the composed Resize,
-// RandomAffine and RandomMirror map, mean-colour letterbox, normalisation tables.  Per chunk of AUG_MAX_BATCH frames one interior
+// RandomAffine and RandomMirror map, mean-colour letterbox, normalisation tables.  Per chunk of FRAME_CHUNK frames (frame_chunks.h) one interior
 // launch (the placed rectangles and their channel sums) and one border launch (the pad colour); the descriptors travel by value
 // (2.8 KB of kernel arguments), no copy, no synchronisation.  Integer code on the device: no float arithmetic, no float atomics.
 //
@@ -22,12 +22,12 @@
 #include <string.h>
 
 #include "../../include/rtm3d_hip.h"
+#include "frame_chunks.h"
 #include "philox.h"
 #include "rgb_runs.h"
 
 #define AUG_PX 4
 #define AUG_THREADS 256
-#define AUG_MAX_BATCH 32
 #define AUG_MAX_SIDE 16384
 #define AUG_BORDER_GRID 512
 
@@ -35,7 +35,7 @@ struct AugFrame {                        // 88 B
     const uint8_t* src;
     rtm3d_augment_frame f;
 };
-struct AugBatch { AugFrame f[AUG_MAX_BATCH]; };                           // 2.8 KB of kernel arguments
+struct AugBatch { AugFrame f[FRAME_CHUNK]; };                             // 2.8 KB of kernel arguments
 
 // the 4 / 2 bytes at any address, low byte first
 __device__ __forceinline__ uint32_t aug_load4(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
@@ -249,8 +249,6 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_border_kernel(const AugBa
 }
 
 // ---------------------------------------------------------------------------------------------------- host
-extern void rt_set_error(const char* fmt, ...);
-
 // Phi^-1(p), 0 < p < 1: Newton steps on Phi(x) - p from the inflection point, on the side where Phi is convex (p < 1/2: the
 // iterates fall monotonically onto the root), the other half by symmetry.  Phi through erfc, which keeps its relative accuracy
 // in the tail.
@@ -317,16 +315,13 @@ static bool below(int64_t v, int bits) { return v > -((int64_t)1 << bits) && v <
 
 // what concerns the descriptors and the canvas alone (the plan has nothing else)
 static int check_frames(const char* who, int B, const rtm3d_augment_frame* h_frames, int out_mode, int H, int W, int out_border) {
-    if (B < 1) { rt_set_error("%s: B = %d", who, B); return 1; }
-    if (!h_frames) { rt_set_error("%s: null pointer", who); return 1; }
+    if (refuse_count(who, B) || refuse_null(who, h_frames)) return 1;
     if (out_mode < 0 || out_mode > 2) { rt_set_error("%s: out_mode %d is none of 0 (fp32 NCHW), 1 (fp16 NHWC4), 2 (packed uint8)", who, out_mode); return 1; }
     if (!side_ok(H) || !side_ok(W)) { rt_set_error("%s: a canvas of %d x %d; a side must lie in 1..%d", who, H, W, AUG_MAX_SIDE); return 1; }
     if (out_mode == 1 && (out_border < 0 || out_border > AUG_MAX_SIDE)) { rt_set_error("%s: out_border %d", who, out_border); return 1; }
     for (int b = 0; b < B; ++b) {
         const rtm3d_augment_frame& f = h_frames[b];
-        if (!side_ok(f.h) || !side_ok(f.w)) {
-            rt_set_error("%s: frame %d is %d x %d; a side must lie in 1..%d", who, b, f.h, f.w, AUG_MAX_SIDE); return 1;
-        }
+        if (refuse_side(who, b, f.h, f.w, 1, AUG_MAX_SIDE)) return 1;
         if (f.rw < 1 || f.rh < 1 || f.x0 < 0 || f.y0 < 0 || f.rw > W || f.rh > H || f.x0 > W - f.rw || f.y0 > H - f.rh) {
             rt_set_error("%s: frame %d: the rectangle %d x %d at (%d, %d) leaves the %d x %d canvas", who, b, f.rh, f.rw, f.y0, f.x0, H, W);
             return 1;
@@ -342,38 +337,38 @@ static int check_frames(const char* who, int B, const rtm3d_augment_frame* h_fra
         if (!below(f.bx, 56) || !below(f.by, 56)) {
             rt_set_error("%s: frame %d: |bx| or |by| (%lld, %lld) at or above 2^56", who, b, (long long)f.bx, (long long)f.by); return 1;
         }
-        if (f.reserved != 0) { rt_set_error("%s: frame %d: reserved = %d, not 0", who, b, (int)f.reserved); return 1; }
+        if (refuse_reserved(who, b, f.reserved)) return 1;
     }
     return 0;
 }
 
 static int runs_between(int lo, int hi, int shift) { return ((hi - 1 + shift) >> 2) - ((lo + shift) >> 2) + 1; }   // runs that meet lo .. hi - 1
 
-static void plan_chunk(int b0, int nb, const rtm3d_augment_frame* h_frames, int out_mode, int H, int W, int out_border, rtm3d_augment_plan* P) {
-    P->first = b0; P->count = nb;
-    P->px_per_thread = AUG_PX; P->threads = AUG_THREADS;
-    P->shift = out_mode == 1 ? (out_border & 3) : 0;
-    P->runs = 0;
+static rtm3d_augment_plan plan_chunk(const FrameChunk c, const rtm3d_augment_frame* h_frames, int out_mode, int H, int W, int out_border) {
+    rtm3d_augment_plan P;
+    P.first = c.b0; P.count = c.nb;
+    P.px_per_thread = AUG_PX; P.threads = AUG_THREADS;
+    P.shift = out_mode == 1 ? (out_border & 3) : 0;
+    P.runs = 0;
     bool border = false;
-    for (int i = 0; i < nb; ++i) {
-        const rtm3d_augment_frame& f = h_frames[b0 + i];
-        const int runs = runs_between(f.x0, f.x0 + f.rw, P->shift) * f.rh;        // <= 4097 * 16384
-        if (runs > P->runs) P->runs = runs;
+    for (int i = 0; i < c.nb; ++i) {
+        const rtm3d_augment_frame& f = h_frames[c.b0 + i];
+        const int runs = runs_between(f.x0, f.x0 + f.rw, P.shift) * f.rh;         // <= 4097 * 16384
+        if (runs > P.runs) P.runs = runs;
         if (f.rw != W || f.rh != H) border = true;
     }
-    P->grid_x = (P->runs + AUG_THREADS - 1) / AUG_THREADS;
-    P->grid_y = nb;
-    P->border_runs_per_row = runs_between(0, W, P->shift);
-    const int all = (P->border_runs_per_row * H + AUG_THREADS - 1) / AUG_THREADS;
-    P->border_grid_x = !border ? 0 : (all > AUG_BORDER_GRID ? AUG_BORDER_GRID : all);
+    P.grid_x = (P.runs + AUG_THREADS - 1) / AUG_THREADS;
+    P.grid_y = c.nb;
+    P.border_runs_per_row = runs_between(0, W, P.shift);
+    const int all = (P.border_runs_per_row * H + AUG_THREADS - 1) / AUG_THREADS;
+    P.border_grid_x = !border ? 0 : (all > AUG_BORDER_GRID ? AUG_BORDER_GRID : all);
+    return P;
 }
 
 extern "C" int rtm3d_frames_augment_plan(int B, const rtm3d_augment_frame* h_frames, int out_mode, int H, int W, int out_border,
                                          rtm3d_augment_plan* out) {
-    if (!out) { rt_set_error("frames_augment_plan: null pointer"); return 1; }
-    if (check_frames("frames_augment_plan", B, h_frames, out_mode, H, W, out_border)) return 1;
-    for (int b0 = 0, k = 0; b0 < B; b0 += AUG_MAX_BATCH, ++k)
-        plan_chunk(b0, B - b0 < AUG_MAX_BATCH ? B - b0 : AUG_MAX_BATCH, h_frames, out_mode, H, W, out_border, &out[k]);
+    if (refuse_null("frames_augment_plan", out) || check_frames("frames_augment_plan", B, h_frames, out_mode, H, W, out_border)) return 1;
+    for (const FrameChunk c : frame_chunks(B)) out[c.k] = plan_chunk(c, h_frames, out_mode, H, W, out_border);
     return 0;
 }
 
@@ -381,8 +376,7 @@ extern "C" int rtm3d_frames_augment_check(int B, const uint8_t* const* h_src, co
                                           int out_mode, int H, int W, int out_border, const int16_t* d_noise_table, const float* d_lut,
                                           const void* d_lut16, const unsigned long long* d_sums) {
     const char* who = "frames_augment";
-    if (!h_src) { rt_set_error("%s: null pointer", who); return 1; }
-    if (check_frames(who, B, h_frames, out_mode, H, W, out_border)) return 1;
+    if (refuse_null(who, h_src) || check_frames(who, B, h_frames, out_mode, H, W, out_border)) return 1;
     if (!d_out) { rt_set_error("%s: the destination is a NULL pointer", who); return 1; }
     if (!d_noise_table) { rt_set_error("%s: the noise table is a NULL pointer", who); return 1; }
     if ((uintptr_t)d_noise_table & 1) { rt_set_error("%s: the noise table's address is odd", who); return 1; }
@@ -418,18 +412,14 @@ extern "C" int rtm3d_frames_augment(void* stream, int B, const uint8_t* const* h
     if (rtm3d_frames_augment_check(B, h_src, h_frames, d_out, out_mode, H, W, out_border, d_noise_table, d_lut, d_lut16, d_sums)) return 1;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(d_sums, 0, (size_t)B * 3 * sizeof(unsigned long long), s) != hipSuccess) { rt_set_error("frames_augment: memset failed"); return 1; }
-    rtm3d_augment_plan plan;
-    for (int b0 = 0; b0 < B; b0 += AUG_MAX_BATCH) {
-        const int nb = B - b0 < AUG_MAX_BATCH ? B - b0 : AUG_MAX_BATCH;
-        plan_chunk(b0, nb, h_frames, out_mode, H, W, out_border, &plan);              // the numbers of rtm3d_frames_augment_plan
+    for (const FrameChunk c : frame_chunks(B)) {
+        const rtm3d_augment_plan plan = plan_chunk(c, h_frames, out_mode, H, W, out_border);       // the numbers of rtm3d_frames_augment_plan
         AugBatch ab;
         memset(&ab, 0, sizeof ab);                                                     // (an unused entry is never indexed: grid_y = nb)
-        for (int i = 0; i < nb; ++i) { ab.f[i].src = h_src[b0 + i]; ab.f[i].f = h_frames[b0 + i]; }
+        for (int i = 0; i < c.nb; ++i) { ab.f[i].src = h_src[c.b0 + i]; ab.f[i].f = h_frames[c.b0 + i]; }
         if (out_mode == 0) launch_chunk<0>(s, plan, ab, d_out, H, W, out_border, d_noise_table, d_lut, d_lut16, d_sums);
         else if (out_mode == 1) launch_chunk<1>(s, plan, ab, d_out, H, W, out_border, d_noise_table, d_lut, d_lut16, d_sums);
         else launch_chunk<2>(s, plan, ab, d_out, H, W, out_border, d_noise_table, d_lut, d_lut16, d_sums);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("frames_augment launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return launch_ok("frames_augment");
 }

@@ -1,7 +1,7 @@
 // Raw sensor frames (include/rtm3d_hip.h, "raw sensor frames"): Bayer mosaics of 8 / 10 / 12 / 14 / 16-bit samples - bytes,
 // uint16 (LSB- or MSB-justified), MIPI RAW10 / RAW12 - to the tightly packed uint8 (h, w, 3) frames every other entry point
 // reads.  Black level, white balance, demosaic (Malvar-He-Cutler or bilinear), colour matrix and tone table in one launch per
-// chunk of DEM_MAX_BATCH frames; the per-frame descriptors travel by value (no copy, no memset, no synchronisation).
+// chunk of FRAME_CHUNK frames (frame_chunks.h); the per-frame descriptors travel by value (no copy, no memset, no synchronisation).
 //
 // Mapping (rtm3d_frames_demosaic_plan returns the same numbers): workgroup blockIdx.x of frame blockIdx.y takes the tile of
 // DEM_TW x DEM_TH pixels at (DEM_TW * (t % tiles_x), DEM_TH * (t / tiles_x)).
@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "../../include/rtm3d_hip.h"
+#include "frame_chunks.h"
 #include "rgb_runs.h"
 
 #define DEM_TW 128
@@ -32,7 +33,6 @@
 #define DEM_PX 8
 #define DEM_ROWS 2
 #define DEM_THREADS 256
-#define DEM_MAX_BATCH 32
 #define DEM_MAX_SIDE 16384
 #define DEM_TONE 4096                                   // bytes of a tone table
 #define DEM_LW (DEM_TW + 2 * DEM_HALO)                  // 132 samples of an LDS row: 264 B, a multiple of 8
@@ -53,7 +53,7 @@ struct DemFrame {                        // 104 B
     int black[4], gain[4];
     int16_t ccm[9], pad;
 };
-struct DemBatch { DemFrame f[DEM_MAX_BATCH]; };          // 3.25 KB of kernel arguments
+struct DemBatch { DemFrame f[FRAME_CHUNK]; };            // 3.25 KB of kernel arguments
 
 // fold() of the header for i in [-2, n + 1], n >= 2 (all that a halo of 2 asks for): |i| is the reflection at 0, p - i the one
 // at n - 1; the second |.| serves n = 2, where p - i can be -1
@@ -273,8 +273,6 @@ __global__ __launch_bounds__(DEM_THREADS, 5) void frames_demosaic_kernel(DemBatc
     else demosaic_run<METHOD, 0>(f, tx0 + lx0, ty0 + ly0, lx0, ly0, lds, tone, dst_order);
 }
 
-extern void rt_set_error(const char* fmt, ...);
-
 // bytes of a row; 0 for an unknown layout or bits the layout does not take
 static int raw_row_bytes(int layout, int bits, int w) {
     switch (layout) {
@@ -301,20 +299,17 @@ extern "C" int rtm3d_raw_src_layout(int layout, int bits, int h, int w, int* min
 
 // every refusal of the header, for the whole batch; h_dst may be NULL (the plan has no destinations)
 static int check_raw(const char* who, int B, const rtm3d_raw_src* h_src, uint8_t* const* h_dst, int method, int dst_order) {
-    if (B < 1) { rt_set_error("%s: B = %d", who, B); return 1; }
-    if (!h_src) { rt_set_error("%s: null pointer", who); return 1; }
+    if (refuse_count(who, B) || refuse_null(who, h_src)) return 1;
     if (method != RTM3D_DEMOSAIC_MHC && method != RTM3D_DEMOSAIC_BILINEAR) { rt_set_error("%s: method %d (0 MHC, 1 bilinear)", who, method); return 1; }
-    if (dst_order != 0 && dst_order != 1) { rt_set_error("%s: dst_order %d (0 R G B, 1 B G R)", who, dst_order); return 1; }
+    if (refuse_order(who, "dst_order", dst_order)) return 1;
     for (int b = 0; b < B; ++b) {
         const rtm3d_raw_src& s = h_src[b];
-        if (s.h < 2 || s.w < 2 || s.h > DEM_MAX_SIDE || s.w > DEM_MAX_SIDE) {
-            rt_set_error("%s: frame %d is %d x %d; a side must lie in 2..%d", who, b, s.h, s.w, DEM_MAX_SIDE); return 1;
-        }
+        if (refuse_side(who, b, s.h, s.w, 2, DEM_MAX_SIDE)) return 1;
         if (!known_layout(s.layout)) { rt_set_error("%s: frame %d has the unknown layout %d", who, b, s.layout); return 1; }
         const int rb = raw_row_bytes(s.layout, s.bits, s.w);
         if (!rb) { rt_set_error("%s: frame %d: layout %d does not take %d bits", who, b, s.layout, s.bits); return 1; }
         if (s.pattern < RTM3D_CFA_RGGB || s.pattern > RTM3D_CFA_GBRG) { rt_set_error("%s: frame %d has the unknown pattern %d", who, b, s.pattern); return 1; }
-        if (s.reserved != 0) { rt_set_error("%s: frame %d: reserved = %d, not 0", who, b, s.reserved); return 1; }
+        if (refuse_reserved(who, b, s.reserved)) return 1;
         if (s.pad != 0) { rt_set_error("%s: frame %d: pad = %d, not 0", who, b, s.pad); return 1; }
         if (!s.plane) { rt_set_error("%s: frame %d: the plane is a NULL pointer", who, b); return 1; }
         if (s.pitch < rb) { rt_set_error("%s: frame %d: pitch %d is below the row's %d bytes", who, b, s.pitch, rb); return 1; }
@@ -328,53 +323,48 @@ static int check_raw(const char* who, int B, const rtm3d_raw_src* h_src, uint8_t
         }
         for (int i = 0; i < 9; ++i)
             if (s.ccm[i] > 8192 || s.ccm[i] < -8192) { rt_set_error("%s: frame %d: ccm[%d] = %d is outside +-8192", who, b, i, s.ccm[i]); return 1; }
-        if (h_dst && !h_dst[b]) { rt_set_error("%s: frame %d: the destination is a NULL pointer", who, b); return 1; }
+        if (h_dst && refuse_null_dst(who, b, h_dst[b])) return 1;
     }
     return 0;
 }
 
-static void plan_raw_chunks(int B, const rtm3d_raw_src* h_src, rtm3d_demosaic_plan* out) {
-    for (int b0 = 0, k = 0; b0 < B; b0 += DEM_MAX_BATCH, ++k) {
-        rtm3d_demosaic_plan& P = out[k];
-        P.first = b0;
-        P.count = B - b0 < DEM_MAX_BATCH ? B - b0 : DEM_MAX_BATCH;
-        P.tile_w = DEM_TW; P.tile_h = DEM_TH; P.halo = DEM_HALO; P.threads = DEM_THREADS;
-        P.tiles = 0;
-        for (int i = 0; i < P.count; ++i) {
-            const rtm3d_raw_src& s = h_src[b0 + i];
-            const int tiles = ((s.w + DEM_TW - 1) / DEM_TW) * ((s.h + DEM_TH - 1) / DEM_TH);          // <= 128 * 512
-            if (tiles > P.tiles) P.tiles = tiles;
-        }
-        P.grid_x = P.tiles;
-        P.grid_y = P.count;
+static rtm3d_demosaic_plan plan_chunk(const FrameChunk c, const rtm3d_raw_src* h_src) {
+    rtm3d_demosaic_plan P;
+    P.first = c.b0; P.count = c.nb;
+    P.tile_w = DEM_TW; P.tile_h = DEM_TH; P.halo = DEM_HALO; P.threads = DEM_THREADS;
+    P.tiles = 0;
+    for (int i = 0; i < c.nb; ++i) {
+        const rtm3d_raw_src& s = h_src[c.b0 + i];
+        const int tiles = ((s.w + DEM_TW - 1) / DEM_TW) * ((s.h + DEM_TH - 1) / DEM_TH);              // <= 128 * 512
+        if (tiles > P.tiles) P.tiles = tiles;
     }
+    P.grid_x = P.tiles;
+    P.grid_y = c.nb;
+    return P;
 }
 
 extern "C" int rtm3d_frames_demosaic_plan(int B, const rtm3d_raw_src* h_src, int method, rtm3d_demosaic_plan* out) {
-    if (!out) { rt_set_error("frames_demosaic_plan: null pointer"); return 1; }
-    if (check_raw("frames_demosaic_plan", B, h_src, nullptr, method, 0)) return 1;
-    plan_raw_chunks(B, h_src, out);
+    if (refuse_null("frames_demosaic_plan", out) || check_raw("frames_demosaic_plan", B, h_src, nullptr, method, 0)) return 1;
+    for (const FrameChunk c : frame_chunks(B)) out[c.k] = plan_chunk(c, h_src);
     return 0;
 }
 
 extern "C" int rtm3d_frames_demosaic_check(int B, const rtm3d_raw_src* h_src, uint8_t* const* h_dst, int method, int dst_order) {
-    if (!h_dst) { rt_set_error("frames_demosaic: null pointer"); return 1; }
+    if (refuse_null("frames_demosaic", h_dst)) return 1;
     return check_raw("frames_demosaic", B, h_src, h_dst, method, dst_order);
 }
 
 extern "C" int rtm3d_frames_demosaic(void* stream, int B, const rtm3d_raw_src* h_src, uint8_t* const* h_dst, int method, int dst_order) {
     if (rtm3d_frames_demosaic_check(B, h_src, h_dst, method, dst_order)) return 1;     // the whole batch, before the first launch
-    rtm3d_demosaic_plan plan;
-    for (int b0 = 0; b0 < B; b0 += DEM_MAX_BATCH) {
-        const int nb = B - b0 < DEM_MAX_BATCH ? B - b0 : DEM_MAX_BATCH;
-        plan_raw_chunks(nb, h_src + b0, &plan);                                        // one chunk: the numbers of rtm3d_frames_demosaic_plan
+    for (const FrameChunk c : frame_chunks(B)) {
+        const rtm3d_demosaic_plan plan = plan_chunk(c, h_src);                         // the numbers of rtm3d_frames_demosaic_plan
         DemBatch fb;
-        for (int i = 0; i < DEM_MAX_BATCH; ++i) {
+        for (int i = 0; i < FRAME_CHUNK; ++i) {
             DemFrame& f = fb.f[i];
             f = DemFrame{};                                                            // (h = w = 0: no tiles)
-            if (i >= nb) continue;
-            const rtm3d_raw_src& s = h_src[b0 + i];
-            f.plane = (const uint8_t*)s.plane; f.tone = s.d_tone; f.dst = h_dst[b0 + i];
+            if (i >= c.nb) continue;
+            const rtm3d_raw_src& s = h_src[c.b0 + i];
+            f.plane = (const uint8_t*)s.plane; f.tone = s.d_tone; f.dst = h_dst[c.b0 + i];
             f.pitch = s.pitch; f.h = s.h; f.w = s.w; f.layout = s.layout; f.bits = s.bits;
             bool identity = true;
             for (int k = 0; k < 9; ++k) { f.ccm[k] = s.ccm[k]; identity = identity && s.ccm[k] == (k % 4 == 0 ? 1024 : 0); }
@@ -387,7 +377,5 @@ extern "C" int rtm3d_frames_demosaic(void* stream, int B, const rtm3d_raw_src* h
         else
             hipLaunchKernelGGL(frames_demosaic_kernel<RTM3D_DEMOSAIC_BILINEAR>, grid, block, 0, (hipStream_t)stream, fb, dst_order);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("frames_demosaic launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return launch_ok("frames_demosaic");
 }

@@ -524,12 +524,29 @@ extern "C" size_t rtm3d_engine_frames_workspace_bytes(rtm3d_ctx* ctx) {
     return st ? frames_layout(st->info).total : 0;
 }
 
+// the opening of every camera-frame entry: the engine state of the context, nullptr after one of the three refusals
+static EngineState* frames_state(rtm3d_ctx* ctx, const char* who, bool null_argument) {
+    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
+    if (!st) rt_set_error("%s: the context was not made by rtm3d_engine_load", who);
+    else if (null_argument) rt_set_error("%s: null argument", who);
+    else if (!st->frames) rt_set_error("%s: call rtm3d_engine_set_frame_params first", who);
+    else return st;
+    return nullptr;
+}
+
+// size_of(b, hw) writes (h, w) of frame b or refuses it; then the frames' place on the canvas
+template <class F> static int place_frames(EngineState* st, std::vector<int>& hw, F size_of) {
+    const rtm3d_engine_info& I = st->info;
+    hw.resize((size_t)I.B * 2);
+    for (int b = 0; b < I.B; ++b)
+        if (size_of(b, &hw[2 * b])) return 1;
+    return rtm3d_frame_geometry(I.B, hw.data(), st->resize_to, I.H, I.W, st->geom.data());
+}
+
 extern "C" int rtm3d_engine_detect_frames(rtm3d_ctx* ctx, void* stream, const uint8_t* const* h_imgs, const int* h_hw,
                                           const double* d_K_camera, float* d_rec, double* d_kitti, void* d_workspace) {
-    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
-    if (!st) EFAIL("engine_detect_frames: the context was not made by rtm3d_engine_load");
-    if (!h_imgs || !h_hw || !d_K_camera || !d_rec || !d_workspace) EFAIL("engine_detect_frames: null argument");
-    if (!st->frames) EFAIL("engine_detect_frames: call rtm3d_engine_set_frame_params first");
+    EngineState* st = frames_state(ctx, "engine_detect_frames", !h_imgs || !h_hw || !d_K_camera || !d_rec || !d_workspace);
+    if (!st) return 1;
     const rtm3d_engine_info& I = st->info;
     for (int b = 0; b < I.B; ++b)
         if (!h_imgs[b]) EFAIL("engine_detect_frames: frame %d is a null pointer", b);
@@ -554,16 +571,12 @@ extern "C" int rtm3d_engine_detect_frames(rtm3d_ctx* ctx, void* stream, const ui
 
 extern "C" int rtm3d_engine_detect_frames_src(rtm3d_ctx* ctx, void* stream, const rtm3d_frame_src* h_src, uint8_t* const* h_packed,
                                               int dst_order, const double* d_K_camera, float* d_rec, double* d_kitti, void* d_workspace) {
-    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
-    if (!st) EFAIL("engine_detect_frames_src: the context was not made by rtm3d_engine_load");
-    if (!h_src || !h_packed || !d_K_camera || !d_rec || !d_workspace) EFAIL("engine_detect_frames_src: null argument");
-    if (!st->frames) EFAIL("engine_detect_frames_src: call rtm3d_engine_set_frame_params first");
+    EngineState* st = frames_state(ctx, "engine_detect_frames_src", !h_src || !h_packed || !d_K_camera || !d_rec || !d_workspace);
+    if (!st) return 1;
     const rtm3d_engine_info& I = st->info;
     // everything either step would refuse, before the first launch: the sources, then the frames' place on the canvas
     if (rtm3d_frames_convert_check(I.B, h_src, h_packed, dst_order)) return 1;
-    st->src_hw.resize((size_t)I.B * 2);
-    for (int b = 0; b < I.B; ++b) { st->src_hw[2 * b] = h_src[b].h; st->src_hw[2 * b + 1] = h_src[b].w; }
-    if (rtm3d_frame_geometry(I.B, st->src_hw.data(), st->resize_to, I.H, I.W, st->geom.data())) return 1;
+    if (place_frames(st, st->src_hw, [&](int b, int* hw) { hw[0] = h_src[b].h; hw[1] = h_src[b].w; return 0; })) return 1;
     if (rtm3d_frames_convert(stream, I.B, h_src, h_packed, dst_order)) return 1;
     return rtm3d_engine_detect_frames(ctx, stream, h_packed, st->src_hw.data(), d_K_camera, d_rec, d_kitti, d_workspace);
 }
@@ -571,16 +584,12 @@ extern "C" int rtm3d_engine_detect_frames_src(rtm3d_ctx* ctx, void* stream, cons
 extern "C" int rtm3d_engine_detect_frames_raw(rtm3d_ctx* ctx, void* stream, const rtm3d_raw_src* h_src, uint8_t* const* h_packed,
                                               int method, int dst_order, const double* d_K_camera, float* d_rec, double* d_kitti,
                                               void* d_workspace) {
-    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
-    if (!st) EFAIL("engine_detect_frames_raw: the context was not made by rtm3d_engine_load");
-    if (!h_src || !h_packed || !d_K_camera || !d_rec || !d_workspace) EFAIL("engine_detect_frames_raw: null argument");
-    if (!st->frames) EFAIL("engine_detect_frames_raw: call rtm3d_engine_set_frame_params first");
+    EngineState* st = frames_state(ctx, "engine_detect_frames_raw", !h_src || !h_packed || !d_K_camera || !d_rec || !d_workspace);
+    if (!st) return 1;
     const rtm3d_engine_info& I = st->info;
     // everything either step would refuse, before the first launch: the sources, then the frames' place on the canvas
     if (rtm3d_frames_demosaic_check(I.B, h_src, h_packed, method, dst_order)) return 1;
-    st->src_hw.resize((size_t)I.B * 2);
-    for (int b = 0; b < I.B; ++b) { st->src_hw[2 * b] = h_src[b].h; st->src_hw[2 * b + 1] = h_src[b].w; }
-    if (rtm3d_frame_geometry(I.B, st->src_hw.data(), st->resize_to, I.H, I.W, st->geom.data())) return 1;
+    if (place_frames(st, st->src_hw, [&](int b, int* hw) { hw[0] = h_src[b].h; hw[1] = h_src[b].w; return 0; })) return 1;
     if (rtm3d_frames_demosaic(stream, I.B, h_src, h_packed, method, dst_order)) return 1;
     return rtm3d_engine_detect_frames(ctx, stream, h_packed, st->src_hw.data(), d_K_camera, d_rec, d_kitti, d_workspace);
 }
@@ -591,21 +600,19 @@ extern "C" int rtm3d_engine_detect_frames_jpeg(rtm3d_ctx* ctx, void* stream, con
                                                int16_t* h_stage, int16_t* d_coef, size_t capacity, uint8_t* const* h_packed,
                                                const size_t* h_packed_bytes, int dst_order, int n_threads, const double* d_K_camera,
                                                float* d_rec, double* d_kitti, void* d_workspace) {
-    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
-    if (!st) EFAIL("engine_detect_frames_jpeg: the context was not made by rtm3d_engine_load");
-    if (!h_data || !h_bytes || !h_stage || !d_coef || !h_packed || !h_packed_bytes || !d_K_camera || !d_rec || !d_workspace)
-        EFAIL("engine_detect_frames_jpeg: null argument");
-    if (!st->frames) EFAIL("engine_detect_frames_jpeg: call rtm3d_engine_set_frame_params first");
+    EngineState* st = frames_state(ctx, "engine_detect_frames_jpeg", !h_data || !h_bytes || !h_stage || !d_coef || !h_packed || !h_packed_bytes ||
+                                                                          !d_K_camera || !d_rec || !d_workspace);
+    if (!st) return 1;
     const rtm3d_engine_info& I = st->info;
     // the frames' place on the canvas, before anything is decoded or launched; rtm3d_frames_jpeg refuses the rest before its first launch
-    st->src_hw.resize((size_t)I.B * 2);
-    for (int b = 0; b < I.B; ++b) {
+    const auto header_size = [&](int b, int* hw) {
         rtm3d_jpeg_stream_info J;
         char msg[200];
         if (rt_jpeg_info(h_data[b], h_bytes[b], &J, msg, sizeof(msg))) EFAIL("engine_detect_frames_jpeg: frame %d: %s", b, msg);
-        st->src_hw[2 * b] = J.h; st->src_hw[2 * b + 1] = J.w;
-    }
-    if (rtm3d_frame_geometry(I.B, st->src_hw.data(), st->resize_to, I.H, I.W, st->geom.data())) return 1;
+        hw[0] = J.h; hw[1] = J.w;
+        return 0;
+    };
+    if (place_frames(st, st->src_hw, header_size)) return 1;
     if (rtm3d_frames_jpeg(stream, I.B, h_data, h_bytes, h_stage, d_coef, capacity, h_packed, h_packed_bytes, dst_order, n_threads)) return 1;
     return rtm3d_engine_detect_frames(ctx, stream, h_packed, st->src_hw.data(), d_K_camera, d_rec, d_kitti, d_workspace);
 }
@@ -614,24 +621,20 @@ extern "C" int rtm3d_engine_detect_frames_lens(rtm3d_ctx* ctx, void* stream, con
                                                const int* h_hw, int dst_order, const rtm3d_lens_map* h_maps, uint8_t* const* h_rect,
                                                const uint8_t fill[3], const double* d_K_rect, float* d_rec, double* d_kitti,
                                                void* d_workspace) {
-    EngineState* st = (EngineState*)rt_ctx_engine(ctx);
-    if (!st) EFAIL("engine_detect_frames_lens: the context was not made by rtm3d_engine_load");
-    if (!h_packed || (!h_src && !h_hw) || !h_maps || !h_rect || !fill || !d_K_rect || !d_rec || !d_workspace)
-        EFAIL("engine_detect_frames_lens: null argument");
-    if (!st->frames) EFAIL("engine_detect_frames_lens: call rtm3d_engine_set_frame_params first");
+    EngineState* st = frames_state(ctx, "engine_detect_frames_lens",
+                                   !h_packed || (!h_src && !h_hw) || !h_maps || !h_rect || !fill || !d_K_rect || !d_rec || !d_workspace);
+    if (!st) return 1;
     const rtm3d_engine_info& I = st->info;
     // everything the three steps would refuse, before the first launch: the sources, the maps and both sets of buffers, then
     // the rectified frames' place on the canvas
     if (h_src && rtm3d_frames_convert_check(I.B, h_src, h_packed, dst_order)) return 1;
     st->src_hw.resize((size_t)I.B * 2);
-    st->rect_hw.resize((size_t)I.B * 2);
     for (int b = 0; b < I.B; ++b) {
         st->src_hw[2 * b] = h_src ? h_src[b].h : h_hw[2 * b];
         st->src_hw[2 * b + 1] = h_src ? h_src[b].w : h_hw[2 * b + 1];
     }
     if (rtm3d_frames_remap_check(I.B, h_packed, st->src_hw.data(), h_maps, h_rect, fill)) return 1;
-    for (int b = 0; b < I.B; ++b) { st->rect_hw[2 * b] = h_maps[b].ho; st->rect_hw[2 * b + 1] = h_maps[b].wo; }
-    if (rtm3d_frame_geometry(I.B, st->rect_hw.data(), st->resize_to, I.H, I.W, st->geom.data())) return 1;
+    if (place_frames(st, st->rect_hw, [&](int b, int* hw) { hw[0] = h_maps[b].ho; hw[1] = h_maps[b].wo; return 0; })) return 1;
     if (h_src && rtm3d_frames_convert(stream, I.B, h_src, h_packed, dst_order)) return 1;
     if (rtm3d_frames_remap(stream, I.B, h_packed, st->src_hw.data(), h_maps, h_rect, fill)) return 1;
     return rtm3d_engine_detect_frames(ctx, stream, h_rect, st->rect_hw.data(), d_K_rect, d_rec, d_kitti, d_workspace);

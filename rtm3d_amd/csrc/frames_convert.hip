@@ -1,6 +1,6 @@
 // Pixel formats (include/rtm3d_hip.h, "pixel formats"): camera and decoder surfaces - packed RGB with a row pitch, NV12 / NV21 /
 // I420 / P010, YUYV / UYVY, GRAY8 - to the tightly packed uint8 (h, w, 3) frames every other entry point reads.  One launch
-// per chunk of CONV_MAX_BATCH frames, the per-frame descriptors travel by value (no copy, no memset, no synchronisation).
+// per chunk of FRAME_CHUNK frames (frame_chunks.h), the per-frame descriptors travel by value (no copy, no memset, no synchronisation).
 //
 // Thread mapping (rtm3d_frames_convert_plan returns the same numbers): a frame is cut into runs of CONV_PX pixels of
 // CONV_ROWS consecutive rows (a row pair: a 4:2:0 chroma row is read once); run t = blockIdx.x * CONV_THREADS + threadIdx.x
@@ -16,12 +16,12 @@
 #include <stdint.h>
 
 #include "../../include/rtm3d_hip.h"
+#include "frame_chunks.h"
 #include "rgb_runs.h"
 
 #define CONV_PX 8
 #define CONV_ROWS 2
 #define CONV_THREADS 256
-#define CONV_MAX_BATCH 32
 #define CONV_MAX_SIDE 16384
 
 // [cy, crv, cgu, cgv, cbu] = round(2^S * v), v from (Kr, Kb) and the range scales (the header's table; tests/pixfmt_ref.py derives
@@ -45,7 +45,7 @@ struct ConvFrame {                       // 64 B
     int table;                           // row of c_conv_tab
     int yo_swap;                         // luma offset (0, 16 or 64) | bit 16: exchange the first and third output byte
 };
-struct ConvBatch { ConvFrame f[CONV_MAX_BATCH]; };       // 2 KB of kernel arguments
+struct ConvBatch { ConvFrame f[FRAME_CHUNK]; };          // 2 KB of kernel arguments
 
 // ---- N bytes (a multiple of 8) at p into dwords; only the first n are read, the rest are zero
 template <int N>
@@ -209,8 +209,6 @@ __global__ __launch_bounds__(CONV_THREADS) void frames_convert_kernel(ConvBatch 
     }
 }
 
-extern void rt_set_error(const char* fmt, ...);
-
 // planes, bytes of a row and rows per plane; 1 for an unknown format
 static int src_layout(int format, int h, int w, int* n_planes, int row_bytes[3], int rows[3]) {
     const int cw = (w + 1) / 2, ch = (h + 1) / 2;
@@ -263,17 +261,13 @@ extern "C" int rtm3d_yuv_coefficients(int format, int matrix, int range, int out
 
 // every refusal of the header, for the whole batch; h_dst may be NULL (the plan has no destinations)
 static int check_sources(const char* who, int B, const rtm3d_frame_src* h_src, uint8_t* const* h_dst, int dst_order) {
-    if (B < 1) { rt_set_error("%s: B = %d", who, B); return 1; }
-    if (!h_src) { rt_set_error("%s: null pointer", who); return 1; }
-    if (dst_order != 0 && dst_order != 1) { rt_set_error("%s: dst_order %d (0 R G B, 1 B G R)", who, dst_order); return 1; }
+    if (refuse_count(who, B) || refuse_null(who, h_src) || refuse_order(who, "dst_order", dst_order)) return 1;
     for (int b = 0; b < B; ++b) {
         const rtm3d_frame_src& s = h_src[b];
-        if (s.h < 1 || s.w < 1 || s.h > CONV_MAX_SIDE || s.w > CONV_MAX_SIDE) {
-            rt_set_error("%s: frame %d is %d x %d; a side must lie in 1..%d", who, b, s.h, s.w, CONV_MAX_SIDE); return 1;
-        }
+        if (refuse_side(who, b, s.h, s.w, 1, CONV_MAX_SIDE)) return 1;
         int np, row_bytes[3], rows[3];
         if (src_layout(s.format, s.h, s.w, &np, row_bytes, rows)) { rt_set_error("%s: frame %d has the unknown format %d", who, b, s.format); return 1; }
-        if (s.reserved != 0) { rt_set_error("%s: frame %d: reserved = %d, not 0", who, b, s.reserved); return 1; }
+        if (refuse_reserved(who, b, s.reserved)) return 1;
         if (is_yuv(s.format) && table_row(s.format, s.matrix, s.range) < 0) {
             rt_set_error("%s: frame %d: unknown matrix %d or range %d", who, b, s.matrix, s.range); return 1;
         }
@@ -286,53 +280,48 @@ static int check_sources(const char* who, int B, const rtm3d_frame_src* h_src, u
                 rt_set_error("%s: frame %d: plane %d of a P010 surface has an odd address or pitch", who, b, p); return 1;
             }
         }
-        if (h_dst && !h_dst[b]) { rt_set_error("%s: frame %d: the destination is a NULL pointer", who, b); return 1; }
+        if (h_dst && refuse_null_dst(who, b, h_dst[b])) return 1;
     }
     return 0;
 }
 
-static void plan_chunks(int B, const rtm3d_frame_src* h_src, rtm3d_convert_plan* out) {
-    for (int b0 = 0, k = 0; b0 < B; b0 += CONV_MAX_BATCH, ++k) {
-        rtm3d_convert_plan& P = out[k];
-        P.first = b0;
-        P.count = B - b0 < CONV_MAX_BATCH ? B - b0 : CONV_MAX_BATCH;
-        P.px_per_thread = CONV_PX; P.rows_per_thread = CONV_ROWS; P.threads = CONV_THREADS;
-        P.runs = 0;
-        for (int i = 0; i < P.count; ++i) {
-            const rtm3d_frame_src& s = h_src[b0 + i];
-            const int runs = ((s.w + CONV_PX - 1) / CONV_PX) * ((s.h + CONV_ROWS - 1) / CONV_ROWS);     // <= 2048 * 8192
-            if (runs > P.runs) P.runs = runs;
-        }
-        P.grid_x = (P.runs + CONV_THREADS - 1) / CONV_THREADS;
-        P.grid_y = P.count;
+static rtm3d_convert_plan plan_chunk(const FrameChunk c, const rtm3d_frame_src* h_src) {
+    rtm3d_convert_plan P;
+    P.first = c.b0; P.count = c.nb;
+    P.px_per_thread = CONV_PX; P.rows_per_thread = CONV_ROWS; P.threads = CONV_THREADS;
+    P.runs = 0;
+    for (int i = 0; i < c.nb; ++i) {
+        const rtm3d_frame_src& s = h_src[c.b0 + i];
+        const int runs = ((s.w + CONV_PX - 1) / CONV_PX) * ((s.h + CONV_ROWS - 1) / CONV_ROWS);         // <= 2048 * 8192
+        if (runs > P.runs) P.runs = runs;
     }
+    P.grid_x = (P.runs + CONV_THREADS - 1) / CONV_THREADS;
+    P.grid_y = c.nb;
+    return P;
 }
 
 extern "C" int rtm3d_frames_convert_plan(int B, const rtm3d_frame_src* h_src, rtm3d_convert_plan* out) {
-    if (!out) { rt_set_error("frames_convert_plan: null pointer"); return 1; }
-    if (check_sources("frames_convert_plan", B, h_src, nullptr, 0)) return 1;
-    plan_chunks(B, h_src, out);
+    if (refuse_null("frames_convert_plan", out) || check_sources("frames_convert_plan", B, h_src, nullptr, 0)) return 1;
+    for (const FrameChunk c : frame_chunks(B)) out[c.k] = plan_chunk(c, h_src);
     return 0;
 }
 
 extern "C" int rtm3d_frames_convert_check(int B, const rtm3d_frame_src* h_src, uint8_t* const* h_dst, int dst_order) {
-    if (!h_dst) { rt_set_error("frames_convert: null pointer"); return 1; }
+    if (refuse_null("frames_convert", h_dst)) return 1;
     return check_sources("frames_convert", B, h_src, h_dst, dst_order);
 }
 
 extern "C" int rtm3d_frames_convert(void* stream, int B, const rtm3d_frame_src* h_src, uint8_t* const* h_dst, int dst_order) {
     if (rtm3d_frames_convert_check(B, h_src, h_dst, dst_order)) return 1;       // the whole batch, before the first launch
-    rtm3d_convert_plan plan;
-    for (int b0 = 0; b0 < B; b0 += CONV_MAX_BATCH) {
-        const int nb = B - b0 < CONV_MAX_BATCH ? B - b0 : CONV_MAX_BATCH;
-        plan_chunks(nb, h_src + b0, &plan);                                     // one chunk: the numbers of rtm3d_frames_convert_plan
+    for (const FrameChunk c : frame_chunks(B)) {
+        const rtm3d_convert_plan plan = plan_chunk(c, h_src);                   // the numbers of rtm3d_frames_convert_plan
         ConvBatch fb;
-        for (int i = 0; i < CONV_MAX_BATCH; ++i) {
+        for (int i = 0; i < FRAME_CHUNK; ++i) {
             ConvFrame& f = fb.f[i];
-            if (i >= nb) { f = ConvFrame{{nullptr, nullptr, nullptr}, nullptr, {0, 0, 0}, 0, 0, -1, 0, 0}; continue; }
-            const rtm3d_frame_src& s = h_src[b0 + i];
+            if (i >= c.nb) { f = ConvFrame{{nullptr, nullptr, nullptr}, nullptr, {0, 0, 0}, 0, 0, -1, 0, 0}; continue; }
+            const rtm3d_frame_src& s = h_src[c.b0 + i];
             for (int p = 0; p < 3; ++p) { f.p[p] = (const uint8_t*)s.plane[p]; f.pitch[p] = s.pitch[p]; }
-            f.dst = h_dst[b0 + i];
+            f.dst = h_dst[c.b0 + i];
             f.h = s.h; f.w = s.w; f.format = s.format;
             const bool yuv = is_yuv(s.format);
             f.table = yuv ? table_row(s.format, s.matrix, s.range) : 0;
@@ -343,7 +332,5 @@ extern "C" int rtm3d_frames_convert(void* stream, int B, const rtm3d_frame_src* 
         hipLaunchKernelGGL(frames_convert_kernel, dim3((unsigned)plan.grid_x, (unsigned)plan.grid_y), dim3(CONV_THREADS), 0,
                            (hipStream_t)stream, fb);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("frames_convert launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return launch_ok("frames_convert");
 }

@@ -1,6 +1,6 @@
 // JPEG frames, device side (include/rtm3d_hip.h, "JPEG frames"): the coefficient buffers the host's Huffman decoder
 // (jpeg_host.cpp) wrote become the tightly packed uint8 (h, w, 3) frames every other entry point reads - dequantisation, the
-// 8 x 8 inverse DCT, chroma upsampling and YCbCr -> RGB in ONE launch per chunk of JPG_MAX_BATCH frames; the per-frame
+// 8 x 8 inverse DCT, chroma upsampling and YCbCr -> RGB in ONE launch per chunk of FRAME_CHUNK frames (frame_chunks.h); the per-frame
 // descriptors travel by value (no copy, no memset, no synchronisation).  The chain rtm3d_frames_jpeg is here too.
 //
 // Mapping (rtm3d_frames_jpeg_plan returns the same numbers): workgroup blockIdx.x of frame blockIdx.y takes the tile of
@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/rtm3d_hip.h"
+#include "frame_chunks.h"
 #include "rgb_runs.h"
 
 #define JPG_TW 128
@@ -37,7 +38,6 @@
 #define JPG_PX 8
 #define JPG_ROWS 4
 #define JPG_THREADS 256
-#define JPG_MAX_BATCH 32
 #define JPG_MAX_SIDE 16384
 #define JPG_YBW (JPG_TW / 8)                             // blocks of Y under a tile
 #define JPG_YBH (JPG_TH / 8)
@@ -51,7 +51,7 @@ struct JpgFrame {                        // 32 B
     uint8_t* dst;
     int h, w, mode, pad;
 };
-struct JpgBatch { JpgFrame f[JPG_MAX_BATCH]; };          // 1 KB of kernel arguments
+struct JpgBatch { JpgFrame f[FRAME_CHUNK]; };            // 1 KB of kernel arguments
 
 // ---- the one-dimensional pass of the rule on x0..x7, in place, outputs (v + 2^(S-1)) >> S
 template <int S>
@@ -225,86 +225,75 @@ __global__ __launch_bounds__(JPG_THREADS) void frames_jpeg_kernel(JpgBatch fb, i
     }
 }
 
-extern void rt_set_error(const char* fmt, ...);
 extern int rt_jpeg_info(const uint8_t* data, size_t bytes, rtm3d_jpeg_stream_info* out, char* msg, size_t msg_len);
 extern int rt_jpeg_entropy_decode(const uint8_t* data, size_t bytes, int16_t* h_coef, size_t capacity, char* msg, size_t msg_len);
 
 // every refusal of the header, for the whole batch; h_dst may be NULL (the plan has no destinations)
 static int check_jpeg(const char* who, int B, const rtm3d_jpeg_frame* h_frames, uint8_t* const* h_dst, int dst_order) {
-    if (B < 1) { rt_set_error("%s: B = %d", who, B); return 1; }
-    if (!h_frames) { rt_set_error("%s: null pointer", who); return 1; }
-    if (dst_order != 0 && dst_order != 1) { rt_set_error("%s: dst_order %d (0 R G B, 1 B G R)", who, dst_order); return 1; }
+    if (refuse_count(who, B) || refuse_null(who, h_frames) || refuse_order(who, "dst_order", dst_order)) return 1;
     for (int b = 0; b < B; ++b) {
         const rtm3d_jpeg_frame& s = h_frames[b];
-        if (s.h < 1 || s.w < 1 || s.h > JPG_MAX_SIDE || s.w > JPG_MAX_SIDE) {
-            rt_set_error("%s: frame %d is %d x %d; a side must lie in 1..%d", who, b, s.h, s.w, JPG_MAX_SIDE); return 1;
-        }
+        if (refuse_side(who, b, s.h, s.w, 1, JPG_MAX_SIDE)) return 1;
         if (s.mode < RTM3D_JPEG_GREY || s.mode > RTM3D_JPEG_420) { rt_set_error("%s: frame %d has the unknown mode %d", who, b, s.mode); return 1; }
-        if (s.reserved != 0) { rt_set_error("%s: frame %d: reserved = %d, not 0", who, b, s.reserved); return 1; }
+        if (refuse_reserved(who, b, s.reserved)) return 1;
         if (!s.d_coef) { rt_set_error("%s: frame %d: the coefficient buffer is a NULL pointer", who, b); return 1; }
         if ((uintptr_t)s.d_coef & 15) { rt_set_error("%s: frame %d: the coefficient buffer is not 16-byte aligned", who, b); return 1; }
-        if (h_dst && !h_dst[b]) { rt_set_error("%s: frame %d: the destination is a NULL pointer", who, b); return 1; }
+        if (h_dst && refuse_null_dst(who, b, h_dst[b])) return 1;
     }
     return 0;
 }
 
-static void plan_jpeg_chunks(int B, const rtm3d_jpeg_frame* h_frames, rtm3d_jpeg_plan* out) {
-    for (int b0 = 0, k = 0; b0 < B; b0 += JPG_MAX_BATCH, ++k) {
-        rtm3d_jpeg_plan& P = out[k];
-        P.first = b0;
-        P.count = B - b0 < JPG_MAX_BATCH ? B - b0 : JPG_MAX_BATCH;
-        P.tile_w = JPG_TW; P.tile_h = JPG_TH; P.halo = JPG_HALO; P.threads = JPG_THREADS;
-        P.tiles = 0;
-        for (int i = 0; i < P.count; ++i) {
-            const rtm3d_jpeg_frame& s = h_frames[b0 + i];
-            const int tiles = ((s.w + JPG_TW - 1) / JPG_TW) * ((s.h + JPG_TH - 1) / JPG_TH);            // <= 128 * 256
-            if (tiles > P.tiles) P.tiles = tiles;
-        }
-        P.grid_x = P.tiles;
-        P.grid_y = P.count;
+static rtm3d_jpeg_plan plan_chunk(const FrameChunk c, const rtm3d_jpeg_frame* h_frames) {
+    rtm3d_jpeg_plan P;
+    P.first = c.b0; P.count = c.nb;
+    P.tile_w = JPG_TW; P.tile_h = JPG_TH; P.halo = JPG_HALO; P.threads = JPG_THREADS;
+    P.tiles = 0;
+    for (int i = 0; i < c.nb; ++i) {
+        const rtm3d_jpeg_frame& s = h_frames[c.b0 + i];
+        const int tiles = ((s.w + JPG_TW - 1) / JPG_TW) * ((s.h + JPG_TH - 1) / JPG_TH);                // <= 128 * 256
+        if (tiles > P.tiles) P.tiles = tiles;
     }
+    P.grid_x = P.tiles;
+    P.grid_y = c.nb;
+    return P;
 }
 
 extern "C" int rtm3d_frames_jpeg_plan(int B, const rtm3d_jpeg_frame* h_frames, rtm3d_jpeg_plan* out) {
-    if (!out) { rt_set_error("frames_jpeg_plan: null pointer"); return 1; }
-    if (check_jpeg("frames_jpeg_plan", B, h_frames, nullptr, 0)) return 1;
-    plan_jpeg_chunks(B, h_frames, out);
+    if (refuse_null("frames_jpeg_plan", out) || check_jpeg("frames_jpeg_plan", B, h_frames, nullptr, 0)) return 1;
+    for (const FrameChunk c : frame_chunks(B)) out[c.k] = plan_chunk(c, h_frames);
     return 0;
 }
 
 extern "C" int rtm3d_frames_jpeg_check(int B, const rtm3d_jpeg_frame* h_frames, uint8_t* const* h_dst, int dst_order) {
-    if (!h_dst) { rt_set_error("frames_jpeg_idct: null pointer"); return 1; }
+    if (refuse_null("frames_jpeg_idct", h_dst)) return 1;
     return check_jpeg("frames_jpeg_idct", B, h_frames, h_dst, dst_order);
 }
 
-// one chunk (nb <= JPG_MAX_BATCH frames, already checked)
-static void launch_jpeg_chunk(hipStream_t stream, int nb, const rtm3d_jpeg_frame* h_frames, uint8_t* const* h_dst, int dst_order) {
-    rtm3d_jpeg_plan plan;
-    plan_jpeg_chunks(nb, h_frames, &plan);                                             // the numbers of rtm3d_frames_jpeg_plan
+// one chunk of a batch that is already checked
+static void launch_chunk(hipStream_t stream, const FrameChunk c, const rtm3d_jpeg_frame* h_frames, uint8_t* const* h_dst, int dst_order) {
+    const rtm3d_jpeg_plan plan = plan_chunk(c, h_frames);                              // the numbers of rtm3d_frames_jpeg_plan
     JpgBatch fb;
-    for (int i = 0; i < JPG_MAX_BATCH; ++i) {
+    for (int i = 0; i < FRAME_CHUNK; ++i) {
         JpgFrame& f = fb.f[i];
         f = JpgFrame{};                                                                // (h = w = 0: no tiles)
-        if (i >= nb) continue;
-        f.coef = h_frames[i].d_coef; f.dst = h_dst[i]; f.h = h_frames[i].h; f.w = h_frames[i].w; f.mode = h_frames[i].mode;
+        if (i >= c.nb) continue;
+        const rtm3d_jpeg_frame& s = h_frames[c.b0 + i];
+        f.coef = s.d_coef; f.dst = h_dst[c.b0 + i]; f.h = s.h; f.w = s.w; f.mode = s.mode;
     }
     hipLaunchKernelGGL(frames_jpeg_kernel, dim3((unsigned)plan.grid_x, (unsigned)plan.grid_y), dim3(JPG_THREADS), 0, stream, fb, dst_order);
 }
 
 extern "C" int rtm3d_frames_jpeg_idct(void* stream, int B, const rtm3d_jpeg_frame* h_frames, uint8_t* const* h_dst, int dst_order) {
     if (rtm3d_frames_jpeg_check(B, h_frames, h_dst, dst_order)) return 1;              // the whole batch, before the first launch
-    for (int b0 = 0; b0 < B; b0 += JPG_MAX_BATCH)
-        launch_jpeg_chunk((hipStream_t)stream, B - b0 < JPG_MAX_BATCH ? B - b0 : JPG_MAX_BATCH, h_frames + b0, h_dst + b0, dst_order);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("frames_jpeg_idct launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    for (const FrameChunk c : frame_chunks(B)) launch_chunk((hipStream_t)stream, c, h_frames, h_dst, dst_order);
+    return launch_ok("frames_jpeg_idct");
 }
 
 // ---- the chain: info, refusals, threaded entropy decode, one copy and one launch per chunk
 extern "C" int rtm3d_frames_jpeg(void* stream, int B, const uint8_t* const* h_data, const size_t* h_bytes, int16_t* h_stage, int16_t* d_coef,
                                  size_t capacity, uint8_t* const* h_dst, const size_t* h_dst_bytes, int dst_order, int n_threads) {
     char msg[200];
-    if (B < 1) { rt_set_error("frames_jpeg: B = %d", B); return 1; }
+    if (refuse_count("frames_jpeg", B)) return 1;
     if (!h_data || !h_bytes || !h_stage || !d_coef || !h_dst || !h_dst_bytes) { rt_set_error("frames_jpeg: null pointer"); return 1; }
     if (n_threads < 0 || n_threads > 64) { rt_set_error("frames_jpeg: n_threads = %d (0: min(B, 8); at most 64)", n_threads); return 1; }
     if (((uintptr_t)d_coef & 127) || ((uintptr_t)h_stage & 1)) { rt_set_error("frames_jpeg: d_coef must be 128-byte aligned, h_stage 2-byte"); return 1; }
@@ -352,13 +341,11 @@ extern "C" int rtm3d_frames_jpeg(void* stream, int B, const uint8_t* const* h_da
         for (std::thread& th : pool) th.join();
     }
     if (failed.load() < B) { rt_set_error("frames_jpeg: frame %d: %s", failed.load(), errors[failed.load()].c_str()); return 1; }
-    for (int b0 = 0; b0 < B; b0 += JPG_MAX_BATCH) {
-        const int nb = B - b0 < JPG_MAX_BATCH ? B - b0 : JPG_MAX_BATCH;
-        hipError_t e = hipMemcpyAsync(d_coef + at[b0], h_stage + at[b0], (at[b0 + nb] - at[b0]) * sizeof(int16_t), hipMemcpyHostToDevice, (hipStream_t)stream);
+    for (const FrameChunk c : frame_chunks(B)) {
+        const size_t lo = at[c.b0], hi = at[c.b0 + c.nb];
+        hipError_t e = hipMemcpyAsync(d_coef + lo, h_stage + lo, (hi - lo) * sizeof(int16_t), hipMemcpyHostToDevice, (hipStream_t)stream);
         if (e != hipSuccess) { rt_set_error("frames_jpeg copy: %s", hipGetErrorString(e)); return 1; }
-        launch_jpeg_chunk((hipStream_t)stream, nb, frames.data() + b0, h_dst + b0, dst_order);
+        launch_chunk((hipStream_t)stream, c, frames.data(), h_dst, dst_order);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("frames_jpeg launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return launch_ok("frames_jpeg");
 }

@@ -1,6 +1,6 @@
 // JPEG encoding, device side (include/rtm3d_hip.h, "JPEG encoding"): tightly packed uint8 (h, w, 3) frames become the
 // coefficient buffers the host's Huffman encoder (jpeg_host.cpp) reads - RGB -> YCbCr, edge replication, chroma downsampling,
-// the 8 x 8 forward DCT and the quantisation in ONE launch per chunk of JPE_MAX_BATCH frames; the per-frame descriptors and the
+// the 8 x 8 forward DCT and the quantisation in ONE launch per chunk of FRAME_CHUNK frames (frame_chunks.h); the descriptors and the
 // two tables (with their division multipliers, jpeg_quant.h) travel by value: no copy, no memset, no synchronisation.  The
 // chain rtm3d_frames_jpeg_encode and its two halves are here too.  The buffer is the decoder's (jpeg.hip reads it back).
 //
@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/rtm3d_hip.h"
+#include "frame_chunks.h"
 #include "jpeg_quant.h"
 
 #define JPE_TW 128
@@ -46,7 +47,6 @@
 #define JPE_PX 8
 #define JPE_ROWS 4
 #define JPE_THREADS 256
-#define JPE_MAX_BATCH 32
 #define JPE_MAX_SIDE 16384
 #define JPE_YBW (JPE_TW / 8)                             // blocks of Y under a tile
 #define JPE_YBH (JPE_TH / 8)
@@ -63,7 +63,7 @@ struct JpeFrame {                        // 32 B
     int16_t* coef;
     int h, w, mode, pad;
 };
-struct JpeBatch { JpeFrame f[JPE_MAX_BATCH]; };          // 1 KB of kernel arguments
+struct JpeBatch { JpeFrame f[FRAME_CHUNK]; };            // 1 KB of kernel arguments
 struct JpeTables { uint32_t q[2][64], m[2][64]; };       // 1 KB: luma, chroma in natural order; m = jpeg_quant_multiplier(q)
 
 // ---- pixels x0 .. x0 + 7 of the row at `row` (columns clamped to w - 1), each byte0 | byte1 << 8 | byte2 << 16
@@ -290,7 +290,6 @@ __global__ __launch_bounds__(JPE_THREADS) void frames_jpeg_fdct_kernel(JpeBatch 
     }
 }
 
-extern void rt_set_error(const char* fmt, ...);
 extern int rt_jpeg_frame_layout(int h, int w, int mode, rtm3d_jpeg_stream_info* out, char* msg, size_t msg_len);
 extern int rt_jpeg_encode_bound(int h, int w, int mode, int restart, size_t* bytes, char* msg, size_t msg_len);
 extern int rt_jpeg_entropy_encode(const int16_t* h_coef, int h, int w, int mode, int restart, uint8_t* out, size_t capacity, size_t* bytes, char* msg,
@@ -299,9 +298,8 @@ extern int rt_jpeg_entropy_encode(const int16_t* h_coef, int h, int w, int mode,
 // every refusal of the header, for the whole batch; tables may be NULL (the plan has none)
 static int check_fdct(const char* who, int B, const rtm3d_jpeg_enc_frame* h_frames, bool plan_only, const uint16_t* q_luma, const uint16_t* q_chroma,
                       int src_order) {
-    if (B < 1) { rt_set_error("%s: B = %d", who, B); return 1; }
-    if (!h_frames || (!plan_only && (!q_luma || !q_chroma))) { rt_set_error("%s: null pointer", who); return 1; }
-    if (src_order != 0 && src_order != 1) { rt_set_error("%s: src_order %d (0 R G B, 1 B G R)", who, src_order); return 1; }
+    if (refuse_count(who, B) || refuse_null(who, h_frames) || (!plan_only && (refuse_null(who, q_luma) || refuse_null(who, q_chroma)))) return 1;
+    if (refuse_order(who, "src_order", src_order)) return 1;
     if (!plan_only)
         for (int t = 0; t < 2; ++t)
             for (int k = 0; k < 64; ++k) {
@@ -310,11 +308,9 @@ static int check_fdct(const char* who, int B, const rtm3d_jpeg_enc_frame* h_fram
             }
     for (int b = 0; b < B; ++b) {
         const rtm3d_jpeg_enc_frame& s = h_frames[b];
-        if (s.h < 1 || s.w < 1 || s.h > JPE_MAX_SIDE || s.w > JPE_MAX_SIDE) {
-            rt_set_error("%s: frame %d is %d x %d; a side must lie in 1..%d", who, b, s.h, s.w, JPE_MAX_SIDE); return 1;
-        }
+        if (refuse_side(who, b, s.h, s.w, 1, JPE_MAX_SIDE)) return 1;
         if (s.mode < RTM3D_JPEG_GREY || s.mode > RTM3D_JPEG_420) { rt_set_error("%s: frame %d has the unknown mode %d", who, b, s.mode); return 1; }
-        if (s.reserved != 0) { rt_set_error("%s: frame %d: reserved = %d, not 0", who, b, s.reserved); return 1; }
+        if (refuse_reserved(who, b, s.reserved)) return 1;
         if (plan_only) continue;
         if (!s.d_src) { rt_set_error("%s: frame %d: the source is a NULL pointer", who, b); return 1; }
         if (!s.d_coef) { rt_set_error("%s: frame %d: the coefficient buffer is a NULL pointer", who, b); return 1; }
@@ -323,28 +319,25 @@ static int check_fdct(const char* who, int B, const rtm3d_jpeg_enc_frame* h_fram
     return 0;
 }
 
-static void plan_fdct_chunks(int B, const rtm3d_jpeg_enc_frame* h_frames, rtm3d_jpeg_enc_plan* out) {
-    for (int b0 = 0, k = 0; b0 < B; b0 += JPE_MAX_BATCH, ++k) {
-        rtm3d_jpeg_enc_plan& P = out[k];
-        P.first = b0;
-        P.count = B - b0 < JPE_MAX_BATCH ? B - b0 : JPE_MAX_BATCH;
-        P.tile_w = JPE_TW; P.tile_h = JPE_TH; P.threads = JPE_THREADS;
-        P.lds_stride = JPE_YS; P.lds_stride_sub = JPE_STRIDE(JPE_TW / 2);
-        P.tiles = 0;
-        for (int i = 0; i < P.count; ++i) {
-            const rtm3d_jpeg_enc_frame& s = h_frames[b0 + i];
-            const int tiles = ((s.w + JPE_TW - 1) / JPE_TW) * ((s.h + JPE_TH - 1) / JPE_TH);            // <= 128 * 256
-            if (tiles > P.tiles) P.tiles = tiles;
-        }
-        P.grid_x = P.tiles;
-        P.grid_y = P.count;
+static rtm3d_jpeg_enc_plan plan_chunk(const FrameChunk c, const rtm3d_jpeg_enc_frame* h_frames) {
+    rtm3d_jpeg_enc_plan P;
+    P.first = c.b0; P.count = c.nb;
+    P.tile_w = JPE_TW; P.tile_h = JPE_TH; P.threads = JPE_THREADS;
+    P.lds_stride = JPE_YS; P.lds_stride_sub = JPE_STRIDE(JPE_TW / 2);
+    P.tiles = 0;
+    for (int i = 0; i < c.nb; ++i) {
+        const rtm3d_jpeg_enc_frame& s = h_frames[c.b0 + i];
+        const int tiles = ((s.w + JPE_TW - 1) / JPE_TW) * ((s.h + JPE_TH - 1) / JPE_TH);                // <= 128 * 256
+        if (tiles > P.tiles) P.tiles = tiles;
     }
+    P.grid_x = P.tiles;
+    P.grid_y = c.nb;
+    return P;
 }
 
 extern "C" int rtm3d_frames_jpeg_fdct_plan(int B, const rtm3d_jpeg_enc_frame* h_frames, rtm3d_jpeg_enc_plan* out) {
-    if (!out) { rt_set_error("frames_jpeg_fdct_plan: null pointer"); return 1; }
-    if (check_fdct("frames_jpeg_fdct_plan", B, h_frames, true, nullptr, nullptr, 0)) return 1;
-    plan_fdct_chunks(B, h_frames, out);
+    if (refuse_null("frames_jpeg_fdct_plan", out) || check_fdct("frames_jpeg_fdct_plan", B, h_frames, true, nullptr, nullptr, 0)) return 1;
+    for (const FrameChunk c : frame_chunks(B)) out[c.k] = plan_chunk(c, h_frames);
     return 0;
 }
 
@@ -352,16 +345,16 @@ extern "C" int rtm3d_frames_jpeg_fdct_check(int B, const rtm3d_jpeg_enc_frame* h
     return check_fdct("frames_jpeg_fdct", B, h_frames, false, q_luma, q_chroma, src_order);
 }
 
-// one chunk (nb <= JPE_MAX_BATCH frames, already checked)
-static void launch_fdct_chunk(hipStream_t stream, int nb, const rtm3d_jpeg_enc_frame* h_frames, const JpeTables& T, int src_order) {
-    rtm3d_jpeg_enc_plan plan;
-    plan_fdct_chunks(nb, h_frames, &plan);                                             // the numbers of rtm3d_frames_jpeg_fdct_plan
+// one chunk of a batch that is already checked
+static void launch_chunk(hipStream_t stream, const FrameChunk c, const rtm3d_jpeg_enc_frame* h_frames, const JpeTables& T, int src_order) {
+    const rtm3d_jpeg_enc_plan plan = plan_chunk(c, h_frames);                          // the numbers of rtm3d_frames_jpeg_fdct_plan
     JpeBatch fb;
-    for (int i = 0; i < JPE_MAX_BATCH; ++i) {
+    for (int i = 0; i < FRAME_CHUNK; ++i) {
         JpeFrame& f = fb.f[i];
         f = JpeFrame{};                                                                // (h = w = 0: no tiles)
-        if (i >= nb) continue;
-        f.src = h_frames[i].d_src; f.coef = h_frames[i].d_coef; f.h = h_frames[i].h; f.w = h_frames[i].w; f.mode = h_frames[i].mode;
+        if (i >= c.nb) continue;
+        const rtm3d_jpeg_enc_frame& s = h_frames[c.b0 + i];
+        f.src = s.d_src; f.coef = s.d_coef; f.h = s.h; f.w = s.w; f.mode = s.mode;
     }
     hipLaunchKernelGGL(frames_jpeg_fdct_kernel, dim3((unsigned)plan.grid_x, (unsigned)plan.grid_y), dim3(JPE_THREADS), 0, stream, fb, T, src_order);
 }
@@ -379,18 +372,14 @@ extern "C" int rtm3d_frames_jpeg_fdct(void* stream, int B, const rtm3d_jpeg_enc_
                                       int src_order) {
     if (rtm3d_frames_jpeg_fdct_check(B, h_frames, q_luma, q_chroma, src_order)) return 1;   // the whole batch, before the first launch
     const JpeTables T = make_tables(q_luma, q_chroma);
-    for (int b0 = 0; b0 < B; b0 += JPE_MAX_BATCH)
-        launch_fdct_chunk((hipStream_t)stream, B - b0 < JPE_MAX_BATCH ? B - b0 : JPE_MAX_BATCH, h_frames + b0, T, src_order);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("frames_jpeg_fdct launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    for (const FrameChunk c : frame_chunks(B)) launch_chunk((hipStream_t)stream, c, h_frames, T, src_order);
+    return launch_ok("frames_jpeg_fdct");
 }
 
 // ---- the chain.  The layout of a batch in d_coef / h_stage: frame b at the int16 offset at[b], the sum of the coef_count before it
 static int chain_layout(const char* who, int B, const int* h_hw, int mode, std::vector<size_t>& at) {
     char msg[200];
-    if (B < 1) { rt_set_error("%s: B = %d", who, B); return 1; }
-    if (!h_hw) { rt_set_error("%s: null pointer", who); return 1; }
+    if (refuse_count(who, B) || refuse_null(who, h_hw)) return 1;
     at.assign((size_t)B + 1, 0);
     for (int b = 0; b < B; ++b) {
         rtm3d_jpeg_stream_info I;
@@ -426,15 +415,13 @@ extern "C" int rtm3d_frames_jpeg_encode_queue(void* stream, int B, const uint8_t
     }
     if (check_fdct(who, B, frames.data(), false, q_luma, q_chroma, src_order)) return 1;   // the whole batch, before the first launch
     const JpeTables T = make_tables(q_luma, q_chroma);
-    for (int b0 = 0; b0 < B; b0 += JPE_MAX_BATCH) {
-        const int nb = B - b0 < JPE_MAX_BATCH ? B - b0 : JPE_MAX_BATCH;
-        launch_fdct_chunk((hipStream_t)stream, nb, frames.data() + b0, T, src_order);
-        hipError_t e = hipMemcpyAsync(h_stage + at[b0], d_coef + at[b0], (at[b0 + nb] - at[b0]) * sizeof(int16_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    for (const FrameChunk c : frame_chunks(B)) {
+        launch_chunk((hipStream_t)stream, c, frames.data(), T, src_order);
+        const size_t lo = at[c.b0], hi = at[c.b0 + c.nb];
+        hipError_t e = hipMemcpyAsync(h_stage + lo, d_coef + lo, (hi - lo) * sizeof(int16_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
         if (e != hipSuccess) { rt_set_error("%s copy: %s", who, hipGetErrorString(e)); return 1; }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("%s launch: %s", who, hipGetErrorString(e)); return 1; }
-    return 0;
+    return launch_ok(who);
 }
 
 extern "C" int rtm3d_frames_jpeg_encode_finish(int B, const int* h_hw, int mode, int restart, const int16_t* h_stage, uint8_t* const* h_out,
@@ -487,7 +474,7 @@ extern "C" int rtm3d_frames_jpeg_encode(void* stream, int B, const uint8_t* cons
     const char* who = "frames_jpeg_encode";
     char msg[200];
     // what the second half would refuse without encoding is refused before the first launch
-    if (B < 1) { rt_set_error("%s: B = %d", who, B); return 1; }
+    if (refuse_count(who, B)) return 1;
     if (!h_hw || !h_out || !h_out_capacity || !h_out_bytes) { rt_set_error("%s: null pointer", who); return 1; }
     if (n_threads < 0 || n_threads > 64) { rt_set_error("%s: n_threads = %d (0: min(B, 8); at most 64)", who, n_threads); return 1; }
     for (int b = 0; b < B; ++b) {

@@ -1,5 +1,5 @@
 // Lens undistortion (include/rtm3d_hip.h, "lens undistortion"): rectifying maps built on the device and the bilinear remap of
-// packed uint8 (h, w, 3) frames through them.  One launch per chunk of LENS_MAX_BATCH frames (LENS_BUILD_BATCH maps), the
+// packed uint8 (h, w, 3) frames through them.  One launch per chunk of FRAME_CHUNK frames (frame_chunks.h; LENS_BUILD_BATCH maps), the
 // descriptors travel by value (no copy, no memset, no synchronisation).
 //
 // Remap, thread mapping (rtm3d_frames_remap_plan returns the same numbers): a destination row is cut into runs of LENS_PX
@@ -24,11 +24,11 @@
 #include <string.h>
 
 #include "../../include/rtm3d_hip.h"
+#include "frame_chunks.h"
 #include "rgb_runs.h"
 
 #define LENS_PX 4
 #define LENS_THREADS 256
-#define LENS_MAX_BATCH 32
 #define LENS_BUILD_BATCH 8
 #define LENS_MAX_SIDE 16384
 
@@ -38,7 +38,7 @@ struct LensFrame {                       // 40 B
     const int32_t* map;
     int h, w, ho, wo;
 };
-struct LensBatch { LensFrame f[LENS_MAX_BATCH]; uint32_t fill; };       // 1.3 KB of kernel arguments; fill = c0 | c1 << 8 | c2 << 16
+struct LensBatch { LensFrame f[FRAME_CHUNK]; uint32_t fill; };          // 1.3 KB of kernel arguments; fill = c0 | c1 << 8 | c2 << 16
 
 // the 4 / 2 bytes at any address, low byte first
 __device__ __forceinline__ uint32_t load4(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
@@ -160,14 +160,11 @@ __global__ __launch_bounds__(LENS_THREADS) void lens_map_build_kernel(LensBuildB
 }
 
 // ---------------------------------------------------------------------------------------------------- host
-extern void rt_set_error(const char* fmt, ...);
-
 static bool side_ok(int v) { return v >= 1 && v <= LENS_MAX_SIDE; }
 
 // the refusals that concern the maps alone (the plan has nothing else)
 static int check_maps(const char* who, int B, const rtm3d_lens_map* h_maps) {
-    if (B < 1) { rt_set_error("%s: B = %d", who, B); return 1; }
-    if (!h_maps) { rt_set_error("%s: null pointer", who); return 1; }
+    if (refuse_count(who, B) || refuse_null(who, h_maps)) return 1;
     for (int b = 0; b < B; ++b) {
         const rtm3d_lens_map& m = h_maps[b];
         if (!m.d_map) { rt_set_error("%s: frame %d: the map is a NULL pointer", who, b); return 1; }
@@ -175,32 +172,29 @@ static int check_maps(const char* who, int B, const rtm3d_lens_map* h_maps) {
         if (!side_ok(m.ho) || !side_ok(m.wo)) {
             rt_set_error("%s: frame %d: a map of %d x %d; a side must lie in 1..%d", who, b, m.ho, m.wo, LENS_MAX_SIDE); return 1;
         }
-        if (m.reserved != 0) { rt_set_error("%s: frame %d: reserved = %d, not 0", who, b, m.reserved); return 1; }
+        if (refuse_reserved(who, b, m.reserved)) return 1;
     }
     return 0;
 }
 
-static void plan_chunks(int B, const rtm3d_lens_map* h_maps, rtm3d_remap_plan* out) {
-    for (int b0 = 0, k = 0; b0 < B; b0 += LENS_MAX_BATCH, ++k) {
-        rtm3d_remap_plan& P = out[k];
-        P.first = b0;
-        P.count = B - b0 < LENS_MAX_BATCH ? B - b0 : LENS_MAX_BATCH;
-        P.px_per_thread = LENS_PX; P.threads = LENS_THREADS;
-        P.runs = 0;
-        for (int i = 0; i < P.count; ++i) {
-            const rtm3d_lens_map& m = h_maps[b0 + i];
-            const int runs = ((m.wo + LENS_PX - 1) / LENS_PX) * m.ho;   // <= 4096 * 16384
-            if (runs > P.runs) P.runs = runs;
-        }
-        P.grid_x = (P.runs + LENS_THREADS - 1) / LENS_THREADS;
-        P.grid_y = P.count;
+static rtm3d_remap_plan plan_chunk(const FrameChunk c, const rtm3d_lens_map* h_maps) {
+    rtm3d_remap_plan P;
+    P.first = c.b0; P.count = c.nb;
+    P.px_per_thread = LENS_PX; P.threads = LENS_THREADS;
+    P.runs = 0;
+    for (int i = 0; i < c.nb; ++i) {
+        const rtm3d_lens_map& m = h_maps[c.b0 + i];
+        const int runs = ((m.wo + LENS_PX - 1) / LENS_PX) * m.ho;       // <= 4096 * 16384
+        if (runs > P.runs) P.runs = runs;
     }
+    P.grid_x = (P.runs + LENS_THREADS - 1) / LENS_THREADS;
+    P.grid_y = c.nb;
+    return P;
 }
 
 extern "C" int rtm3d_frames_remap_plan(int B, const rtm3d_lens_map* h_maps, rtm3d_remap_plan* out) {
-    if (!out) { rt_set_error("frames_remap_plan: null pointer"); return 1; }
-    if (check_maps("frames_remap_plan", B, h_maps)) return 1;
-    plan_chunks(B, h_maps, out);
+    if (refuse_null("frames_remap_plan", out) || check_maps("frames_remap_plan", B, h_maps)) return 1;
+    for (const FrameChunk c : frame_chunks(B)) out[c.k] = plan_chunk(c, h_maps);
     return 0;
 }
 
@@ -212,10 +206,7 @@ extern "C" int rtm3d_frames_remap_check(int B, const uint8_t* const* h_src, cons
     for (int b = 0; b < B; ++b) {
         const int h = h_hw[2 * b], w = h_hw[2 * b + 1];
         if (!h_src[b]) { rt_set_error("%s: frame %d: the source is a NULL pointer", who, b); return 1; }
-        if (!h_dst[b]) { rt_set_error("%s: frame %d: the destination is a NULL pointer", who, b); return 1; }
-        if (!side_ok(h) || !side_ok(w)) {
-            rt_set_error("%s: frame %d is %d x %d; a side must lie in 1..%d", who, b, h, w, LENS_MAX_SIDE); return 1;
-        }
+        if (refuse_null_dst(who, b, h_dst[b]) || refuse_side(who, b, h, w, 1, LENS_MAX_SIDE)) return 1;
         const uintptr_t s0 = (uintptr_t)h_src[b], s1 = s0 + (size_t)h * w * 3;
         const uintptr_t d0 = (uintptr_t)h_dst[b], d1 = d0 + (size_t)h_maps[b].ho * h_maps[b].wo * 3;
         if (d0 < s1 && s0 < d1) { rt_set_error("%s: frame %d: the destination overlaps its source", who, b); return 1; }
@@ -226,25 +217,22 @@ extern "C" int rtm3d_frames_remap_check(int B, const uint8_t* const* h_src, cons
 extern "C" int rtm3d_frames_remap(void* stream, int B, const uint8_t* const* h_src, const int* h_hw, const rtm3d_lens_map* h_maps,
                                   uint8_t* const* h_dst, const uint8_t fill[3]) {
     if (rtm3d_frames_remap_check(B, h_src, h_hw, h_maps, h_dst, fill)) return 1;      // the whole batch, before the first launch
-    rtm3d_remap_plan plan;
-    for (int b0 = 0; b0 < B; b0 += LENS_MAX_BATCH) {
-        const int nb = B - b0 < LENS_MAX_BATCH ? B - b0 : LENS_MAX_BATCH;
-        plan_chunks(nb, h_maps + b0, &plan);                                           // one chunk: the numbers of rtm3d_frames_remap_plan
+    for (const FrameChunk c : frame_chunks(B)) {
+        const rtm3d_remap_plan plan = plan_chunk(c, h_maps);                           // the numbers of rtm3d_frames_remap_plan
         LensBatch fb;
         fb.fill = (uint32_t)fill[0] | ((uint32_t)fill[1] << 8) | ((uint32_t)fill[2] << 16);
-        for (int i = 0; i < LENS_MAX_BATCH; ++i) {
+        for (int i = 0; i < FRAME_CHUNK; ++i) {
             LensFrame& f = fb.f[i];
-            if (i >= nb) { f = LensFrame{nullptr, nullptr, nullptr, 0, 0, 0, 0}; continue; }
-            f.src = h_src[b0 + i]; f.dst = h_dst[b0 + i]; f.map = h_maps[b0 + i].d_map;
-            f.h = h_hw[2 * (b0 + i)]; f.w = h_hw[2 * (b0 + i) + 1];
-            f.ho = h_maps[b0 + i].ho; f.wo = h_maps[b0 + i].wo;
+            if (i >= c.nb) { f = LensFrame{nullptr, nullptr, nullptr, 0, 0, 0, 0}; continue; }
+            const int b = c.b0 + i;
+            f.src = h_src[b]; f.dst = h_dst[b]; f.map = h_maps[b].d_map;
+            f.h = h_hw[2 * b]; f.w = h_hw[2 * b + 1];
+            f.ho = h_maps[b].ho; f.wo = h_maps[b].wo;
         }
         hipLaunchKernelGGL(frames_remap_kernel, dim3((unsigned)plan.grid_x, (unsigned)plan.grid_y), dim3(LENS_THREADS), 0,
                            (hipStream_t)stream, fb);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("frames_remap launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return launch_ok("frames_remap");
 }
 
 // no skew, bottom row 0 0 1, positive focal lengths
@@ -291,7 +279,5 @@ extern "C" int rtm3d_lens_map_build(void* stream, int n, const rtm3d_lens_model*
         hipLaunchKernelGGL(lens_map_build_kernel, dim3((unsigned)((px + LENS_THREADS - 1) / LENS_THREADS), (unsigned)nb), dim3(LENS_THREADS),
                            0, (hipStream_t)stream, bb);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { rt_set_error("lens_map_build launch: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return launch_ok(who);
 }

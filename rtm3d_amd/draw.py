@@ -12,7 +12,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _frames, _lib
 
 FACE, BOX2D, WIREFRAME, KEYPOINT, BEV = 1, 2, 4, 8, 16
 LABEL, TRACK_BEV = 32, 64
@@ -133,8 +133,7 @@ def _check_frames(who, images, rec):
     if len(images) != B:
         raise ValueError('%s: %d frames for the records of %d images' % (who, len(images), B))
     for i, img in enumerate(images):
-        if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 \
-                or not img.is_contiguous() or img.device != dev:
+        if not _frames.is_packed_frame(img, device=dev):
             raise ValueError('%s: frame %d must be a contiguous uint8 (h, w, 3) tensor on %s (it is painted in place)' % (who, i, dev))
 
 

@@ -446,6 +446,26 @@ class Engine(object):
             return res + extra
         return res if len(res) > 1 else res[0]
 
+    def _frames_step(self, who, front, K, kitti, out, draw, tracker, nms3d, queued=None):
+        """The body of every detect_frames*: rtm3d_engine_<who> and what follows it.  front(), called on the engine's device
+        once the draw is checked, returns (the entry's own leading arguments, the frames draw= paints, the attributes to
+        remember: last_packed, last_rect); queued() is called right behind the library call.  Returns _result's arguments."""
+        import torch
+        K = self._intrinsics(K)
+        with torch.cuda.device(self.device):
+            self._check_draw(who, draw, tracker)
+            args, paint, remember = front()
+            rec, rows = self._outputs(out, kitti)
+            _lib.check(getattr(self.lib, 'rtm3d_engine_' + who)(
+                self.ctx, _lib.stream_ptr(self.device), *args, ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+                ctypes.c_void_p(rows.data_ptr()) if kitti else None, ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_' + who)
+            if queued is not None:
+                queued()
+            for name, frames in remember.items():
+                setattr(self, name, frames)
+            panels, ids = self._after_step(rec, rows, K, paint, draw, tracker, nms3d)
+        return rec, rows, panels, ids
+
     # (nms3d stays the LAST parameter of detect and detect_frames - tests/test_box_overlap_cpu.py pins it - so tracker, which runs
     # after nms3d, stands before it in the signatures; pass both by keyword)
     def detect(self, x, K_per_image, out=None, tracker=None, nms3d=None):
@@ -489,26 +509,13 @@ class Engine(object):
         (ValueError without one) and paints with the ids of this step and the tracker's table (draw.draw_tracks) instead.
         tracker: as for detect; it runs after nms3d and before draw, and the (B, topk) int32 ids are the last element of what is
         returned.  None launches nothing and returns what is returned without it."""
-        import torch
-        from . import box_overlap
+        from . import _frames, box_overlap
         nms3d = box_overlap.nms3d_options(nms3d)
         images = self._frames_ready('detect_frames', images)
-        imgs = []
-        for img in images:
-            if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_cuda:
-                raise ValueError('expected uint8 (h, w, 3) CUDA frames')
-            imgs.append(img.contiguous())
-        K = self._intrinsics(K_camera)
-        with torch.cuda.device(self.device):
-            self._check_draw('detect_frames', draw, tracker)
-            rec, rows = self._outputs(out, kitti)
-            _lib.check(self.lib.rtm3d_engine_detect_frames(self.ctx, _lib.stream_ptr(self.device), _lib.ptr_array(imgs), _lib.hw_array(imgs),
-                                                           ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
-                                                           ctypes.c_void_p(rows.data_ptr()) if kitti else None,
-                                                           ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames')
-            # (the caller's tensors, not their contiguous copies: the drawing refuses a frame it could not paint in place)
-            panels, ids = self._after_step(rec, rows, K, images, draw, tracker, nms3d)
-        return self._result(rec, rows, panels, ids)
+        imgs = _frames.packed_frames(images)
+        # (draw= paints the caller's tensors, not their contiguous copies: the drawing refuses a frame it could not paint in place)
+        front = lambda: ((_lib.ptr_array(imgs), _lib.hw_array(imgs)), images, {})
+        return self._result(*self._frames_step('detect_frames', front, K_camera, kitti, out, draw, tracker, nms3d))
 
     def detect_frames_rig(self, images, K_camera, rig, kitti=False, nms3d=None, tracker=None, out=None):
         """detect_frames on the R * C frames of a rig.Rig (frame r * C + c = camera c of rig r; the engine's batch is R * C), then
@@ -546,23 +553,15 @@ class Engine(object):
         order: 'rgb' | 'bgr', the byte order of the packed pixels = the channel order the checkpoint was trained on; the
         library cannot know it (the reference's loader hands the network B G R).
         Every other keyword is detect_frames' and what is returned is what it returns; draw= paints into ``packed``."""
-        import torch
         from . import box_overlap, pixfmt
         nms3d = box_overlap.nms3d_options(nms3d)
         sources = self._frames_ready('detect_frames_src', sources)
         src = pixfmt.c_sources(sources)
-        K = self._intrinsics(K_camera)
-        with torch.cuda.device(self.device):
-            self._check_draw('detect_frames_src', draw, tracker)
-            packed = pixfmt.packed_buffers(sources, packed)
-            rec, rows = self._outputs(out, kitti)
-            _lib.check(self.lib.rtm3d_engine_detect_frames_src(
-                self.ctx, _lib.stream_ptr(self.device), src, _lib.ptr_array(packed), pixfmt._lookup(pixfmt.ORDERS, order, 'order'),
-                ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(rows.data_ptr()) if kitti else None,
-                ctypes.c_void_p(self.frames_workspace.data_ptr())), 'engine_detect_frames_src')
-            self.last_packed = packed
-            panels, ids = self._after_step(rec, rows, K, packed, draw, tracker, nms3d)
-        return self._result(rec, rows, panels, ids)
+
+        def front():
+            dst = pixfmt.packed_buffers(sources, packed)
+            return (src, _lib.ptr_array(dst), pixfmt._lookup(pixfmt.ORDERS, order, 'order')), dst, dict(last_packed=dst)
+        return self._result(*self._frames_step('detect_frames_src', front, K_camera, kitti, out, draw, tracker, nms3d))
 
     def detect_frames_raw(self, sources, K_camera, method='mhc', order='rgb', packed=None, kitti=False, out=None, draw=None, tracker=None,
                           nms3d=None):
@@ -575,24 +574,16 @@ class Engine(object):
         checkpoint was trained on.  Every other keyword is detect_frames' and what is returned is what it returns; draw= paints
         into ``packed``.  For a real lens chain the stages yourself: raw.demosaic(sources) gives the packed frames that
         detect_frames_lens(frames, maps) takes."""
-        import torch
         from . import box_overlap, raw
         nms3d = box_overlap.nms3d_options(nms3d)
         sources = self._frames_ready('detect_frames_raw', sources)
         src = raw.c_sources(sources)
-        K = self._intrinsics(K_camera)
-        with torch.cuda.device(self.device):
-            self._check_draw('detect_frames_raw', draw, tracker)
-            packed = raw.packed_buffers(sources, packed)
-            rec, rows = self._outputs(out, kitti)
-            _lib.check(self.lib.rtm3d_engine_detect_frames_raw(
-                self.ctx, _lib.stream_ptr(self.device), src, _lib.ptr_array(packed), raw._lookup(raw.METHODS, method, 'method'),
-                raw._lookup(raw.ORDERS, order, 'order'), ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
-                ctypes.c_void_p(rows.data_ptr()) if kitti else None, ctypes.c_void_p(self.frames_workspace.data_ptr())),
-                'engine_detect_frames_raw')
-            self.last_packed = packed
-            panels, ids = self._after_step(rec, rows, K, packed, draw, tracker, nms3d)
-        return self._result(rec, rows, panels, ids)
+
+        def front():
+            dst = raw.packed_buffers(sources, packed)
+            return (src, _lib.ptr_array(dst), raw._lookup(raw.METHODS, method, 'method'), raw._lookup(raw.ORDERS, order, 'order')), dst, \
+                dict(last_packed=dst)
+        return self._result(*self._frames_step('detect_frames_raw', front, K_camera, kitti, out, draw, tracker, nms3d))
 
     def detect_frames_jpeg(self, datas, K_camera, order='rgb', packed=None, kitti=False, out=None, draw=None, tracker=None, nms3d=None):
         """detect_frames fed by JPEG streams (rtm3d_engine_detect_frames_jpeg), the twin of detect_frames_raw: datas = list of B
@@ -602,29 +593,22 @@ class Engine(object):
         as ``engine.last_packed`` - and the step reads those; the device is never waited for.
         order: 'rgb' | 'bgr', the byte order of the packed pixels = the channel order the checkpoint was trained on.  Every other
         keyword is detect_frames' and what is returned is what it returns; draw= paints into ``packed``."""
-        import torch
         from . import box_overlap, jpeg
         nms3d = box_overlap.nms3d_options(nms3d)
         datas = self._frames_ready('detect_frames_jpeg', datas)
         arrs, ptrs, sizes = jpeg._streams(datas)
         infos = jpeg.batch_info(arrs, 'engine_detect_frames_jpeg')
-        K = self._intrinsics(K_camera)
-        with torch.cuda.device(self.device):
-            self._check_draw('detect_frames_jpeg', draw, tracker)
-            packed = jpeg._destinations([(i['h'], i['w']) for i in infos], packed, self.device)
-            rec, rows = self._outputs(out, kitti)
+        s = None                                 # the staging set of this call
+
+        def front():
+            nonlocal s
+            dst = jpeg._destinations([(i['h'], i['w']) for i in infos], packed, self.device)
             s, cap = jpeg.staging(self.device, sum(i['coef_count'] for i in infos) * 2)
-            nbytes = (ctypes.c_size_t * len(packed))(*[p.numel() for p in packed])
-            _lib.check(self.lib.rtm3d_engine_detect_frames_jpeg(
-                self.ctx, _lib.stream_ptr(self.device), ptrs, sizes, s.host.data_ptr(), s.dev.data_ptr(), cap, _lib.ptr_array(packed), nbytes,
-                jpeg._order(order), 0, ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
-                ctypes.c_void_p(rows.data_ptr()) if kitti else None, ctypes.c_void_p(self.frames_workspace.data_ptr())),
-                'engine_detect_frames_jpeg')
-            s.event = torch.cuda.Event()
-            s.event.record(torch.cuda.current_stream(self.device))
-            self.last_packed = packed
-            panels, ids = self._after_step(rec, rows, K, packed, draw, tracker, nms3d)
-        return self._result(rec, rows, panels, ids)
+            nbytes = (ctypes.c_size_t * len(dst))(*[p.numel() for p in dst])
+            return (ptrs, sizes, s.host.data_ptr(), s.dev.data_ptr(), cap, _lib.ptr_array(dst), nbytes, jpeg._order(order), 0), dst, \
+                dict(last_packed=dst)
+        return self._result(*self._frames_step('detect_frames_jpeg', front, K_camera, kitti, out, draw, tracker, nms3d,
+                                               queued=lambda: s.mark(self.device)))
 
     def detect_frames_lens(self, frames_or_sources, maps, order='rgb', fill=(0, 0, 0), K_rect=None, packed=None, rect=None, kitti=False,
                            out=None, draw=None, tracker=None, nms3d=None):
@@ -636,7 +620,6 @@ class Engine(object):
         synchronises.  Records and KITTI rows are in the pixels and the camera of the rectified frames; draw= paints into them.
         fill: the bytes of a pixel without a source.  Every other keyword is detect_frames'.  Returns what detect_frames
         returns, as a tuple, with the list of rectified frames appended: (records[, rows][, panels][, ids], rect)."""
-        import torch
         from . import box_overlap, lens, pixfmt
         nms3d = box_overlap.nms3d_options(nms3d)
         raw, maps = self._frames_ready('detect_frames_lens', frames_or_sources, maps)
@@ -648,26 +631,20 @@ class Engine(object):
             if any(m.K_rect is None for m in maps):
                 raise ValueError('Engine.detect_frames_lens: a map without K_rect needs K_rect=')
             K_rect = np.stack([m.K_rect for m in maps])
-        K = self._intrinsics(K_rect)
-        with torch.cuda.device(self.device):
-            self._check_draw('detect_frames_lens', draw, tracker)
+
+        def front():
             if from_src:
                 src, hw = pixfmt.c_sources(raw), None
-                packed = pixfmt.packed_buffers(raw, packed)
+                mid = pixfmt.packed_buffers(raw, packed)
             else:
                 src = None
-                packed = lens.packed_frames(raw)
-                hw = _lib.hw_array(packed)
-            rect = lens.rect_buffers(maps, rect)
-            rec, rows = self._outputs(out, kitti)
-            _lib.check(self.lib.rtm3d_engine_detect_frames_lens(
-                self.ctx, _lib.stream_ptr(self.device), src, _lib.ptr_array(packed), hw, pixfmt._lookup(pixfmt.ORDERS, order, 'order'), cm,
-                _lib.ptr_array(rect), lens.c_fill(fill), ctypes.c_void_p(K.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
-                ctypes.c_void_p(rows.data_ptr()) if kitti else None, ctypes.c_void_p(self.frames_workspace.data_ptr())),
-                'engine_detect_frames_lens')
-            self.last_packed, self.last_rect = packed, rect
-            panels, ids = self._after_step(rec, rows, K, rect, draw, tracker, nms3d)
-        return self._result(rec, rows, panels, ids, extra=(rect,))
+                mid = lens.packed_frames(raw)
+                hw = _lib.hw_array(mid)
+            dst = lens.rect_buffers(maps, rect)
+            return (src, _lib.ptr_array(mid), hw, pixfmt._lookup(pixfmt.ORDERS, order, 'order'), cm, _lib.ptr_array(dst), lens.c_fill(fill)), \
+                dst, dict(last_packed=mid, last_rect=dst)
+        res = self._frames_step('detect_frames_lens', front, K_rect, kitti, out, draw, tracker, nms3d)
+        return self._result(*res, extra=(self.last_rect,))
 
     def close(self):
         if self.ctx:

@@ -13,12 +13,12 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _frames, _lib
+from ._frames import CHUNK  # noqa: F401  (a name the tests use)
 
 MODES = {'grey': 0, '444': 1, '422': 2, '420': 3}
 MODE_NAMES = {v: k for k, v in MODES.items()}
 ORDERS = {'rgb': 0, 'bgr': 1}
-CHUNK = 32
 TABLE_WORDS = 192                        # int16 in front of the planes of a coefficient buffer: three tables of 64
 
 
@@ -96,22 +96,11 @@ def plan(frames):
     """rtm3d_frames_jpeg_plan: the launch schedule of idct(frames), one JpegPlan per chunk of 32 frames (host only; ``frames``:
     what c_frames takes, or its result)."""
     arr = frames if isinstance(frames, ctypes.Array) else c_frames(frames)
-    out = (_lib.JpegPlan * ((len(arr) + CHUNK - 1) // CHUNK))()
-    _lib.check(_lib.load().rtm3d_frames_jpeg_plan(len(arr), arr, out), 'frames_jpeg_plan')
-    return list(out)
+    return _frames.chunk_plans('frames_jpeg_plan', _lib.JpegPlan, arr)
 
 
 def _destinations(sizes, out, dev):
-    import torch
-    if out is None:
-        return [torch.empty(h, w, 3, dtype=torch.uint8, device=dev) for h, w in sizes]
-    out = list(out)
-    if len(out) != len(sizes):
-        raise ValueError('%d destinations for %d streams' % (len(out), len(sizes)))
-    for (h, w), o in zip(sizes, out):
-        if not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or not o.is_cuda or tuple(o.shape) != (h, w, 3) or not o.is_contiguous():
-            raise ValueError('a destination is a contiguous uint8 CUDA tensor of its stream\'s (h, w, 3) = %s' % ((h, w, 3),))
-    return out
+    return _frames.packed_buffers(sizes, [dev] * len(sizes), out, 'stream')
 
 
 def idct(frames, order='rgb', out=None):
@@ -143,6 +132,12 @@ class _Staging(object):
         if self.dev is None or self.dev.numel() * 2 < nbytes or self.dev.device != device:
             self.dev = torch.empty(max(nbytes // 2, 1), dtype=torch.int16, device=device)
         return min(self.host.numel(), self.dev.numel()) * 2
+
+    def mark(self, device):
+        """Behind the call that uses the buffers: the event ready() waits for."""
+        import torch
+        self.event = torch.cuda.Event()
+        self.event.record(torch.cuda.current_stream(device))
 
 
 _sets = {}                               # device -> [two _Staging, the index of the next]
@@ -182,8 +177,7 @@ def decode(datas, order='rgb', out=None, threads=0, device=None):
         nbytes = (ctypes.c_size_t * len(out))(*[o.numel() for o in out])
         _lib.check(_lib.load().rtm3d_frames_jpeg(_lib.stream_ptr(dev), len(arrs), ptrs, sizes, s.host.data_ptr(), s.dev.data_ptr(), cap,
                                                  _lib.ptr_array(out), nbytes, _order(order), int(threads)), 'frames_jpeg')
-        s.event = torch.cuda.Event()
-        s.event.record(torch.cuda.current_stream(dev))
+        s.mark(dev)
     return out
 
 
@@ -267,9 +261,7 @@ def fdct_plan(frames):
     """rtm3d_frames_jpeg_fdct_plan: the launch schedule of fdct, one JpegEncPlan per chunk of 32 frames (host only; ``frames``: what
     c_enc_frames takes, or its result)."""
     arr = frames if isinstance(frames, ctypes.Array) else c_enc_frames(frames)
-    out = (_lib.JpegEncPlan * ((len(arr) + CHUNK - 1) // CHUNK))()
-    _lib.check(_lib.load().rtm3d_frames_jpeg_fdct_plan(len(arr), arr, out), 'frames_jpeg_fdct_plan')
-    return list(out)
+    return _frames.chunk_plans('frames_jpeg_fdct_plan', _lib.JpegEncPlan, arr)
 
 
 def _frame_list(frames):
@@ -283,9 +275,8 @@ def _frame_list(frames):
     frames = list(frames)
     if not frames:
         raise ValueError('expected a non-empty list of frames')
-    for f in frames:
-        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or not f.is_cuda or f.dim() != 3 or f.shape[2] != 3 or not f.is_contiguous():
-            raise ValueError('a frame is a contiguous uint8 (h, w, 3) CUDA tensor')
+    if not all(_frames.is_packed_frame(f) for f in frames):
+        raise ValueError('a frame is a contiguous uint8 (h, w, 3) CUDA tensor')
     return frames
 
 
@@ -343,8 +334,7 @@ class Encoder(object):
             cap = s.ready(n.value, dev)
             _lib.check(lib.rtm3d_frames_jpeg_encode_queue(_lib.stream_ptr(dev), len(frames), _lib.ptr_array(frames), hw, self.mode, self.luma.ctypes.data,
                                                           self.chroma.ctypes.data, self.order, s.dev.data_ptr(), s.host.data_ptr(), cap), 'frames_jpeg_encode')
-            s.event = torch.cuda.Event()
-            s.event.record(torch.cuda.current_stream(dev))
+            s.mark(dev)
         self.pending.append((s, len(frames), hw, bounds, frames))          # (the frames stay alive until their kernels have run)
 
     def collect(self):

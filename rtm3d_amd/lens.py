@@ -8,11 +8,11 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _frames, _lib
+from ._frames import CHUNK  # noqa: F401  (a name the tests use)
 
 KINDS = {'brown': 0, 'fisheye': 1}
 OUTSIDE = -2 ** 31
-CHUNK = 32
 
 
 def _k9(K, what='K'):
@@ -110,12 +110,11 @@ def build_maps(models, K_rect=None, R=None, out_size=None, device='cuda'):
     import torch
     models = list(models)
     n = len(models)
-    if not models or not all(isinstance(m, LensModel) for m in models):
-        raise ValueError('expected a non-empty list of LensModel')
+    cm = _frames.struct_array(_lib.LensModelC, models, LensModel)
     Ks = _per_model(K_rect, n, 'K_rect', lambda v: np.asarray(v, np.float64).size == 9)
     Rs = _per_model(R, n, 'R', lambda v: np.asarray(v, np.float64).size == 9)
     sizes = _per_model(out_size, n, 'sizes', lambda v: len(v) == 2 and not hasattr(v[0], '__len__'))
-    cm, cr = (_lib.LensModelC * n)(), (_lib.LensRectC * n)()
+    cr = (_lib.LensRectC * n)()
     dev = torch.device(device)
     dev = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
     maps = []
@@ -124,7 +123,6 @@ def build_maps(models, K_rect=None, R=None, out_size=None, device='cuda'):
             K = m.K if Ks[i] is None else _k9(Ks[i], 'K_rect')
             Rt = np.eye(3).reshape(9) if Rs[i] is None else np.ascontiguousarray(_k9(Rs[i], 'R').reshape(3, 3).T).reshape(9)
             ho, wo = (m.h, m.w) if sizes[i] is None else (int(sizes[i][0]), int(sizes[i][1]))
-            cm[i] = m.c_struct()
             cr[i] = _lib.LensRectC(ho, wo, (ctypes.c_double * 9)(*K), (ctypes.c_double * 9)(*Rt))
             if not (1 <= ho <= 16384 and 1 <= wo <= 16384):
                 raise ValueError('map %d: a map of %d x %d; a side must lie in 1..16384' % (i, ho, wo))
@@ -136,22 +134,14 @@ def build_maps(models, K_rect=None, R=None, out_size=None, device='cuda'):
 
 def c_maps(maps):
     """list of LensMap -> ctypes array of rtm3d_lens_map."""
-    maps = list(maps)
-    if not maps or not all(isinstance(m, LensMap) for m in maps):
-        raise ValueError('expected a non-empty list of LensMap')
-    arr = (_lib.LensMapC * len(maps))()
-    for i, m in enumerate(maps):
-        arr[i] = m.c_struct()
-    return arr
+    return _frames.struct_array(_lib.LensMapC, maps, LensMap)
 
 
 def plan(maps):
     """rtm3d_frames_remap_plan: the launch schedule of remap(frames, maps), one RemapPlan per chunk of 32 frames (host only;
     ``maps``: LensMap list or a ctypes array of LensMapC)."""
     arr = maps if isinstance(maps, ctypes.Array) else c_maps(maps)
-    out = (_lib.RemapPlan * ((len(arr) + CHUNK - 1) // CHUNK))()
-    _lib.check(_lib.load().rtm3d_frames_remap_plan(len(arr), arr, out), 'frames_remap_plan')
-    return list(out)
+    return _frames.chunk_plans('frames_remap_plan', _lib.RemapPlan, arr)
 
 
 def c_fill(fill):
@@ -163,28 +153,12 @@ def c_fill(fill):
 
 def packed_frames(frames):
     """The frames a remap reads: checked (uint8 (h, w, 3) CUDA), made contiguous."""
-    import torch
-    out = []
-    for f in frames:
-        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or not f.is_cuda:
-            raise ValueError('expected uint8 (h, w, 3) CUDA frames')
-        out.append(f.contiguous())
-    return out
+    return _frames.packed_frames(frames)
 
 
 def rect_buffers(maps, out=None):
     """The destination frames of a remap: ``out`` checked (uint8 contiguous CUDA (ho, wo, 3) per map), or new tensors."""
-    import torch
-    if out is None:
-        return [torch.empty(m.size[0], m.size[1], 3, dtype=torch.uint8, device=m.device) for m in maps]
-    out = list(out)
-    if len(out) != len(maps):
-        raise ValueError('%d destinations for %d maps' % (len(out), len(maps)))
-    for m, o in zip(maps, out):
-        if not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or not o.is_cuda or tuple(o.shape) != m.size + (3,) \
-                or not o.is_contiguous():
-            raise ValueError('a destination is a contiguous uint8 CUDA tensor of its map\'s (ho, wo, 3) = %s' % (m.size + (3,),))
-    return out
+    return _frames.packed_buffers([m.size for m in maps], [m.device for m in maps], out, 'map', '(ho, wo, 3)')
 
 
 def remap(frames, maps, fill=(0, 0, 0), out=None):

@@ -5,7 +5,8 @@ that Engine.detect_frames, preprocess_batch and the drawing entry points read - 
 tests/pixfmt_ref.py restates it in numpy."""
 import ctypes
 
-from . import _lib
+from . import _frames, _lib
+from ._frames import CHUNK, lookup as _lookup  # noqa: F401  (names the tests and the engine use)
 
 FORMATS = {'rgb24': 0, 'bgr24': 1, 'rgba32': 2, 'bgra32': 3, 'gray8': 4, 'nv12': 5, 'nv21': 6, 'i420': 7, 'yuyv': 8, 'uyvy': 9,
            'p010': 10}
@@ -13,7 +14,6 @@ _ALIASES = {'rgb': 'rgb24', 'bgr': 'bgr24', 'rgba': 'rgba32', 'bgra': 'bgra32', 
 MATRICES = {'bt601': 0, 'bt709': 1}
 RANGES = {'limited': 0, 'full': 1}
 ORDERS = {'rgb': 0, 'bgr': 1}
-CHUNK = 32
 
 
 def format_id(format):
@@ -27,14 +27,6 @@ def format_id(format):
     if int(format) not in FORMATS.values():
         raise ValueError('unknown pixel format %r' % (format,))
     return int(format)
-
-
-def _lookup(table, v, what):
-    if isinstance(v, str):
-        if v.lower() not in table:
-            raise ValueError('unknown %s %r (one of %s)' % (what, v, ', '.join(sorted(table))))
-        return table[v.lower()]
-    return int(v)                        # a number is passed on: the library refuses what it does not know
 
 
 def layout(format, h, w):
@@ -78,19 +70,12 @@ class FrameSource(object):
                 (t.dtype == torch.uint8 or (self.format == FORMATS['p010'] and t.dtype == torch.uint16))
             if not ok:
                 raise ValueError('plane %d: expected a uint8 (P010: uint16 or uint8) CUDA tensor of 1 to 3 dimensions' % i)
-            if t.dim() == 1:
-                own.append(None)
-                continue
-            inner = list(zip(t.shape[1:], t.stride()[1:]))
-            if inner[-1][1] != 1 or (len(inner) == 2 and inner[0][1] != inner[1][0]):
-                raise ValueError('plane %d: the bytes of a row must be contiguous (strides %s)' % (i, tuple(t.stride())))
-            own.append(int(t.stride(0)) * t.element_size() if t.shape[0] > 1 else
-                       int(t.shape[1] * (t.shape[2] if t.dim() == 3 else 1)) * t.element_size())
+            own.append(_frames.plane_pitch(t, 'plane %d' % i))
         if size is None:
             p0 = planes[0]
             if p0.dim() == 1:
                 raise ValueError('a 1-D plane is a raw buffer: give size=(h, w) and pitches=')
-            h, row = int(p0.shape[0]), int(p0.shape[1] * (p0.shape[2] if p0.dim() == 3 else 1)) * p0.element_size()
+            h, row = int(p0.shape[0]), _frames.plane_row_bytes(p0)
             bpp = {0: 3, 1: 3, 2: 4, 3: 4, 4: 1, 5: 1, 6: 1, 7: 1, 8: 2, 9: 2, 10: 2}[self.format]
             if row % bpp:
                 raise ValueError('plane 0 has rows of %d bytes, no multiple of %d' % (row, bpp))
@@ -104,20 +89,11 @@ class FrameSource(object):
         if len(pitches) != len(planes):
             raise ValueError('%d pitches for %d planes' % (len(pitches), len(planes)))
         self.planes, self.pitches = planes, pitches
-        # what the tensors hold must cover what the kernel reads: rows x row bytes of every plane (the library cannot see sizes)
         need = layout(self.format, self.h, self.w)
         if len(need) != len(planes):
             raise ValueError('format %d has %d planes, got %d' % (self.format, len(need), len(planes)))
         for i, (t, (row, rows)) in enumerate(zip(planes, need)):
-            if t.dim() == 1:
-                have = t.numel() * t.element_size()
-                if pitches[i] >= row and have < (rows - 1) * pitches[i] + row:
-                    raise ValueError('plane %d holds %d bytes, %d rows of %d at pitch %d need %d' % (i, have, rows, row, pitches[i],
-                                                                                                   (rows - 1) * pitches[i] + row))
-            else:
-                trow = int(t.shape[1] * (t.shape[2] if t.dim() == 3 else 1)) * t.element_size()
-                if t.shape[0] < rows or trow < row:
-                    raise ValueError('plane %d is %d rows of %d bytes, the format needs %d rows of %d' % (i, t.shape[0], trow, rows, row))
+            _frames.check_plane_covers(t, pitches[i], row, rows, 'plane %d' % i, 'format')
 
     # ---- constructors by layout
     @classmethod
@@ -167,37 +143,19 @@ class FrameSource(object):
 
 def c_sources(sources):
     """list of FrameSource -> ctypes array of rtm3d_frame_src."""
-    sources = list(sources)
-    if not sources or not all(isinstance(s, FrameSource) for s in sources):
-        raise ValueError('expected a non-empty list of FrameSource')
-    arr = (_lib.FrameSrc * len(sources))()
-    for i, s in enumerate(sources):
-        arr[i] = s.c_struct()
-    return arr
+    return _frames.struct_array(_lib.FrameSrc, sources, FrameSource)
 
 
 def plan(sources):
     """rtm3d_frames_convert_plan: the launch schedule of convert(sources), one ConvertPlan per chunk of 32 frames (host only;
     ``sources``: FrameSource list or a ctypes array of FrameSrc)."""
     arr = sources if isinstance(sources, ctypes.Array) else c_sources(sources)
-    out = (_lib.ConvertPlan * ((len(arr) + CHUNK - 1) // CHUNK))()
-    _lib.check(_lib.load().rtm3d_frames_convert_plan(len(arr), arr, out), 'frames_convert_plan')
-    return list(out)
+    return _frames.chunk_plans('frames_convert_plan', _lib.ConvertPlan, arr)
 
 
 def packed_buffers(sources, out=None):
     """The destination frames of a conversion: ``out`` checked (uint8 contiguous CUDA (h, w, 3) per source), or new tensors."""
-    import torch
-    if out is None:
-        return [torch.empty(s.h, s.w, 3, dtype=torch.uint8, device=s.device) for s in sources]
-    out = list(out)
-    if len(out) != len(sources):
-        raise ValueError('%d destinations for %d sources' % (len(out), len(sources)))
-    for s, o in zip(sources, out):
-        if not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or not o.is_cuda or tuple(o.shape) != (s.h, s.w, 3) \
-                or not o.is_contiguous():
-            raise ValueError('a destination is a contiguous uint8 CUDA tensor of its source\'s (h, w, 3) = %s' % ((s.h, s.w, 3),))
-    return out
+    return _frames.packed_buffers([(s.h, s.w) for s in sources], [s.device for s in sources], out, 'source')
 
 
 def convert(sources, order='rgb', out=None):

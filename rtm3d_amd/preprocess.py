@@ -19,7 +19,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _frames, _lib
 
 
 def normalize_lut(mean, std):
@@ -65,10 +65,7 @@ def letterbox_normalize(images, size, mean, std, out=None):
         sums = torch.zeros(B, 3, dtype=torch.int64, device=dev)
         pads = []
         stream = _lib.stream_ptr(dev)
-        for b, img in enumerate(images):
-            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
-                raise ValueError('expected uint8 (h, w, 3) images')
-            img = img.contiguous()
+        for b, img in enumerate(_frames.packed_frames(images, 'expected uint8 (h, w, 3) images')):
             h, w = int(img.shape[0]), int(img.shape[1])
             _lib.check(lib.rtm3d_preprocess(stream, img.data_ptr(), h, w, out[b].data_ptr(), H, W, lut.data_ptr(), sums[b].data_ptr()),
                        'preprocess')
@@ -117,11 +114,7 @@ def preprocess_batch(images, size, mean, std, resize_to=None, out=None, model=No
     if dev.type != 'cuda':
         raise RuntimeError('rtm3d_amd.preprocess needs CUDA (ROCm) tensors; there is no CPU path')
     B = len(images)
-    imgs = []
-    for img in images:
-        if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
-            raise ValueError('expected uint8 (h, w, 3) images')
-        imgs.append(img.contiguous())
+    imgs = _frames.packed_frames(images, 'expected uint8 (h, w, 3) images')
     hw = np.array([[int(i.shape[0]), int(i.shape[1])] for i in imgs], np.int32)
     rhw = np.array([resized_size(h, w, resize_to) if resize_to else (h, w) for h, w in hw], np.int32)
     if (rhw[:, 0] > H).any() or (rhw[:, 1] > W).any() or (rhw < 1).any():

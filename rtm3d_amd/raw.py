@@ -8,7 +8,8 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _frames, _lib
+from ._frames import CHUNK, lookup as _lookup  # noqa: F401  (names the tests and the engine use)
 
 LAYOUTS = {'u8': 0, 'u16': 1, 'u16_msb': 2, 'mipi10': 3, 'mipi12': 4}
 _ALIASES = {'raw8': 'u8', 'raw16': 'u16', 'raw10': 'mipi10', 'raw12': 'mipi12'}
@@ -19,19 +20,8 @@ PATTERNS = {'rggb': 0, 'bggr': 1, 'grbg': 2, 'gbrg': 3}
 PATTERN_CELLS = {'rggb': (0, 1, 1, 2), 'bggr': (2, 1, 1, 0), 'grbg': (1, 0, 2, 1), 'gbrg': (1, 2, 0, 1)}
 METHODS = {'mhc': 0, 'bilinear': 1}
 ORDERS = {'rgb': 0, 'bgr': 1}
-CHUNK = 32
 TONE_SIZE = 4096
 MAX_GAIN, MAX_CCM = 16384, 8192
-
-
-def _lookup(table, v, what, aliases=None):
-    if isinstance(v, str):
-        name = v.lower()
-        name = (aliases or {}).get(name, name)
-        if name not in table:
-            raise ValueError('unknown %s %r (one of %s)' % (what, v, ', '.join(sorted(table))))
-        return table[name]
-    return int(v)                        # a number is passed on: the library refuses what it does not know
 
 
 def layout_id(layout):
@@ -146,11 +136,7 @@ class RawSource(object):
         if not ok:
             raise ValueError('plane: expected a uint8 (u16 layouts: uint16, int16 or uint8) CUDA tensor of 1 or 2 dimensions')
         es = plane.element_size()
-        own = None
-        if plane.dim() == 2:
-            if plane.stride(1) != 1:
-                raise ValueError('plane: the bytes of a row must be contiguous (strides %s)' % (tuple(plane.stride()),))
-            own = int(plane.stride(0)) * es if plane.shape[0] > 1 else int(plane.shape[1]) * es
+        own = _frames.plane_pitch(plane, 'plane')
         if size is None:
             if plane.dim() == 1 or name in ('mipi10', 'mipi12'):
                 raise ValueError('a 1-D plane or a MIPI plane does not tell its size: give size=(h, w)')
@@ -171,17 +157,8 @@ class RawSource(object):
                     or tone.numel() != TONE_SIZE or not tone.is_contiguous() or tone.device != plane.device:
                 raise ValueError('tone: a contiguous uint8 CUDA tensor of %d on the plane\'s device' % TONE_SIZE)
         self.tone = tone
-        # what the tensor holds must cover what the kernel reads: rows x row bytes (the library cannot see sizes)
         row, rows = _plane_layout(self.layout, self.bits, self.h, self.w)
-        if plane.dim() == 1:
-            have = plane.numel() * es
-            if self.pitch >= row and have < (rows - 1) * self.pitch + row:
-                raise ValueError('plane holds %d bytes, %d rows of %d at pitch %d need %d' % (have, rows, row, self.pitch,
-                                                                                            (rows - 1) * self.pitch + row))
-        else:
-            trow = int(plane.shape[1]) * es
-            if plane.shape[0] < rows or trow < row:
-                raise ValueError('plane is %d rows of %d bytes, the layout needs %d rows of %d' % (plane.shape[0], trow, rows, row))
+        _frames.check_plane_covers(plane, self.pitch, row, rows, 'plane', 'layout')
 
     @property
     def device(self):
@@ -201,22 +178,14 @@ class RawSource(object):
 
 def c_sources(sources):
     """list of RawSource -> ctypes array of rtm3d_raw_src."""
-    sources = list(sources)
-    if not sources or not all(isinstance(s, RawSource) for s in sources):
-        raise ValueError('expected a non-empty list of RawSource')
-    arr = (_lib.RawSrc * len(sources))()
-    for i, s in enumerate(sources):
-        arr[i] = s.c_struct()
-    return arr
+    return _frames.struct_array(_lib.RawSrc, sources, RawSource)
 
 
 def plan(sources, method='mhc'):
     """rtm3d_frames_demosaic_plan: the launch schedule of demosaic(sources), one DemosaicPlan per chunk of 32 frames (host only;
     ``sources``: RawSource list or a ctypes array of RawSrc)."""
     arr = sources if isinstance(sources, ctypes.Array) else c_sources(sources)
-    out = (_lib.DemosaicPlan * ((len(arr) + CHUNK - 1) // CHUNK))()
-    _lib.check(_lib.load().rtm3d_frames_demosaic_plan(len(arr), arr, _lookup(METHODS, method, 'method'), out), 'frames_demosaic_plan')
-    return list(out)
+    return _frames.chunk_plans('frames_demosaic_plan', _lib.DemosaicPlan, arr, _lookup(METHODS, method, 'method'))
 
 
 def packed_buffers(sources, out=None):

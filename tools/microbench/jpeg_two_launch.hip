@@ -12,7 +12,7 @@ int rt_jpeg_info(const uint8_t*, size_t, rtm3d_jpeg_stream_info*, char*, size_t)
 int rt_jpeg_entropy_decode(const uint8_t*, size_t, int16_t*, size_t, char*, size_t) { return 1; }
 
 struct TwoFrame { const int16_t* coef; uint8_t* dst; uint8_t* ws; int h, w, mode, pad; };
-struct TwoBatch { TwoFrame f[JPG_MAX_BATCH]; };
+struct TwoBatch { TwoFrame f[FRAME_CHUNK]; };
 
 struct Geo { int hx, vy, mcus_x, mcus_y, ybw, ybh, cw, ch; size_t ny, nc; };
 __device__ __forceinline__ Geo geo_of(int h, int w, int mode) {
@@ -86,11 +86,11 @@ __global__ __launch_bounds__(JPG_THREADS) void pixels_kernel(TwoBatch fb, int ds
 
 // B <= 32 frames of one chunk; h_ws[b]: DEVICE workspace of (coef_count - 192) bytes, 16-byte aligned
 extern "C" int two_launch(void* stream, int B, const rtm3d_jpeg_frame* h_frames, uint8_t* const* h_dst, uint8_t* const* h_ws, int dst_order) {
-    if (B < 1 || B > JPG_MAX_BATCH) return 1;
+    if (B < 1 || B > FRAME_CHUNK) return 1;
     TwoBatch fb;
     size_t max_blocks = 0;
     int max_tiles = 0;
-    for (int i = 0; i < JPG_MAX_BATCH; ++i) {
+    for (int i = 0; i < FRAME_CHUNK; ++i) {
         TwoFrame& f = fb.f[i];
         f = TwoFrame{};
         if (i >= B) continue;
