@@ -2064,6 +2064,99 @@ int rtm3d_optim_step(void* stream, const rtm3d_optim_segment* d_segment_table, c
                      const rtm3d_optim_hyper* hyper, const float* d_loss, unsigned* d_skipped);
 /* d_segment_table, d_chunk_table: the two tables on the DEVICE; hyper: HOST; d_loss: DEVICE fp32 or NULL; d_skipped: DEVICE uint32. */
 
+/* ---- head backward (rtm3d_amd/head_train.py): from dL/dlogits to the gradients of the detection heads' conv parameters ---------
+ * The link between rtm3d_loss_grad and rtm3d_optim_step for the G head branches (models/nets/header.py): per branch a 3x3
+ * dilation-6 conv 256 -> 256 + BN + ReLU on the fused map z, (HEADER_NUM_CONV - 1) x [3x3 conv 256 -> 256 + BN + ReLU], and a final
+ * 3x3 conv 256 -> K with bias.  The forward's activations (z, h1, h2 ... in the plan's workspace) are the saved activations.
+ *
+ * DEVIATION: BatchNorm is FROZEN.  Running statistics and the affine pair are constants (FrozenBatchNorm: the function the folded
+ * plan computes); the reference trains BN on batch statistics.  Trainable: weight and bias of every head conv.
+ *
+ * THE RULE.  s = gamma / sqrt(var + eps); Wf = fp16(s w), the folded weight as the forward used it; S a power-of-two grad_scale.
+ *   1. go = fp16(S dL/dlogit), gathered from the G fp32 NCHW maps into one NHWC map, 16 channels per head (k >= K: zero).
+ *   2. final conv of head g:   dWo[k][c][tap] = (1/S) sum_p go[p][k] h_last[p + tap][c],     dbo[k] = (1/S) sum_p go[p][k]
+ *   3. dh_last[p][c] = fp16( [h_last[p][c] > 0] sum_{k, tap} go[p - tap][k] Wo[k][c][tap] )          (Wo = fp16(wo))
+ *   4. each 256 -> 256 conv, last to first, with dY the gradient at its output and X its input, dilation d:
+ *          dWf[co][ci][tap] = (1/S) sum_p dY[p][co] X[p + d tap][ci],      dbf[co] = (1/S) sum_p dY[p][co]
+ *          dX[p][ci] = fp16( [X[p][ci] > 0] sum_{co, tap} dY[p - d tap][co] Wf[co][ci][tap] )   if a conv precedes it or dz is wanted;
+ *      z carries no mask, and dz sums over the G branches (one accumulator, branch after branch).
+ *   5. dw = s[co] dWf, db = s[co] dbf, in fp32 after the reduction.  The final convs have no BN.
+ * tap = (ky - 1, kx - 1), ky-major, as torch's cross-correlation.  Every product is an fp16 x fp16 MFMA product with fp32
+ * accumulation; the only fp16 roundings of gradients are the ones written above (dz is stored as fp16 too, still scaled by S).
+ * Parameter gradients leave as fp32, unscaled, in torch's (cout, cin, 3, 3) order.  NO FLOAT ATOMICS: the sums over the
+ * B H W pixels are cut into slices of whole 32-pixel tiles (rtm3d_head_backward_slices), each slice writes a partial to the
+ * workspace, and a second pass adds the partials in slice order - two runs on equal inputs leave equal bytes.  The order of the
+ * additions inside a slice is the kernel's (MFMA order) and not part of the rule.  The bias sums use slices of their own: at most
+ * 1024 runs of ceil(B H W / 1024) consecutive pixels, added in pixel order inside a run, the runs in index order.  Every produced parameter gradient that is NaN or
+ * +-Inf adds 1 to *d_nonfinite (an integer atomic; no host synchronisation).
+ *
+ * MAPS (rtm3d_hb_map): fp16 NHWC [B][H + 2 P][W + 2 P][C] with a border of P pixels, as rtm3d_tensor_info describes the plan's
+ * tensors; branch g's channels are coff + g * gstride .. .  A gradient map needs the border of its reader's taps (go: 1, the
+ * gradient at a dilation-d conv's output: d) and that border must be ZERO: the launches write interior pixels only, so a map
+ * that was cleared once stays valid.  An activation map needs the border of the conv that read it (z: 6, h: 1).
+ *
+ * ENTRY POINTS.  All take raw device pointers plus geometry, check on the HOST first and launch nothing when they refuse
+ * (RTM3D_HB_E_*, the message in rtm3d_last_error):
+ *   E_NULL a NULL argument; E_SHAPE B, H, W outside 1 .. 16384 or B H W >= 2^31; E_GROUPS a branch count other than 1, 2, 4;
+ *   E_CHANNELS K outside 1 .. 16, a channel width other than 16 / 256, offsets that are no multiple of 8 or leave the map,
+ *   branches of dY that are not adjacent; E_NUM_CONV HEADER_NUM_CONV < 1; E_SCALE a grad_scale that is no power of two;
+ *   E_SLICES a slice count outside 1 .. RTM3D_HB_MAX_SLICES (or a refresh job count outside 1 .. RTM3D_HB_MAX_JOBS); E_BORDER a border narrower than the taps; E_ALIGN an address that is
+ *   no multiple of 16 (maps, weights, workspace) or 4 (fp32); E_WORKSPACE a workspace that is too small; E_LAUNCH.
+ * rtm3d_head_backward_check / _slices / _workspace_bytes are HOST functions and run without a GPU.
+ * rtm3d_head_backward_slices: ntiles = ceil(npix / 32); tiles_per_slice = ceil(ntiles / want); n_slices = ceil(ntiles /
+ * tiles_per_slice) <= want - every slice but the last holds tiles_per_slice tiles, the last the remainder, none is empty.
+ *
+ * REFRESH.  After an optimiser step the plan's packed fp16 weights, fp32 biases and the rotated dgrad copies are stale.
+ * rtm3d_head_refresh rebuilds them in ONE launch from a table of jobs: packed[i] = fp16(fp32(w[perm[i]] * s[c])) (kind 0) or
+ * fp32((b[perm[i]] - mean[c]) * s[c] + beta[c]) (kind 1), the product and the sum in fp64 without contraction - the operations
+ * of the host fold, so the bytes are the host packers' bytes.  w / b: one fp32 arena of all parameters; c = scale_of[perm[i]]
+ * names a row {s, mean, beta} of the fp64 table bn (a conv without BN: {1, 0, 0}); perm[i] < 0 is a padding element, zero.
+ * The caller builds perm ONCE by sending index arrays through the packers and guarantees 0 <= perm[i] < arena size or < 0.
+ *
+ * OUT OF SCOPE: the neck's and the backbone's backward (dz is the hand-off), training BatchNorm, head_precision = 'mxfp8'.  */
+#define RTM3D_HB_MAX_SLICES 256
+#define RTM3D_HB_MAX_JOBS 64
+enum { RTM3D_HB_E_NULL = 1, RTM3D_HB_E_SHAPE = 2, RTM3D_HB_E_GROUPS = 3, RTM3D_HB_E_CHANNELS = 4, RTM3D_HB_E_NUM_CONV = 5,
+       RTM3D_HB_E_SCALE = 6, RTM3D_HB_E_SLICES = 7, RTM3D_HB_E_BORDER = 8, RTM3D_HB_E_ALIGN = 9, RTM3D_HB_E_WORKSPACE = 10,
+       RTM3D_HB_E_LAUNCH = 11 };
+typedef struct rtm3d_hb_map {
+    void* d;                               /* DEVICE address of padded element [0][0][0][0] */
+    int C;                                 /* channels of the tensor */
+    int P;                                 /* border in pixels */
+    int coff;                              /* first channel of branch 0 */
+    int gstride;                           /* channels from one branch to the next */
+} rtm3d_hb_map;
+typedef struct rtm3d_hb_refresh_job {
+    void* dst;                             /* DEVICE: fp16 (kind 0) or fp32 (kind 1) array of n elements */
+    const void* perm;                      /* DEVICE: n int32 indices into the parameter arena, < 0 for padding */
+    long long n;
+    int kind;                              /* 0: folded fp16 weights, 1: folded fp32 biases */
+    int reserved;                          /* 0 */
+} rtm3d_hb_refresh_job;
+int rtm3d_head_backward_check(int B, int H, int W, int G, const int* K, int num_conv, float grad_scale);
+int rtm3d_head_backward_slices(long long npix, int want, int* n_slices, int* tiles_per_slice);
+size_t rtm3d_head_backward_workspace_bytes(int G, int n_slices);      /* 0 for a G or slice count the launches refuse */
+/* step 1.  d_dlogit[G]: HOST array of DEVICE fp32 (B, K[g], H, W); go: 16 channels per head, written on the interior. */
+int rtm3d_head_go(void* stream, int B, int H, int W, int G, const int* K, const float* const* d_dlogit, float grad_scale,
+                  const rtm3d_hb_map* go);
+/* steps 2, 4, 5 of one conv layer of all G branches: dY has cout (16: final conv, 256) channels per branch, X 256 with a border
+ * >= dil.  d_s[g]: the 256 BN scales or NULL (d_s itself may be NULL); d_dw[g]: (cout_valid[g], 256, 3, 3) fp32 or NULL;
+ * d_db[g]: cout_valid[g] fp32 or NULL - a NULL output is skipped and the others are the bits of the full call.  d_ws:
+ * rtm3d_head_backward_workspace_bytes(G, n_slices) bytes for the n_slices that `want_slices` gives at B H W pixels. */
+int rtm3d_head_wgrad(void* stream, int B, int H, int W, int G, int dil, int cout, const int* cout_valid, const rtm3d_hb_map* dy,
+                     const rtm3d_hb_map* x, float grad_scale, const float* const* d_s, float* const* d_dw, float* const* d_db,
+                     int want_slices, void* d_ws, size_t ws_bytes, unsigned* d_nonfinite);
+/* steps 3, 4: dX of n_out branches, each summing n_sum branches of dY (one of the two counts is 1: n_sum = G gives dz).  dY: kc
+ * (16 / 256) channels per branch, zero border >= dil; d_wr: the rotated weights fp16 [branch][tap][ci = 256][kc], element =
+ * Wf[co = k][ci][tap]; mask: X (256 channels per output branch) or NULL / d == NULL for none; out: 256 channels per output branch. */
+int rtm3d_head_dgrad(void* stream, int B, int H, int W, int n_out, int n_sum, int dil, int kc, const rtm3d_hb_map* dy,
+                     const void* d_wr, const rtm3d_hb_map* mask, const rtm3d_hb_map* out);
+/* h_jobs: the n_jobs descriptors on the HOST (checked: rtm3d_head_refresh_check, callable without a GPU), d_jobs: the same table on
+ * the DEVICE (8-byte aligned); d_bn: fp64 rows {s, mean, beta}. */
+int rtm3d_head_refresh_check(int n_jobs, const rtm3d_hb_refresh_job* jobs);
+int rtm3d_head_refresh(void* stream, int n_jobs, const rtm3d_hb_refresh_job* h_jobs, const rtm3d_hb_refresh_job* d_jobs,
+                       const float* d_arena, const int* d_scale_of, const double* d_bn);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,5 +7,6 @@ from .model_factory import create_model                       # noqa: F401
 from .model import Model                                      # noqa: F401
 from .ParamList import ParamList                              # noqa: F401
 from . import model_utils, weights, check_point               # noqa: F401
+from .head_train import TrainableHeads, HeadBackward          # noqa: F401
 
 __version__ = '0.1.0'

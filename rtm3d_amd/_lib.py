@@ -221,6 +221,16 @@ class OptimHyperC(ctypes.Structure):
                 ('ema_d', c_float), ('ema_omd', c_float), ('reserved', c_int)]
 
 
+class HbMapC(ctypes.Structure):
+    """Mirror of struct rtm3d_hb_map (rtm3d_amd/head_train.py)."""
+    _fields_ = [('d', c_void_p), ('C', c_int), ('P', c_int), ('coff', c_int), ('gstride', c_int)]
+
+
+class HbRefreshJobC(ctypes.Structure):
+    """Mirror of struct rtm3d_hb_refresh_job."""
+    _fields_ = [('dst', c_void_p), ('perm', c_void_p), ('n', ctypes.c_longlong), ('kind', c_int), ('reserved', c_int)]
+
+
 # name -> (restype, argtypes); also the list of symbols include/rtm3d_hip.h declares
 SIGNATURES = {
     'rtm3d_last_error': (ctypes.c_char_p, []),
@@ -408,6 +418,19 @@ SIGNATURES = {
     'rtm3d_optim_plan': (c_int, [c_int, ctypes.POINTER(OptimSegmentC), ctypes.POINTER(OptimSegmentC), ctypes.POINTER(OptimChunkC),
                                  ctypes.POINTER(c_int)]),
     'rtm3d_optim_step': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(OptimHyperC), c_void_p, c_void_p]),
+    # head backward: dL/dlogits -> gradients of the head convs' parameters and of the fused map (rtm3d_amd/head_train.py)
+    'rtm3d_head_backward_check': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_float]),
+    'rtm3d_head_backward_slices': (c_int, [ctypes.c_longlong, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'rtm3d_head_backward_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'rtm3d_head_go': (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_void_p), c_float,
+                              ctypes.POINTER(HbMapC)]),
+    'rtm3d_head_wgrad': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(HbMapC),
+                                 ctypes.POINTER(HbMapC), c_float, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                 ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, c_void_p]),
+    'rtm3d_head_refresh_check': (c_int, [c_int, ctypes.POINTER(HbRefreshJobC)]),
+    'rtm3d_head_refresh': (c_int, [c_void_p, c_int, ctypes.POINTER(HbRefreshJobC), c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rtm3d_head_dgrad': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(HbMapC), c_void_p,
+                                 ctypes.POINTER(HbMapC), ctypes.POINTER(HbMapC)]),
 }
 
 _lib = None

@@ -1229,6 +1229,7 @@ class PlanRecorder(object):
             self.tids.append(tid.value)
         self.op_names = []                      # one entry per RECORDED runtime op (a fused pair records one)
         self.weight_ranges = []                 # per recorded conv: largest |weight| / |bias| as realized (after the level rewrites)
+        self.param_blobs = []                   # per recorded conv / headout: its blob ids and packing (head_train refreshes them in place)
         for L in self.lowering['launches']:
             getattr(self, '_rec_' + L['kind'])(L)
             self.op_names.append(L['name'])
@@ -1335,13 +1336,16 @@ class PlanRecorder(object):
         cout_pad = -(-op['cout'] // bn) * bn if bn else op['cout']
         biases = [np.pad(np.asarray(op['bias'][g], np.float32), (0, cout_pad - op['cout'])) for g in range(G)]
         d.w_blob, d.bias_blob = self._blob(np.concatenate(packed)), self._blob(np.concatenate(biases))
+        self.param_blobs.append({'name': op['name'], 'op': op, 'w_blob': int(d.w_blob), 'bias_blob': int(d.bias_blob), 'pack': pack, 'cout_pad': cout_pad})
         _lib.check(self.lib.rtm3d_op_conv(self.ctx, ctypes.byref(d)), 'op_conv ' + op['name'])
 
     def _rec_headout(self, L):
         op = L['op']
         w, b = pack_headout_weights(op['w'], op['bias'])
         co = (ctypes.c_int * 4)(*([x.shape[0] for x in op['w']] + [0] * (4 - len(op['w']))))
-        _lib.check(self.lib.rtm3d_op_headout(self.ctx, self.tids[op['inp'].tid], self._blob(w), self._blob(b), len(op['w']), co), 'op_headout')
+        wb, bb = self._blob(w), self._blob(b)
+        self.param_blobs.append({'name': op['name'], 'op': op, 'w_blob': wb, 'bias_blob': bb, 'pack': None, 'cout_pad': 16})
+        _lib.check(self.lib.rtm3d_op_headout(self.ctx, self.tids[op['inp'].tid], wb, bb, len(op['w']), co), 'op_headout')
 
     def _rec_quant_mx8(self, L):
         op = L['op']
@@ -1404,6 +1408,7 @@ class RealizedPlan(object):
         self.ctx = ctx
         self.lowering, self.unwritten = rec.lowering, rec.lowering['unwritten']
         self.tids, self.op_names, self.weight_ranges, self.yx_blob = rec.tids, rec.op_names, rec.weight_ranges, rec.yx_blob
+        self.param_blobs = rec.param_blobs
 
     def tensor_info(self, s):
         """(device address of padded element [0][0][0][0], B, H, W, C, border) of the tensor a Slice lives in."""
