@@ -2113,7 +2113,8 @@ int rtm3d_optim_step(void* stream, const rtm3d_optim_segment* d_segment_table, c
  * names a row {s, mean, beta} of the fp64 table bn (a conv without BN: {1, 0, 0}); perm[i] < 0 is a padding element, zero.
  * The caller builds perm ONCE by sending index arrays through the packers and guarantees 0 <= perm[i] < arena size or < 0.
  *
- * OUT OF SCOPE: the neck's and the backbone's backward (dz is the hand-off), training BatchNorm, head_precision = 'mxfp8'.  */
+ * OUT OF SCOPE: the backward upstream of dz (dz is the hand-off; "neck fusion backward" below takes it one stage up), training
+ * BatchNorm, head_precision = 'mxfp8'.  */
 #define RTM3D_HB_MAX_SLICES 256
 #define RTM3D_HB_MAX_JOBS 64
 enum { RTM3D_HB_E_NULL = 1, RTM3D_HB_E_SHAPE = 2, RTM3D_HB_E_GROUPS = 3, RTM3D_HB_E_CHANNELS = 4, RTM3D_HB_E_NUM_CONV = 5,
@@ -2156,6 +2157,70 @@ int rtm3d_head_dgrad(void* stream, int B, int H, int W, int n_out, int n_sum, in
 int rtm3d_head_refresh_check(int n_jobs, const rtm3d_hb_refresh_job* jobs);
 int rtm3d_head_refresh(void* stream, int n_jobs, const rtm3d_hb_refresh_job* h_jobs, const rtm3d_hb_refresh_job* d_jobs,
                        const float* d_arena, const int* d_scale_of, const double* d_bn);
+
+/* ---- neck fusion backward (rtm3d_amd/neck_train.py): from dz to the gradients of the fusion's transposed convs and of kfpn_h* ----
+ * The stage upstream of the heads' dz is the fusion half of the neck (models/nets/keypoint_fpn_fusion.py, forward):
+ *     z = z0 + sum_i u_i * softmax_{H W}(u_i.detach()),     u_i = fusion_up{i}(kfpn_h{i}),    i = 3, 4, 5
+ * where fusion_up{i} is a chain of i - 2 ConvTranspose2d(256, 256, k = 4, s = 2, p = 1, bias = False).  Here the operands are
+ * numbered l = 1 .. levels (levels = 3: l = 1 is kfpn_h3's chain of one transposed conv, l = 3 kfpn_h5's chain of three); the
+ * input of operand l is (H / 2^l) x (W / 2^l) for the H x W map of z.  The forward's tensors (kfpn_h*, the intermediate up maps,
+ * u_l) are the saved activations.
+ *
+ * THE RULE.  S: the heads' grad_scale.  T: a second power of two, the fusion scale - the softmax weights are about 1 / (H W), so
+ * du would underflow fp16 without it.  dz arrives as fp16 NHWC, times S.
+ *   1. dz0 = dz.  The SAME tensor: no launch, no copy - the gradient at z0 is the map the head backward wrote.
+ *   2. softmax statistics per operand l, image b, channel c:  m = max_p u_l[p],  Z = sum_p exp(u_l[p] - m),  exp in fp32.  The
+ *      pixels of an image are cut into at most 32 runs of R = 8 ceil(ceil(H W / 32) / 8) consecutive pixels; a run's (m, Z) is
+ *      formed by 8 lanes, lane j taking pixels j, j + 8 .. of the run in that order with a running maximum (Z <- Z exp(m_old -
+ *      m_new) + exp(u - m_new)), the 8 lanes are combined in lane order and the runs in index order, each as
+ *      Z = sum_k Z_k exp(m_k - max m).  The pass is this code's own: the forward's statistics belong to the plan and are not read.
+ *   3. du_l[p][c] = fp16( (T dz[p][c]) * (exp(u_l[p][c] - m) / Z) ), the softmax weight being detached in the reference: this is
+ *      the whole derivative.  Written to the interior of a map with a zero border of 1.
+ *   4. each transposed conv, last to first, with X (Hi x Wi) its input, dY (2 Hi x 2 Wi, zero border 1) the gradient at its output,
+ *      W its (ci, co, ky, kx) weight and Wf = fp16(W) the weight as the forward used it:
+ *          dW[ci][co][ky][kx] = 1 / (S T) sum_{b, y, x} X[y][x][ci] dY[2 y + ky - 1][2 x + kx - 1][co]
+ *          dX[y][x][ci] = fp16( sum_{ky, kx, co} dY[2 y + ky - 1][2 x + kx - 1][co] Wf[ci][co][ky][kx] )
+ *      dX is written on the interior of a map with border 1, which is the next transposed conv's dY; for the first of a chain it is
+ *      the FUSION-PATH term of d kfpn_h{i}, times S T (the kfpn_up path of the FPN half adds to it and is not built).
+ *   5. Every product is an fp16 x fp16 MFMA product with fp32 accumulation; the only fp16 roundings of gradients are the ones
+ *      written above.  dW leaves as fp32, unscaled, in torch's (cin, cout, 4, 4) order.
+ *   6. NO FLOAT ATOMICS.  The wgrad's sum over the B Hi Wi pixels uses the head backward's K-split over slices of whole 32-pixel
+ *      tiles (rtm3d_head_backward_slices); partials go to the workspace and are added in slice order, then multiplied by
+ *      1 / (S T).  Two runs on equal inputs leave equal bytes.  Every dW element that is NaN or +-Inf adds 1 to *d_nonfinite.
+ *
+ * MAPS are rtm3d_hb_map with gstride unused: 256 channels from coff on, of a tensor of C channels (a widened tensor: its real C).
+ * A gradient map's border must be ZERO; the launches write interiors only, so a map cleared once stays valid.
+ *
+ * ENTRY POINTS.  Raw device pointers plus geometry; the checks run on the HOST first and nothing is launched when they refuse
+ * (RTM3D_NB_E_*, the message in rtm3d_last_error): E_NULL a NULL argument; E_SHAPE B, H, W outside 1 .. 16384 or B H W >= 2^31;
+ * E_LEVELS levels (operands) outside 1 .. 3; E_CHANNELS a map that does not hold 256 channels at its offset in steps of 8;
+ * E_MULTIPLE a map H or W that is no multiple of 2^levels; E_SCALE a scale that is no power of two (or a product S T outside the
+ * fp32 range); E_SLICES a slice count outside 1 .. RTM3D_HB_MAX_SLICES; E_BORDER a border narrower than 1 on a dY / du map;
+ * E_ALIGN an address that is no multiple of 16 (4: the counter); E_WORKSPACE a workspace that is too small; E_LAUNCH.
+ * rtm3d_neck_backward_check and _workspace_bytes are HOST functions and run without a GPU.
+ *
+ * The weight refresh after an optimiser step is rtm3d_head_refresh as it is: kind 0, BN row 0 = {1, 0, 0}.
+ *
+ * OUT OF SCOPE: the FPN half of the neck (kfpn_up*, the composed proj + head 1x1 convs) and the backbone backward; graph-replayed
+ * plans; head_precision = 'mxfp8'; training BatchNorm.  */
+enum { RTM3D_NB_E_NULL = 1, RTM3D_NB_E_SHAPE = 2, RTM3D_NB_E_LEVELS = 3, RTM3D_NB_E_CHANNELS = 4, RTM3D_NB_E_MULTIPLE = 5,
+       RTM3D_NB_E_SCALE = 6, RTM3D_NB_E_SLICES = 7, RTM3D_NB_E_BORDER = 8, RTM3D_NB_E_ALIGN = 9, RTM3D_NB_E_WORKSPACE = 10,
+       RTM3D_NB_E_LAUNCH = 11 };
+int rtm3d_neck_backward_check(int B, int H, int W, int levels, float grad_scale, float fusion_scale);      /* H, W: the map of z */
+/* bytes that serve the softmax statistics of `levels` operands at batch B and every wgrad of n_slices slices; 0 for arguments the
+ * launches refuse */
+size_t rtm3d_neck_backward_workspace_bytes(int B, int levels, int n_slices);
+/* steps 2, 3 for n_ops operands (three launches).  dz: H x W, any border; u[n_ops], du[n_ops]: HOST arrays of maps, du with a zero
+ * border >= 1. */
+int rtm3d_neck_softmax_grad(void* stream, int B, int H, int W, int n_ops, const rtm3d_hb_map* dz, const rtm3d_hb_map* u,
+                            const rtm3d_hb_map* du, float fusion_scale, void* d_ws, size_t ws_bytes);
+/* step 4, dW of one transposed conv whose input is Hi x Wi.  d_dw: (256, 256, 4, 4) fp32, 16-byte aligned, or NULL (checked, then
+ * skipped). */
+int rtm3d_neck_deconv_wgrad(void* stream, int B, int Hi, int Wi, const rtm3d_hb_map* x, const rtm3d_hb_map* dy, float grad_scale,
+                            float fusion_scale, float* d_dw, int want_slices, void* d_ws, size_t ws_bytes, unsigned* d_nonfinite);
+/* step 4, dX.  d_wr: fp16 [tap = 4 ky + kx][ci = 256][co = 256] = Wf.permute(2, 3, 0, 1): no flip and no cin / cout swap, a
+ * ConvTranspose2d weight is (ci, co) already. */
+int rtm3d_neck_deconv_dgrad(void* stream, int B, int Hi, int Wi, const rtm3d_hb_map* dy, const void* d_wr, const rtm3d_hb_map* dx);
 
 #ifdef __cplusplus
 }

@@ -431,6 +431,14 @@ SIGNATURES = {
     'rtm3d_head_refresh': (c_int, [c_void_p, c_int, ctypes.POINTER(HbRefreshJobC), c_void_p, c_void_p, c_void_p, c_void_p]),
     'rtm3d_head_dgrad': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(HbMapC), c_void_p,
                                  ctypes.POINTER(HbMapC), ctypes.POINTER(HbMapC)]),
+    # neck fusion backward: dz -> gradients of the fusion_up transposed convs and of kfpn_h* (rtm3d_amd/neck_train.py)
+    'rtm3d_neck_backward_check': (c_int, [c_int, c_int, c_int, c_int, c_float, c_float]),
+    'rtm3d_neck_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'rtm3d_neck_softmax_grad': (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(HbMapC), ctypes.POINTER(HbMapC),
+                                        ctypes.POINTER(HbMapC), c_float, c_void_p, c_size_t]),
+    'rtm3d_neck_deconv_wgrad': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(HbMapC), ctypes.POINTER(HbMapC), c_float, c_float,
+                                        c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'rtm3d_neck_deconv_dgrad': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(HbMapC), c_void_p, ctypes.POINTER(HbMapC)]),
 }
 
 _lib = None
