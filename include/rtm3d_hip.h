@@ -2181,7 +2181,7 @@ int rtm3d_head_refresh(void* stream, int n_jobs, const rtm3d_hb_refresh_job* h_j
  *          dW[ci][co][ky][kx] = 1 / (S T) sum_{b, y, x} X[y][x][ci] dY[2 y + ky - 1][2 x + kx - 1][co]
  *          dX[y][x][ci] = fp16( sum_{ky, kx, co} dY[2 y + ky - 1][2 x + kx - 1][co] Wf[ci][co][ky][kx] )
  *      dX is written on the interior of a map with border 1, which is the next transposed conv's dY; for the first of a chain it is
- *      the FUSION-PATH term of d kfpn_h{i}, times S T (the kfpn_up path of the FPN half adds to it and is not built).
+ *      the FUSION-PATH term of d kfpn_h{i}, times S T (the kfpn_up path of the FPN half adds to it: "neck FPN backward" below).
  *   5. Every product is an fp16 x fp16 MFMA product with fp32 accumulation; the only fp16 roundings of gradients are the ones
  *      written above.  dW leaves as fp32, unscaled, in torch's (cin, cout, 4, 4) order.
  *   6. NO FLOAT ATOMICS.  The wgrad's sum over the B Hi Wi pixels uses the head backward's K-split over slices of whole 32-pixel
@@ -2201,8 +2201,8 @@ int rtm3d_head_refresh(void* stream, int n_jobs, const rtm3d_hb_refresh_job* h_j
  *
  * The weight refresh after an optimiser step is rtm3d_head_refresh as it is: kind 0, BN row 0 = {1, 0, 0}.
  *
- * OUT OF SCOPE: the FPN half of the neck (kfpn_up*, the composed proj + head 1x1 convs) and the backbone backward; graph-replayed
- * plans; head_precision = 'mxfp8'; training BatchNorm.  */
+ * OUT OF SCOPE: the FPN half of the neck (kfpn_up*, the composed proj + head 1x1 convs: "neck FPN backward" below) and the backbone
+ * backward; graph-replayed plans; head_precision = 'mxfp8'; training BatchNorm.  */
 enum { RTM3D_NB_E_NULL = 1, RTM3D_NB_E_SHAPE = 2, RTM3D_NB_E_LEVELS = 3, RTM3D_NB_E_CHANNELS = 4, RTM3D_NB_E_MULTIPLE = 5,
        RTM3D_NB_E_SCALE = 6, RTM3D_NB_E_SLICES = 7, RTM3D_NB_E_BORDER = 8, RTM3D_NB_E_ALIGN = 9, RTM3D_NB_E_WORKSPACE = 10,
        RTM3D_NB_E_LAUNCH = 11 };
@@ -2221,6 +2221,72 @@ int rtm3d_neck_deconv_wgrad(void* stream, int B, int Hi, int Wi, const rtm3d_hb_
 /* step 4, dX.  d_wr: fp16 [tap = 4 ky + kx][ci = 256][co = 256] = Wf.permute(2, 3, 0, 1): no flip and no cin / cout swap, a
  * ConvTranspose2d weight is (ci, co) already. */
 int rtm3d_neck_deconv_dgrad(void* stream, int B, int Hi, int Wi, const rtm3d_hb_map* dy, const void* d_wr, const rtm3d_hb_map* dx);
+
+/* ---- neck FPN backward (rtm3d_amd/fpn_train.py): from dz0 to the gradients of the FPN's convs and of the backbone features --------
+ * The stage upstream of the fusion is the FPN half of the neck (models/nets/keypoint_fpn_fusion.py, _fpn):
+ *     h5 = head5(feat3);   x_{i-1} = proj_i(cat[up_i(h_i), feat_{i-1}]),   h_{i-1} = head_{i-1}(x_{i-1}),   i = 5, 4, 3;   z0 = h2
+ * head / proj are 1x1 convs with bias, up_i is ConvTranspose2d(256, 256, k = 4, s = 2, p = 1, bias = False).  Nothing non-linear
+ * stands between proj_i and head_{i-1}, and the plan runs the pair as ONE composed 1x1 conv over the concat tensor
+ * ncat = [up(256) | feat]:  A = Wh Wp  (256 x Cin),  b = Wh bp + bh.  The backward is taken of that function, on the plan's TRAINING
+ * lowering (plan.lower(neck_fold=False)), which keeps ncat*, kfpn_h* and z0 as plain tensors - the saved activations.
+ *
+ * THE RULE.  S: the heads' grad_scale, T: the fusion scale, U: a third power of two, the fpn scale.  Levels k = 0, 1, 2 name the
+ * composed convs from the map of z0 (H x W) upwards: level k works at (H >> k) x (W >> k), X_k = ncat_k (Cin = 320 / 384 / 512 for
+ * DLA-34), A_k the composed weight, and its output is z0 (k = 0), kfpn_h3 (k = 1), kfpn_h4 (k = 2).  g_0 = dz, times S.
+ *   1. conv1x1 wgrad:   dA[co][ci] = inv sum_p dY[p][co] X[p][ci],    db[co] = inv sum_p dY[p][co]
+ *      with dY = g_k and inv the reciprocal of the factor g_k carries (1 / S at k = 0, 1 / (S U) behind it).
+ *   2. conv1x1 dgrad:   dX[p][ci] = fp16( mul sum_co dY[p][co] Af[co][ci] ),   Af = fp16(A) as the forward used it,
+ *      mul a power of two applied in fp32 before the rounding (U at k = 0, 1 behind it): D_k, Cin channels, times S U.
+ *      D_k[:, 256:] is d feat_k; D_k[:, :256] is the gradient at the output of kfpn_up{k+3}.
+ *   3. the transposed conv kfpn_up{k+3}: rtm3d_neck_deconv_wgrad (x = kfpn_h{k+3}, dy = D_k[:, :256], grad_scale = S, fusion_scale =
+ *      U) and rtm3d_neck_deconv_dgrad into E_k - "neck fusion backward", step 4, unchanged.
+ *   4. grad add:   g_{k+1}[p][c] = fp16( fp32(E_k[p][c]) + fp32(F_k[p][c]) r ),   r = U / T,
+ *      F_k being the fusion-path term of d kfpn_h{k+3} (times S T): g_{k+1} is the FULL gradient at kfpn_h{k+3}, times S U.
+ *   5. after level 2, kfpn_head5: step 1 with X = feat3 (Cin = 512), dY = g_3, and step 2 with mul = 1 into d feat3.
+ *   6. THE FACTOR RULE gives the reference's own parameters from the composed gradients, exactly (there is no non-linearity):
+ *          dWh = dA Wp^T + db bp^T,   dWp = Wh^T dA,   dbh = db,   dbp = Wh^T db
+ *      (head's input is Wp ncat + bp: proj's bias reaches head's weight) - weight-sized products, formed in fp64 by the caller
+ *      and stored as fp32.
+ *   7. Every product is an fp16 x fp16 MFMA product with fp32 accumulation; the only fp16 roundings of gradients are the ones
+ *      written above.  dA, db leave as fp32 in torch's (256, Cin, 1, 1) order.
+ *   8. NO FLOAT ATOMICS.  The wgrad's sum over the B H W pixels uses the head backward's K-split over slices of whole 32-pixel
+ *      tiles (rtm3d_head_backward_slices); partials go to the workspace and are added in slice order, then multiplied by inv.  The
+ *      bias sums use the head backward's rule: at most 1024 runs of ceil(B H W / 1024) consecutive pixels, added in pixel order
+ *      inside a run, the runs in index order.  Two runs on equal inputs leave equal bytes.  Every dA / db element that is NaN or
+ *      +-Inf adds 1 to *d_nonfinite.
+ *
+ * MAPS are rtm3d_hb_map with gstride unused: X and dX hold Cin channels from coff on, dY, E, F and g 256, of a tensor of C
+ * channels; any border 0 .. 64.  The launches write interiors only, so a gradient map whose border was cleared once stays valid
+ * for the transposed conv that reads it.  Cin: a multiple of 64 in 64 .. 1024.
+ *
+ * ENTRY POINTS.  Raw device pointers plus geometry; the checks run on the HOST first and nothing is launched when they refuse
+ * (RTM3D_FB_E_*, the message in rtm3d_last_error): E_NULL a NULL argument; E_SHAPE B, H, W outside 1 .. 16384 or B H W >= 2^31;
+ * E_CIN a Cin that is no multiple of 64 in 64 .. 1024; E_CHANNELS a map that does not hold its channels at its offset in steps of
+ * 8; E_SCALE an inv / mul / r that is no power of two (or whose reciprocal leaves the fp32 range); E_SLICES a slice count
+ * outside 1 .. RTM3D_HB_MAX_SLICES; E_BORDER a border outside 0 .. 64; E_ALIGN an address that is no multiple of 16 (4: db, the
+ * counter); E_WORKSPACE a workspace that is too small; E_LAUNCH.
+ * rtm3d_fpn_backward_check and _workspace_bytes are HOST functions and run without a GPU.
+ *
+ * The weight refresh after an optimiser step is rtm3d_head_refresh as it is (kinds 0 and 1, BN row 0 = {1, 0, 0}) over an arena
+ * that holds the composed A and b next to the parameters.
+ *
+ * OUT OF SCOPE: the backbone backward (d feat0 .. d feat3 are the hand-off); graph-replayed plans; head_precision = 'mxfp8';
+ * training BatchNorm.  */
+enum { RTM3D_FB_E_NULL = 1, RTM3D_FB_E_SHAPE = 2, RTM3D_FB_E_CIN = 3, RTM3D_FB_E_CHANNELS = 4, RTM3D_FB_E_SCALE = 5,
+       RTM3D_FB_E_SLICES = 6, RTM3D_FB_E_BORDER = 7, RTM3D_FB_E_ALIGN = 8, RTM3D_FB_E_WORKSPACE = 9, RTM3D_FB_E_LAUNCH = 10 };
+int rtm3d_fpn_backward_check(int B, int H, int W, int Cin, float factor);      /* H, W: the conv's own map; factor: an inv, mul or r */
+/* bytes that serve one wgrad of n_slices slices at Cin channels (weight partials and the 1024 bias runs); 0 for arguments the
+ * launches refuse */
+size_t rtm3d_fpn_backward_workspace_bytes(int Cin, int n_slices);
+/* step 1.  d_dA: (256, Cin, 1, 1) fp32, 16-byte aligned, or NULL; d_db: 256 fp32 or NULL - a NULL output is skipped and the other
+ * is the bits of the full call. */
+int rtm3d_fpn_conv1x1_wgrad(void* stream, int B, int H, int W, int Cin, const rtm3d_hb_map* x, const rtm3d_hb_map* dy, float inv,
+                            float* d_dA, float* d_db, int want_slices, void* d_ws, size_t ws_bytes, unsigned* d_nonfinite);
+/* step 2.  d_wr: fp16 [ci = Cin][co = 256] = Af transposed. */
+int rtm3d_fpn_conv1x1_dgrad(void* stream, int B, int H, int W, int Cin, const rtm3d_hb_map* dy, const void* d_wr, float mul,
+                            const rtm3d_hb_map* dx);
+/* step 4.  g may be E or F itself (each thread reads its own 16 bytes before it writes them). */
+int rtm3d_fpn_grad_add(void* stream, int B, int H, int W, const rtm3d_hb_map* e, const rtm3d_hb_map* f, float r, const rtm3d_hb_map* g);
 
 #ifdef __cplusplus
 }

@@ -9,5 +9,6 @@ from .ParamList import ParamList                              # noqa: F401
 from . import model_utils, weights, check_point               # noqa: F401
 from .head_train import TrainableHeads, HeadBackward          # noqa: F401
 from .neck_train import TrainableFusion, FusionBackward       # noqa: F401
+from .fpn_train import TrainableNeck, FpnBackward             # noqa: F401
 
 __version__ = '0.1.0'

@@ -439,6 +439,15 @@ SIGNATURES = {
     'rtm3d_neck_deconv_wgrad': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(HbMapC), ctypes.POINTER(HbMapC), c_float, c_float,
                                         c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'rtm3d_neck_deconv_dgrad': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(HbMapC), c_void_p, ctypes.POINTER(HbMapC)]),
+    # neck FPN backward: dz0 -> gradients of the composed 1x1 convs, kfpn_up* and the backbone features (rtm3d_amd/fpn_train.py)
+    'rtm3d_fpn_backward_check': (c_int, [c_int, c_int, c_int, c_int, c_float]),
+    'rtm3d_fpn_backward_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'rtm3d_fpn_conv1x1_wgrad': (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(HbMapC), ctypes.POINTER(HbMapC), c_float,
+                                        c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'rtm3d_fpn_conv1x1_dgrad': (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(HbMapC), c_void_p, c_float,
+                                        ctypes.POINTER(HbMapC)]),
+    'rtm3d_fpn_grad_add': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(HbMapC), ctypes.POINTER(HbMapC), c_float,
+                                   ctypes.POINTER(HbMapC)]),
 }
 
 _lib = None

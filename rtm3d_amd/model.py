@@ -167,10 +167,11 @@ class Model(object):
     def _precision(self, head_precision):
         return self.head_precision if head_precision is None else _check_precision(head_precision)
 
-    def _plan_for(self, B, H, W, device, heads='dense', head_precision=None):
+    def _plan_for(self, B, H, W, device, heads='dense', head_precision=None, neck_fold=None):
         """heads = 'dense': all branches on the whole map (Model.forward); 'peaks': the heat map alone plus the patch plan that
         evaluates the regression branches at the detected peaks (detect3d(sparse_heads=True), csrc/sparse_heads.hip).
-        head_precision: None = the model's; 'mxfp8' plans are kept under keys of their own."""
+        head_precision: None = the model's; 'mxfp8' plans are kept under keys of their own.
+        neck_fold: None = the default lowering; False = the training lowering (plan.lower), a dense plan under a key of its own."""
         if heads not in ('dense', 'peaks'):
             raise ValueError("heads must be 'dense' or 'peaks'")
         prec = self._precision(head_precision)
@@ -181,6 +182,10 @@ class Model(object):
         key = (B, H, W, device.index) if heads == 'dense' else (B, H, W, device.index, heads)
         if prec != 'fp16':
             key = key + (prec,)
+        if neck_fold is not None:
+            if heads != 'dense' or neck_fold:
+                raise ValueError("neck_fold: None (the default lowering) or False (the training lowering of a dense plan)")
+            key = key + ('neck_fold=False',)
         p = self._plans.get(key)
         if p is not None:
             self._plans[key] = self._plans.pop(key)          # most recently used last
@@ -197,7 +202,7 @@ class Model(object):
                                      num_classes=self._num_classes, dense_heads=1 if heads == 'peaks' else None,
                                      header_num_conv=self._num_conv, head_precision=prec)
             with torch.cuda.device(device):
-                p = plan_mod.RealizedPlan(ir, device.index)
+                p = plan_mod.RealizedPlan(ir, device.index, neck_fold=neck_fold)
                 # small batches are bound by launch gaps, not by the kernels: replay those plans as one hipGraph
                 use_graph = self.use_graph if self.use_graph is not None else B <= GRAPH_MAX_BATCH
                 p.set_graph(use_graph)
@@ -222,7 +227,7 @@ class Model(object):
             x = x.float()
         return x.contiguous()
 
-    def input_tensor(self, B, H, W, device=None, heads='dense', head_precision=None):
+    def input_tensor(self, B, H, W, device=None, heads='dense', head_precision=None, neck_fold=None):
         """(device address, border) of the fp16 NHWC4 input tensor of the plan for (B, H, W): the target of
         ``rtm3d_amd.preprocess.preprocess_batch(..., model=self)``.  heads: which plan ('dense' / 'peaks': they own separate
         workspaces) the following ``forward_logits(None, preloaded=..., heads=...)`` will replay."""
@@ -230,9 +235,9 @@ class Model(object):
         if dev is None or dev.type != 'cuda':
             raise RuntimeError('rtm3d_amd.Model.input_tensor needs a CUDA (ROCm) device; call model.to("cuda") first')
         dev = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
-        return self._plan_for(B, H, W, dev, heads, head_precision).input_tensor()
+        return self._plan_for(B, H, W, dev, heads, head_precision, neck_fold).input_tensor()
 
-    def forward_logits(self, x, preloaded=None, out=None, heads='dense', head_precision=None):
+    def forward_logits(self, x, preloaded=None, out=None, heads='dense', head_precision=None, neck_fold=None):
         """backbone -> neck -> heads: the four fp32 NCHW logit maps (models/model.py:21-23).
         preloaded=(B, H, W): ``x`` is None and the plan's input tensor was filled by preprocess_batch(model=self).
         out: where the logits go instead of four fresh tensors - a tuple of contiguous fp32 CUDA tensors of the logit
@@ -241,7 +246,8 @@ class Model(object):
         (rtm3d_forward), so a loop that holds on to its fresh outputs would pay a capture per call; with out= it replays one
         graph (the bs=1 detect.py loop).
         heads='peaks': only the heat-map branch is evaluated (a 1-tuple comes back); feed it to ``decode2d_sparse``.
-        head_precision: 'fp16' | 'mxfp8' for this call (None: the model's, Model(head_precision=...))."""
+        head_precision: 'fp16' | 'mxfp8' for this call (None: the model's, Model(head_precision=...)).
+        neck_fold: None, or False for the plan of the training lowering (_plan_for)."""
         if preloaded is not None:
             if x is not None:
                 raise ValueError('forward_logits: pass x=None with preloaded=(B, H, W)')
@@ -255,7 +261,7 @@ class Model(object):
             B, _, H, W = x.shape
             dev = x.device
             xptr = x.data_ptr()
-        plan = self._plan_for(B, H, W, dev, heads, head_precision)
+        plan = self._plan_for(B, H, W, dev, heads, head_precision, neck_fold)
         with torch.cuda.device(dev):
             shapes = [(B, c, H // 4, W // 4) for c in (self._head_channels if heads == 'dense' else self._head_channels[:1])]
             if out is None:

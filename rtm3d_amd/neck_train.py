@@ -25,9 +25,10 @@ S T (S: the heads' grad_scale); the weight gradients leave unscaled.  The defaul
 Labels or weights with larger gradients want a smaller T: an overflow shows as Inf / NaN weight gradients, which ``nonfinite()``
 counts.
 
-LEFT UNDONE: the FPN half of the neck (kfpn_up*, the composed proj + head 1x1 convs: the plan folds them away, their backward needs
-a training lowering first) and the backbone backward; graph-replayed plans; head_precision='mxfp8'; training BatchNorm.
-``input_grads()['kfpn_h*']`` are therefore the FUSION-PATH terms only: a later FPN backward adds the kfpn_up path to them.
+The FPN half of the neck (kfpn_up*, the composed proj + head 1x1 convs) is rtm3d_amd/fpn_train.py: ``TrainableNeck`` composes a
+TrainableFusion, runs the plan's training lowering and adds the kfpn_up path to ``input_grads()['kfpn_h*']``, which here are the
+FUSION-PATH terms only.
+LEFT UNDONE: the backbone backward; graph-replayed plans; head_precision='mxfp8'; training BatchNorm.
 """
 import ctypes
 
@@ -359,7 +360,7 @@ class TrainableFusion(object):
         """The gradients the last backward left at the inputs of the fusion: {'z0', 'kfpn_h3', 'kfpn_h4', 'kfpn_h5'}.  fp16 NHWC
         device tensors (views), 'z0' (dz itself: the same tensor, no copy) times grad_scale and the others times grad_scale *
         fusion_scale; with ``fp32=True`` fresh fp32 NCHW tensors, unscaled.  The kfpn_h* entries are the FUSION-PATH terms only:
-        a later FPN backward adds the kfpn_up path."""
+        fpn_train.TrainableNeck adds the kfpn_up path."""
         if self._last is None:
             raise RuntimeError('TrainableFusion.input_grads: run a backward first')
         fb = self._last['fb']

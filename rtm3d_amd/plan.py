@@ -1114,8 +1114,10 @@ def _launch(kind, name, ops, op, **decisions):
     return dict({'kind': kind, 'name': name, 'ops': ops, 'op': op, 's2d_out': None, 'write_out': True}, **decisions)
 
 
-def lower(P):
+def lower(P, neck_fold=None):
     """Plan P -> the runtime launches that record it, with every fusion, rewrite and kernel choice decided (no device).
+    neck_fold: None = the module's FOLD_NECK_UP; False = the TRAINING lowering, which skips _neck_up_folds: kfpn_up*, the composed
+    1x1 convs, kfpn_h* and the concat tensors stay plain launches and plain tensors (rtm3d_amd/fpn_train.py reads them back).
 
     Returns {'launches': [...], 'widen': {tensor id: extra channels for a space-to-depth copy}, 'stat_slots': {conv op index:
     softmax partials slot}, 'unwritten': {(tid, coff, C) of plan output slices no launch writes}, 's2d_only': {(tid, coff, C)
@@ -1126,7 +1128,7 @@ def lower(P):
     stat_slots = _softmax_stat_producers(P)
     tail = _level_tail_chains(P) if FUSE_LEVEL_TAIL else {}
     folds = _project_folds(P) if FOLD_PROJECT else {}
-    nfold = _neck_up_folds(P, tail, stat_slots) if FOLD_NECK_UP else []
+    nfold = _neck_up_folds(P, tail, stat_slots) if (FOLD_NECK_UP if neck_fold is None else neck_fold) else []
     s2d_only, s2d_readers, s2d_only_producers = _plan_s2d_only(P, nfold, tail, folds)
     stem = _stem_fusion_pairs(P) if FUSE_STEM else {}
     entry = _level_entry_triples(P) if FUSE_LEVEL_ENTRY else {}
@@ -1214,10 +1216,10 @@ class PlanRecorder(object):
     """The launches of lower(plan) issued on `lib`, one rtm3d_* call sequence per launch kind: tensor and blob creation and the
     rtm3d_op_* entries, nothing else.  `lib` is the ctypes library or anything with those entries (an engine export, a test's
     call log); `ctx` is handed through as their first argument and never looked at (None where `lib` has no context)."""
-    def __init__(self, plan, lib, ctx):
+    def __init__(self, plan, lib, ctx, neck_fold=None):
         self.lib, self.plan, self.cache, self.ctx = lib, plan, plan.cache, ctx
         self.yx_blob = None                     # blob of the peak coordinates: created by a patch plan's first patch_mask launch
-        self.lowering = lower(plan)
+        self.lowering = lower(plan) if neck_fold is None else lower(plan, neck_fold=neck_fold)      # (the default call as it always was)
         self.tids = []
         for i, t in enumerate(plan.tensors):
             tid = ctypes.c_int()
@@ -1395,13 +1397,14 @@ class PlanRecorder(object):
 
 class RealizedPlan(object):
     """A Plan recorded into a librtm3d_hip context of its own (PlanRecorder on the library), and the handle of that context."""
-    def __init__(self, plan, device_index):
+    def __init__(self, plan, device_index, neck_fold=None):
         lib = _lib.load()
         self.lib, self.plan, self.cache, self.peak, self.ctx = lib, plan, plan.cache, None, None
+        self.neck_fold = neck_fold              # None: the default lowering; False: the training lowering (lower)
         ctx = ctypes.c_void_p()
         _lib.check(lib.rtm3d_ctx_create(int(device_index), ctypes.byref(ctx)), 'ctx_create')
         try:
-            rec = PlanRecorder(plan, lib, ctx)
+            rec = PlanRecorder(plan, lib, ctx, neck_fold=neck_fold)
         except BaseException:
             lib.rtm3d_ctx_destroy(ctx)
             raise
